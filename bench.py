@@ -9,10 +9,13 @@ Cholesky -> right-hand side -> forward/backward block solves, all on device-resi
     python bench.py --gpus N --steps K --warmup W
 
 Protocol ("median and min reported"): W untimed warmup steps, then the K-step timed
-region -- barrier + synchronize on both sides, max over ranks -- is REPEATED (at least --repeats
-times and until --min-timed-ms of timed work has run); `value` = K / median region time, the
-regions' min / max / count ride along in `regions`.  No untimed pre-heating: a region that caught
-the clock ramp of a freshly started process shows up as `regions.max`.
+region -- barrier + synchronize on both sides, max over ranks.  By default it runs once, so exactly K
+steps are timed and `ms_per_step` is that region's time / K; with --repeats / --min-timed-ms it is
+REPEATED (at least --repeats times and until --min-timed-ms of timed work has run) and `value` = K /
+median region time, the regions' min / max / count ride along in `regions`.  Between the
+warmup and the timed region, untimed steps run for --preheat-ms (30 ms by default) so that the one
+region starts at steady clocks instead of catching the clock ramp of a freshly started process.  --dump-outputs DIR writes what the last timed step computed (y, the factorization
+flag) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
 
 N > 1: one process per GPU.  Started under torch.distributed.run the script is one rank; started
 plainly (`python bench.py --gpus N`) it launches torch.distributed.run on itself as a child
@@ -173,18 +176,43 @@ def newton_step_section(prob, device, ctx_stats):
                     "exists); kernel times from hipEvent pairs on the dispatch in one extra, instrumented solve"}
 
 
+def dump_outputs(out_dir, ctx, ok, rank):
+    """What a caller of the timed path receives from its last step: the Newton direction y (N
+    doubles) and the factorization flag of that step.  Sharded, cxk_get_y assembles the whole y
+    across the ranks (a collective: every rank calls this), and rank 0 writes; under --shard-path the
+    one-rank communicator leaves y with this GPU's shard alone."""
+    import numpy as np
+    y = ctx.get_y()
+    if rank != 0:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "y.npy"), np.asarray(y, dtype=np.float64))
+    np.save(os.path.join(out_dir, "factor_ok.npy"), np.array([1.0 if ok else 0.0]))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=7,
-                    help="the K-step timed region is repeated at least this many times; value = K / median")
-    ap.add_argument("--min-timed-ms", type=float, default=30.0,
-                    help="... and until this much timed work has run (a 20-step region of config 4 is 1 ms: seven "
-                         "of them would be over before a freshly started process has its clocks up)")
+    ap.add_argument("--repeats", type=int, default=1,
+                    help="the K-step timed region is repeated at least this many times; value = K / median "
+                         "(default 1: exactly --steps timed steps)")
+    ap.add_argument("--min-timed-ms", type=float, default=0.0,
+                    help="... and until this much timed work has run (default 0: off; a 20-step region of "
+                         "config 4 is 1 ms)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy, "
+                         "float64: y.npy, the Newton direction (sharded: assembled across the ranks; with "
+                         "--shard-path only this GPU's shard contributes, so y is repeatable but not the "
+                         "program's direction), and factor_ok.npy, the factorization flag of the last timed "
+                         "step (`config.factor_ok` is the AND over every step)"),
     ap.add_argument("--preheat", type=int, default=0,
                     help="extra untimed steps before the --warmup steps (default 0; reported as config.preheat_steps)")
+    ap.add_argument("--preheat-ms", type=float, default=30.0,
+                    help="after the --warmup steps, untimed steps until this much time has passed, so that "
+                         "the timed region starts at steady clocks (default 30; 0 = off; reported as "
+                         "config.preheat_ms)"),
     ap.add_argument("--K", type=int, default=1000)
     ap.add_argument("--workload", choices=["c4", "c2", "c3", "c5", "c4s", "maxcut"], default="c4",
                     help="c4 (default, the metric's config): 1000 LMIs n=20; c5 mixed complex Hermitian "
@@ -354,6 +382,7 @@ def main():
         """K-step regions, each bracketed by barrier + synchronize on both sides, max over ranks."""
         times = []
         okc = True
+        ok_last = True
         while len(times) < repeats or (sum(times) < min_total_s and len(times) < cap):
             fence()
             t0 = time.perf_counter()
@@ -361,20 +390,43 @@ def main():
                 c.kkt_solve_async(0.7, 0.9, 0.8)
             fence()
             el = time.perf_counter() - t0
-            okc = c.sync() and okc
+            ok_last = bool(c.sync())
+            okc = ok_last and okc
             if sharded:
                 t = torch.tensor([el], dtype=torch.float64)
                 dist.all_reduce(t, op=dist.ReduceOp.MAX)     # every rank sees the same number: same loop count
                 el = float(t.item())
             times.append(el)
-        return times, okc
+        return times, okc, ok_last
+
+    def preheat(c, ms):
+        """Untimed steps in batches of 10 until `ms` have passed; max over ranks, so every rank
+        runs the same number of steps."""
+        if ms <= 0:
+            return
+        fence()
+        t0 = time.perf_counter()
+        while True:
+            for _ in range(10):
+                c.kkt_solve_async(0.7, 0.9, 0.8)
+            c.sync()
+            el = time.perf_counter() - t0
+            if sharded:
+                t = torch.tensor([el], dtype=torch.float64)
+                dist.all_reduce(t, op=dist.ReduceOp.MAX)
+                el = float(t.item())
+            if el >= 1e-3 * ms:
+                return
 
     for _ in range(max(0, args.preheat) + args.warmup):
         ctx.kkt_solve_async(0.7, 0.9, 0.8)
     ok = ctx.sync()
-    times, okr = timed_regions(ctx, args.steps, args.repeats, 1e-3 * args.min_timed_ms)
+    preheat(ctx, args.preheat_ms)
+    times, okr, ok_last = timed_regions(ctx, args.steps, args.repeats, 1e-3 * args.min_timed_ms)
     ok = ok and okr
     med = statistics.median(times)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ctx, ok_last, rank)
 
     # N > 1 (and the one-GPU rehearsal): the SAME step unsharded on every rank, timed beside the sharded
     # one.  `value` stays the sharded layout's; the replicated rate is one rank's rate (NOT multiplied
@@ -386,7 +438,8 @@ def main():
         for _ in range(args.warmup):
             rep.kkt_solve_async(0.7, 0.9, 0.8)
         rep.sync()
-        rt, rok = timed_regions(rep, args.steps, min(args.repeats, 5), 0.5e-3 * args.min_timed_ms)
+        preheat(rep, args.preheat_ms)
+        rt, rok, _ = timed_regions(rep, args.steps, min(args.repeats, 5), 0.5e-3 * args.min_timed_ms)
         rmed = statistics.median(rt)
         replicated = {"value": args.steps / rmed, "us_per_step": 1e6 * rmed / args.steps,
                       "us_per_step_min": 1e6 * min(rt) / args.steps, "regions": len(rt), "factor_ok": bool(rok)}
@@ -422,6 +475,7 @@ def main():
             "unit": "KKT-solves/s",
             "n_gpus": world,
             "steps": args.steps,
+            "timed_steps": args.steps * len(times),
             "warmup": args.warmup,
             "ms_per_step": 1e3 * med / args.steps,
             "higher_is_better": True,
@@ -459,6 +513,7 @@ def main():
                        "fused_tree": bool(ctx.fused_tree()),
                        "n_ranks_seen": ctx.comm_count() if sharded else 1,
                        "preheat_steps": max(0, args.preheat),
+                       "preheat_ms": max(0.0, args.preheat_ms),
                        "factor_ok": bool(ok)},
         }
         if sharded:

@@ -8,6 +8,8 @@ reference's own known-answer tests in tests/test_oracle_kat.py, test_oracle_herm
 test_oracle_equality.py) on seeded inputs from conex_amd/synthetic.py:
 
     python tests/golden/make_golden.py
+    python tests/golden/make_golden.py --reference REFERENCE_ROOT   # the reference fixtures, see
+                                                                    # reference_fixtures()
 
 For every case: the permuted Newton direction y = K^-1 (k (b bs + AQc cs) - 2 AW), the
 assembled residual vectors, and the PrepareStep / eigenvalue summaries.  tests/test_golden.py
@@ -15,6 +17,7 @@ checks that (a) the oracle still reproduces them bit for bit (CPU suite) and (b)
 matches them to the stated tolerances (GPU suite) -- the latter needs neither the oracle nor
 /root/reference on the GPU box.
 """
+import json
 import os
 import sys
 
@@ -95,7 +98,33 @@ def run(p, W, b):
     return dict(y=y, AW=AW, AQc=AQc, sc=sc, eig=np.asarray(eig), info=np.asarray(info))
 
 
+def reference_fixtures(ref_root):
+    """The two fixtures that stand in for the reference tree (which only the build machine has):
+    ref_path_in_tree.npz, PathInTree of conex/tree_utils.cc as compiled into oracle/_ref (`make -C
+    oracle ref`) on the trees of test_oracle_kat.path_in_tree_cases, and reference_header.json, the
+    SHA-256 of interfaces/conex.h in test_abi's normalised form (prototype types, struct fields,
+    CONEX_* constants; no text of the header is stored)."""
+    import test_abi
+    import test_oracle_kat as kat
+    R = kat._ref_tree_lib()
+    if R is None:
+        raise SystemExit("oracle/_ref/libconex_ref_tree.so is not built (make -C oracle ref)")
+    paths = [kat._tree_path(R.ref_path_in_tree, x, y, parent, height)
+             for _, x, y, parent, height in kat.path_in_tree_cases()]
+    offsets = np.concatenate([[0], np.cumsum([len(q) for q in paths])]).astype(np.int32)
+    np.savez_compressed(os.path.join(HERE, "ref_path_in_tree.npz"),
+                        paths=np.concatenate(paths).astype(np.int32), offsets=offsets)
+    digest = test_abi.normalised_header_digest(os.path.join(ref_root, "interfaces", "conex.h"))
+    with open(os.path.join(HERE, "reference_header.json"), "w") as f:
+        json.dump({"interfaces/conex.h": {"normalised_sha256": digest}}, f, indent=1)
+        f.write("\n")
+    print("wrote ref_path_in_tree.npz and reference_header.json")
+
+
 def main():
+    if len(sys.argv) == 3 and sys.argv[1] == "--reference":
+        reference_fixtures(sys.argv[2])
+        return
     out = {}
     for name, (kind, prob, W, eqs) in cases().items():
         o = build(ol.Program, kind, prob, eqs)

@@ -2,6 +2,8 @@
 headers under include/ declare, and reproduces the status codes the reference's interface tests
 pin (interfaces/test/interface_test.cc:5-120, interface_test_soc.cc:5-65).  No compute calls."""
 import ctypes as C
+import hashlib
+import json
 import os
 import re
 
@@ -178,25 +180,34 @@ def _normalised_header(path):
     return protos, structs, defines
 
 
-REFERENCE_HEADER = "/root/reference/interfaces/conex.h"
+def normalised_header_digest(path):
+    """SHA-256 of _normalised_header(path) in a canonical JSON form."""
+    protos, structs, defines = _normalised_header(path)
+    canon = {"prototypes": {k: [r, list(ps)] for k, (r, ps) in protos.items()},
+             "structs": {k: [list(f) for f in v] for k, v in structs.items()},
+             "defines": defines}
+    return hashlib.sha256(json.dumps(canon, sort_keys=True).encode()).hexdigest()
 
 
-@pytest.mark.skipif(not os.path.exists(REFERENCE_HEADER),
-                    reason="the reference tree is only present in the build container")
+REFERENCE_HEADER = os.path.join(ROOT, "tests", "golden", "reference_header.json")
+
+
 def test_conex_h_equals_the_reference_header_prototype_by_prototype():
     """interfaces/conex.h:7-99 against include/conex.h: return types, argument TYPES in order, the
     field list (types, names, order) of CONEX_SolverConfiguration and the status constants.  The
-    symbol-name test above cannot see a swapped argument or a reordered field; this one does."""
+    symbol-name test above cannot see a swapped argument or a reordered field; this one does.  The
+    reference's side is the digest of its normalised header (tests/golden/reference_header.json,
+    tests/golden/make_golden.py --reference): the whole normalised form must be equal."""
     ours = _normalised_header(os.path.join(ROOT, "include", "conex.h"))
-    ref = _normalised_header(REFERENCE_HEADER)
-    assert len(ref[0]) == 21 and "CONEX_SolverConfiguration" in ref[1]
-    assert sorted(ours[0]) == sorted(ref[0])
-    for name, sig in ref[0].items():
-        assert ours[0][name] == sig, f"{name}: {ours[0][name]} != reference {sig}"
-    assert ours[1]["CONEX_SolverConfiguration"] == ref[1]["CONEX_SolverConfiguration"]
-    assert len(ref[1]["CONEX_SolverConfiguration"]) == 19
-    for name, val in ref[2].items():
-        assert ours[2].get(name) == val, name
+    assert len(ours[0]) == 21 and "CONEX_SolverConfiguration" in ours[1]
+    assert len(ours[1]["CONEX_SolverConfiguration"]) == 19
+    with open(REFERENCE_HEADER) as f:
+        ref = json.load(f)["interfaces/conex.h"]["normalised_sha256"]
+    assert normalised_header_digest(os.path.join(ROOT, "include", "conex.h")) == ref, (
+        "include/conex.h no longer equals the reference's interfaces/conex.h in normalised form; on a "
+        "machine with the reference, compare _normalised_header() of both files to see which prototype, "
+        "field or constant differs (tests/golden/make_golden.py --reference REFERENCE_ROOT remakes the "
+        "digest if the reference itself changed)")
 
 
 def test_ctypes_configuration_mirror_has_the_header_field_order():

@@ -61,12 +61,11 @@ def test_path_in_tree_literals(oracle):
     assert _path(2, 4, parent, height, L.cxo_path_in_tree) == [2, 1, 0, 3, 4]
 
 
-def test_path_in_tree_against_compiled_reference(oracle):
-    """oracle/_ref holds conex/tree_utils.cc compiled from the reference itself."""
-    R = _ref_tree_lib()
-    if R is None:
-        pytest.skip("oracle/_ref not built (reference absent)")
-    L = oracle.lib()
+GOLDEN_PATHS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_path_in_tree.npz")
+
+
+def path_in_tree_cases():
+    """50 seeded random trees: (n, x, y, parent, height)."""
     rng = np.random.default_rng(7)
     for _ in range(50):
         n = int(rng.integers(2, 40))
@@ -76,11 +75,30 @@ def test_path_in_tree_against_compiled_reference(oracle):
             parent[i] = rng.integers(0, i)
             height[i] = height[parent[i]] + 1
         x, y = int(rng.integers(0, n)), int(rng.integers(0, n))
-        o1 = np.zeros(2 * n + 2, dtype=np.int32)
-        o2 = np.zeros(2 * n + 2, dtype=np.int32)
-        n1 = L.cxo_path_in_tree(x, y, n, ip(parent), ip(height), ip(o1))
-        n2 = R.ref_path_in_tree(x, y, n, ip(parent), ip(height), ip(o2))
-        assert n1 == n2 and list(o1[:n1]) == list(o2[:n2])
+        yield n, x, y, parent, height
+
+
+def _tree_path(fn, x, y, parent, height):
+    out = np.zeros(2 * len(parent) + 2, dtype=np.int32)
+    k = fn(x, y, len(parent), ip(parent), ip(height), ip(out))
+    return out[:k].copy()
+
+
+def test_path_in_tree_against_compiled_reference(oracle):
+    """conex/tree_utils.cc compiled from the reference itself (oracle/_ref, made by `make -C oracle
+    ref`): its PathInTree outputs on the 50 trees are stored in tests/golden/ref_path_in_tree.npz
+    (tests/golden/make_golden.py --reference REFERENCE_ROOT); when oracle/_ref is built, it is
+    compared live too."""
+    L = oracle.lib()
+    R = _ref_tree_lib()
+    gold = np.load(GOLDEN_PATHS)
+    paths, offsets = gold["paths"], gold["offsets"]
+    for k, (n, x, y, parent, height) in enumerate(path_in_tree_cases()):
+        p1 = _tree_path(L.cxo_path_in_tree, x, y, parent, height)
+        assert list(p1) == list(paths[offsets[k]:offsets[k + 1]]), k
+        if R is not None:
+            assert list(p1) == list(_tree_path(R.ref_path_in_tree, x, y, parent, height)), k
+    assert len(offsets) == 51
 
 
 # --------------------------------------------------------------------------
