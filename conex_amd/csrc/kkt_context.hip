@@ -1147,6 +1147,7 @@ int DisableFusedTree(cxk_context* ctx) {
   ctx->fused_tree = false;
   ctx->fused_sweep = false;
   ctx->y3_valid = false;
+  ctx->y_deferred = false;  // (its three parts came from the launch that timed out)
   ctx->fused_timeouts++;
   fprintf(stderr, "conex_kkt_hip: a wait inside the whole-tree launch ran out (device shared with other work?); "
                   "this context sweeps its elimination tree level by level from now on\n");
@@ -1537,8 +1538,16 @@ int FlushDeferred(cxk_context* ctx, bool keep_scalars = false, bool keep_y = fal
   }
   return CXK_SUCCESS;
 }
+// The three solutions of cxk_factor_solve_triple_async hold for the b, the W, the slab and the factor of that
+// launch: an entry point that changes one of them drops them (a direction already asked for is formed first).
+int DropTriple(cxk_context* ctx) {
+  if (FlushDirection(ctx)) return CXK_FAILURE;
+  ctx->y3_valid = false;
+  return CXK_SUCCESS;
+}
 #define CXK_ENTER_KEEP(ctx)                     \
   if (CheckReady(ctx)) return CXK_FAILURE;      \
+  (ctx)->calls++;                               \
   DeviceGuard cxk_device_guard_((ctx)->device)
 #define CXK_ENTER(ctx)   \
   CXK_ENTER_KEEP(ctx);   \
@@ -2281,6 +2290,7 @@ int cxk_dual_size(const cxk_context* ctx, int i) {
 
 int cxk_set_identity(cxk_context* ctx) {
   CXK_ENTER(ctx);
+  if (DropTriple(ctx)) return CXK_FAILURE;
   for (Group& g : ctx->groups) {
     const size_t cnt = g.ids.size();
     if (cnt == 0) continue;
@@ -2325,6 +2335,7 @@ int cxk_get_W(cxk_context* ctx, int i, double* out) {
 
 int cxk_set_W(cxk_context* ctx, int i, const double* in) {
   CXK_ENTER(ctx);
+  if (DropTriple(ctx)) return CXK_FAILURE;
   CXK_DEMAND(i >= 0 && i < (int)ctx->cons.size() && ctx->cons[i].group >= 0, "invalid constraint");
   const ConstraintRec& c = ctx->cons[i];
   const size_t sz = (size_t)cxk_dual_size(ctx, i);
@@ -2494,6 +2505,7 @@ int ReduceStepInfoAndSync(cxk_context* ctx, int mode, const double* info, const 
 
 int cxk_factor_async(cxk_context* ctx) {
   CXK_ENTER(ctx);
+  if (DropTriple(ctx)) return CXK_FAILURE;
   // the gather that assembled the system has cleared the failure flag (GatherBody); a factorization
   // of a slab that came another way (cxk_set_slab, a second factorization) clears it here
   if (!ctx->fail_clean) CXK_TRY(hipMemsetAsync(ctx->d_fail.p, 0, sizeof(int), ctx->stream));
@@ -2589,6 +2601,7 @@ int cxk_step_scalars_async(cxk_context* ctx) {
 // direction, with (-bs, cs, 0) the right-hand side of ComputeMuFromDivergence (cone_program.cc:173-214).
 int cxk_factor_solve_async(cxk_context* ctx, double cb, double cq, double cw) {
   CXK_ENTER_KEEP(ctx);
+  if (DropTriple(ctx)) return CXK_FAILURE;
   const int N = ctx->md.N;
   if (ctx->asm_deferred && FusedAssembly(ctx)) {  // gather and right-hand side ride in the first factor level
     ctx->asm_deferred = false;
@@ -2610,6 +2623,7 @@ int cxk_factor_solve_async(cxk_context* ctx, double cb, double cq, double cw) {
   if (LaunchTree(ctx, 0, true, true)) return CXK_FAILURE;
   CXK_DEMAND(!ctx->asm_pending.on, "internal error: the folded assembly was not launched");
   ctx->factor_seq = ++ctx->seq;
+  ctx->redo_call = ctx->calls;
   return CXK_SUCCESS;
 }
 
@@ -2647,13 +2661,17 @@ int cxk_factor_solve_triple_async(cxk_context* ctx, double bs, double cs) {
   if (LaunchTree(ctx, 0, true, true)) return CXK_FAILURE;
   CXK_DEMAND(!ctx->asm_pending.on, "internal error: the folded assembly was not launched");
   ctx->factor_seq = ++ctx->seq;
+  ctx->redo_call = ctx->calls;
   ctx->y3_valid = true;
+  ctx->y3_bs = bs;
+  ctx->y3_cs = cs;
   return CXK_SUCCESS;
 }
 
 // cxk_factor_async + cxk_newton_direction in one upward pass: y <- K^-1 (k (b bs + AQc cs) - 2 AW).
 int cxk_factor_direction_async(cxk_context* ctx, double k, double bs, double cs) {
   CXK_ENTER_KEEP(ctx);
+  if (DropTriple(ctx)) return CXK_FAILURE;
   const int N = ctx->md.N;
   if (ctx->asm_deferred && FusedAssembly(ctx)) {
     ctx->asm_deferred = false;
@@ -2675,6 +2693,7 @@ int cxk_factor_direction_async(cxk_context* ctx, double k, double bs, double cs)
   if (LaunchTree(ctx, 0, true, true)) return CXK_FAILURE;
   CXK_DEMAND(!ctx->asm_pending.on, "internal error: the folded assembly was not launched");
   ctx->factor_seq = ++ctx->seq;
+  ctx->redo_call = ctx->calls;
   return CXK_SUCCESS;
 }
 
@@ -2691,9 +2710,16 @@ int cxk_sync(cxk_context* ctx, int* factor_ok) {
   if (FusedTimedOut(ctx) && ctx->world > 1) {
     timed_out = true;
     ctx->timeout_pending = false;
-  } else if (FusedTimedOut(ctx)) {  // redo the factor-and-solve level by level instead of reporting a failure
+  } else if (FusedTimedOut(ctx) && ctx->redo_call == ctx->calls - 1) {
+    // the factor-and-solve was the last call before this one: redo it level by level instead of reporting a failure
     if (RedoFactorSolveOnLevels(ctx) || SyncMailbox(ctx)) return CXK_FAILURE;
     CXK_TRY(hipStreamSynchronize(ctx->stream));
+  } else if (FusedTimedOut(ctx)) {
+    // other work went out behind it (a solve-only sweep, the mu selection, a direction, PrepareStep), or the
+    // inputs changed: the redo would not rebuild what it computed -- reported as cxk_factor_status does
+    if (DisableFusedTree(ctx)) return CXK_FAILURE;
+    ctx->timeout_unreported = true;
+    timed_out = true;
   }
   if (factor_ok) *factor_ok = ctx->mbv[10] == 0.0 && !timed_out;
   // fold finished timing samples
@@ -2710,6 +2736,7 @@ int cxk_sync(cxk_context* ctx, int* factor_ok) {
 
 int cxk_set_cost(cxk_context* ctx, const double* b) {
   CXK_ENTER(ctx);
+  if (DropTriple(ctx)) return CXK_FAILURE;
   const int N = ctx->md.N;
   std::vector<double> bp(N, 0.0);
   for (int i = 0; i < N; i++) {
@@ -2835,6 +2862,7 @@ int cxk_step_scalars(cxk_context* ctx, double* out6) {
 
 int cxk_kkt_solve_async(cxk_context* ctx, double k, double bs, double cs) {
   CXK_ENTER(ctx);
+  if (DropTriple(ctx)) return CXK_FAILURE;
   if (LaunchSchur(ctx)) return CXK_FAILURE;
   // single GPU, Cholesky, no refinement copies of the assembled system: the assembly rides in
   // the first factor level's launch (BuildPlans decides whether the tree allows it)
@@ -2854,6 +2882,7 @@ int cxk_kkt_solve_async(cxk_context* ctx, double k, double bs, double cs) {
   if (LaunchTree(ctx, 0, true, true)) return CXK_FAILURE;  // sharded contexts: local sweep, all-reduce, top, back
   CXK_DEMAND(!ctx->asm_pending.on, "internal error: the folded assembly was not launched");
   ctx->factor_seq = ++ctx->seq;
+  ctx->redo_call = ctx->calls;
   return CXK_SUCCESS;
 }
 
@@ -3183,7 +3212,7 @@ int cxk_newton_direction_device_mu(cxk_context* ctx, double bs, double cs) {
   CXK_DEMAND(DeviceMuOk(ctx) && ctx->mu_dev.n == 1, "cxk_newton_direction_device_mu: no barrier parameter on the device");
   // behind cxk_factor_solve_triple_async the direction is a combination of the three solutions at hand
   // (cone_program.cc:409-411 by linearity): one elementwise launch instead of a sweep over the tree
-  if (ctx->y3_valid) {
+  if (ctx->y3_valid && bs == ctx->y3_bs && cs == ctx->y3_cs) {  // (other scalings: the sweep below)
     ctx->y3_valid = false;
     ctx->y_deferred = true;  // normally combined inside the PrepareStep launch that follows (PrepareStepImpl)
     if (ctx->no_y_deferral && FlushDirection(ctx)) return CXK_FAILURE;
@@ -3222,6 +3251,7 @@ int cxk_get_slab(cxk_context* ctx, double* out) {
 }
 int cxk_set_slab(cxk_context* ctx, const double* in) {
   CXK_ENTER(ctx);
+  if (DropTriple(ctx)) return CXK_FAILURE;
   CXK_DEMAND(ctx->segments == 0, "cxk_set_slab needs the reference's block layout: CXK_CHAIN_SEGMENTS=0");
   CXK_TRY(hipStreamSynchronize(ctx->stream));
   CXK_TRY(hipMemcpy(ctx->slab.p, in, sizeof(double) * (size_t)ctx->lay.slab_size,

@@ -265,7 +265,8 @@ struct cxk_context {
   long long fx_fwd_stride = 0;
   unsigned fused_tgen = 0;
   DevBuf<double> y3;
-  bool y3_valid = false;
+  bool y3_valid = false;      // y3 holds the solutions for the current b, factor and slab (DropTriple clears it)
+  double y3_bs = 0, y3_cs = 0;  // the scalings they were formed with: another bs / cs solves instead
   bool y_deferred = false;  // the direction is still y3 and mu_dev: combined inside the PrepareStep launch that follows (or FlushDeferred)
   bool no_y_deferral = false;  // CXK_NO_Y_DEFERRAL=1 at cxk_create: the direction in a launch of its own (newton_from_three)
   DevBuf<unsigned long long> y_done;  // count of the direction's workgroups, all launches so far
@@ -277,6 +278,9 @@ struct cxk_context {
   int fused_timeouts = 0;            // times that happened (the whole-tree launch is given up at the first)
   bool timeout_pending = false;      // seen (and the slots rebuilt) by MakeFusedTreeArgs, not yet acted on
   bool timeout_unreported = false;   // ... and cxk_fused_tree_timed_out has not told the caller yet
+  // entry points called so far (CXK_ENTER), and the value at the end of the latest factor-and-solve: cxk_sync
+  // redoes a timed-out factor-and-solve silently only when nothing was called between it and the sync
+  long long calls = 0, redo_call = -1;
   bool asm_deferred = false;  // cxk_assemble ran the Schur kernels; the gather waits for the factorization that follows
   // solve-only sweeps whose every forward launch is a lean kernel form the right-hand side inside
   // those kernels (RhsIn) instead of in a launch of their own

@@ -244,7 +244,12 @@ int cxk_newton_direction_device_mu(cxk_context* ctx, double b_scaling, double c_
  * cxk_assemble, cxk_factor_solve_triple_async, cxk_select_mu_async, cxk_newton_direction_device_mu,
  * cxk_prepare_take_step_device_mu.  cxk_triple_supported: 1 where that applies (the tree in one launch on one
  * GPU, every constraint on the register LMI kernels, the barrier parameter on the device, no refinement)
- * AND the assembly just enqueued still waits to ride in the factorization (ask directly behind cxk_assemble). */
+ * AND the assembly just enqueued still waits to ride in the factorization (ask directly behind cxk_assemble).
+ * The three solutions hold for the b, W, slab and factor of that launch and for its b_scaling / c_scaling:
+ * cxk_set_cost, cxk_set_W, cxk_set_identity, cxk_set_slab, cxk_assemble, cxk_factor(_async),
+ * cxk_factor_solve_async, cxk_factor_direction_async and cxk_kkt_solve_async drop them (a direction already
+ * asked for is formed first), and a cxk_newton_direction_device_mu with other scalings than the launch's solves
+ * instead of combining them.  Solve-only sweeps (cxk_solve_rhs, cxk_newton_direction) and the queries keep them. */
 int cxk_triple_supported(cxk_context* ctx);
 int cxk_factor_solve_triple_async(cxk_context* ctx, double b_scaling, double c_scaling);
 /* cxk_prepare_take_step with c_weight = the device's inv_sqrt_mu * c_scaling; waits, and returns
@@ -401,8 +406,11 @@ int cxk_fused_tree(const cxk_context* ctx);
  * shared with other streams or processes a wait can run out.  That is not a failed factorization:
  * the context then gives the whole-tree launch up for good and sweeps level by level (kernel
  * boundaries instead of in-kernel waits).  cxk_sync redoes the pending factor-and-solve that way
- * itself; cxk_factor_status reports failure and this function returns 1 ONCE, so that an
- * interior-point loop (program.cc) redoes its iteration instead of giving up. */
+ * itself when that factor-and-solve was the last call before it; when anything else was called in
+ * between (a solve-only sweep, the mu selection, a direction, PrepareStep, new inputs) it reports
+ * failure instead, as cxk_factor_status always does.  After such a failure this function returns 1
+ * ONCE, so that the caller (the interior-point loop of program.cc) redoes its sequence instead of
+ * giving up. */
 int cxk_fused_tree_timed_out(cxk_context* ctx);
 /* test hook: pretend the latest whole-tree launch reported a wait that ran out */
 int cxk_debug_force_fused_timeout(cxk_context* ctx);
