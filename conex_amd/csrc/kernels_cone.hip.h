@@ -520,12 +520,18 @@ __device__ __forceinline__ void MailboxPack(const MailboxArgs& m) {
 // after the sum every rank holds every rank's values and combines them in RANK ORDER
 // (step_slots_reduce): min / max / sum as the mode asks, the sums in one fixed order on every rank.
 // mode 0: {sum normsqrd, max norminfd}; mode 1: {min lambda_min, max lambda_max, sum frob, sum trace}.
-__global__ void step_slots_fill(int rank, int world, const double* __restrict__ red, double* __restrict__ slots) {
+// Slot 4 world is the time-out mark (ShardMark, kernels_kkt.hip.h): a whole-tree launch of some rank whose wait ran
+// out travels with the reduction to every rank.
+__global__ void step_slots_fill(int rank, int world, const double* __restrict__ red, double* __restrict__ slots,
+                                const int* __restrict__ fail, int tag, const double* host_flag) {
   for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < 4 * world; q += gridDim.x * blockDim.x)
     slots[q] = (q >> 2) == rank ? red[q & 3] : 0.0;
+  if (blockIdx.x == 0 && threadIdx.x == 0) slots[4 * world] = ShardMark(fail, tag, host_flag);
 }
-__global__ void step_slots_reduce(int mode, int world, const double* __restrict__ slots, double* __restrict__ red) {
+__global__ void step_slots_reduce(int mode, int world, const double* __restrict__ slots, double* __restrict__ red,
+                                  int* __restrict__ fail, int tag) {
   if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  ShardMarkSeen(slots[4 * world], fail, tag);
   double v0 = slots[0], v1 = slots[1], v2 = slots[2], v3 = slots[3];
   for (int r = 1; r < world; r++) {
     const double* s = slots + 4 * r;

@@ -2175,9 +2175,27 @@ struct ExchangeArgs {
   double* sys_sc;
   int* fail;
   int tag;  // a failed pivot in a first level with the assembly folded in is reported as fail[1] == tag
+  const double* host_flag;  // pinned word a whole-tree launch's wait that ran out raises (ShardMark)
   double* x;
   double cb, cq, cw;
 };
+
+// The time-out mark of a sharded context's collectives behind a whole-tree factor launch (tag: that launch's).  A
+// wait of the launch that ran out leaves fail[1] = tag and the pinned host word raised (tree_fused.hip; a failed
+// pivot of the launch leaves fail[1] = tag alone).  The solve exchange and the step reductions carry 1.0 for it in
+// one extra summed slot, and every rank that receives a mark > 0 records it as a failed factorization (fail[0])
+// and a time-out of that launch (fail[2] = tag).  ResolveShardTimeout reads it.
+__device__ __forceinline__ double ShardMark(const int* fail, int tag, const double* host_flag) {
+  return tag != 0 && fail[1] == tag && __hip_atomic_load(host_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0.0
+             ? 1.0
+             : 0.0;
+}
+__device__ __forceinline__ void ShardMarkSeen(double mark, int* fail, int tag) {
+  if (mark > 0.0 && tag != 0) {
+    fail[0] = 1;
+    fail[2] = tag;
+  }
+}
 
 __global__ void __launch_bounds__(256) exchange_pack(ExchangeArgs a) {
   const int64_t gid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -2237,6 +2255,7 @@ __global__ void __launch_bounds__(256) exchange_unpack(ExchangeArgs a) {
 // variables travel, x[j] = sum of its published t values; after the sum all-reduce every rank
 // subtracts the total from its (replicated, complete) right-hand side of the top.
 __global__ void __launch_bounds__(256) exchange_pack_solve(ExchangeArgs a) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) a.x[a.n_xv] = ShardMark(a.fail, a.tag, a.host_flag);
   for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < a.n_xv; j += (int64_t)gridDim.x * blockDim.x) {
     double f = 0;
     for (int q = a.pf_ptr[j]; q < a.pf_ptr[j + 1]; q++) f += a.updb[a.pf_src[q]];
@@ -2244,6 +2263,7 @@ __global__ void __launch_bounds__(256) exchange_pack_solve(ExchangeArgs a) {
   }
 }
 __global__ void __launch_bounds__(256) exchange_unpack_solve(ExchangeArgs a) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) ShardMarkSeen(a.x[a.n_xv], a.fail, a.tag);
   for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < a.n_xv; j += (int64_t)gridDim.x * blockDim.x)
     a.y[a.xv_idx[j]] -= a.x[j];
 }

@@ -279,6 +279,7 @@ ExchangeArgs MakeExchange(cxk_context* ctx, double k, double bs, double cs) {
   a.y = ctx->y.p;
   a.sys_sc = ctx->sys_sc.p;
   a.fail = ctx->d_fail.p;
+  a.host_flag = ctx->fx_flag;
   a.tag = ctx->fail_tag;
   a.x = ctx->xbuf.p;
   a.cb = k * bs;
@@ -1050,6 +1051,22 @@ int MakeFusedTreeArgs(cxk_context* ctx, FusedTreeArgs* out) {
 int ShardAllReduce(cxk_context* ctx, double* buf, size_t count, int op);
 long ExchangeCount(const cxk_context* ctx);
 
+// Test hook (cxk_debug_fused_timeout_at): behind the launch just enqueued, what a wait of it that ran out
+// reports -- d_fail[1] = tag on the device and the pinned host word.  Nothing else.  The host
+// word is raised before this returns, or (CXK_DEBUG_FUSED_STREAM_ORDERED) by a host function on the stream,
+// as late as a launch that is still running when the host goes on would raise it.
+void RaiseHostWord(void* flag) { *static_cast<double*>(flag) = 1.0; }
+int DebugReportTimeout(cxk_context* ctx) {
+  CXK_TRY(hipMemcpyAsync(ctx->d_fail.p + 1, &ctx->asm_tag, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+  if (ctx->debug_stream_ordered) {
+    CXK_TRY(hipLaunchHostFunc(ctx->stream, RaiseHostWord, ctx->fx_flag));
+    return CXK_SUCCESS;
+  }
+  CXK_TRY(hipStreamSynchronize(ctx->stream));
+  *ctx->fx_flag = 1.0;
+  return CXK_SUCCESS;
+}
+
 // The factor-and-solve of a sharded context on the whole-tree kernels: own subtrees up with the pack of
 // the exchange buffer behind them (one launch), the sum all-reduce, the replicated top straight from
 // the buffer and the way back down the own subtrees (one launch).  Consumes the pending assembly.
@@ -1068,9 +1085,21 @@ int LaunchFusedShard(cxk_context* ctx) {
   a.cw = ap.cw;
   a.comb = ap.with_rhs == 2;
   a.done_target = ++ctx->fx_done_target;  // (up launches so far: kFusedShardUp's counters)
+  const bool hook = ctx->debug_timeout_at >= 0 && ctx->fused_launches++ == ctx->debug_timeout_at;
   CXK_TRY(LaunchFusedTree(a, ctx->fused_sa, ctx->fused_sb, kFusedShardUp, ctx->stream));
+  if (hook && ctx->debug_timeout_site == CXK_DEBUG_FUSED_SHARD_UP && DebugReportTimeout(ctx)) return CXK_FAILURE;
+  if (*ctx->fx_flag != 0.0) {
+    // a wait of this launch ran out and the host already sees it: make sure it travels (the launch's
+    // tail folds what it sees itself, ShardPackTail) -- failure word and time-out count of the exchange
+    static const double kTimedOut[2] = {1.0, 1.0};
+    CXK_TRY(hipMemcpyAsync(ctx->xbuf.p + ExchangeCount(ctx) - 2, kTimedOut, sizeof(kTimedOut), hipMemcpyHostToDevice,
+                           ctx->stream));
+  }
   if (ShardAllReduce(ctx, ctx->xbuf.p, (size_t)ExchangeCount(ctx), 0 /* kOpSum */)) return CXK_FAILURE;
+  ctx->shard_fused_tag = ctx->asm_tag;
+  ctx->shard_launch_collectives = ctx->collectives;  // (what has gone out behind the launch: ResolveShardTimeout)
   CXK_TRY(LaunchFusedTree(a, ctx->fused_sa, ctx->fused_sb, kFusedShardTop, ctx->stream));
+  if (hook && ctx->debug_timeout_site == CXK_DEBUG_FUSED_SHARD_TOP && DebugReportTimeout(ctx)) return CXK_FAILURE;
   return CXK_SUCCESS;
 }
 
@@ -1099,13 +1128,10 @@ int LaunchFusedTreeSolve(cxk_context* ctx) {
   } else {
     CXK_TRY(LaunchFusedTree(a, ctx->fused_sa, ctx->fused_sb, kFusedFull, ctx->stream, ctx->clk_e0, ctx->clk_e1));
   }
-  if (ctx->debug_timeout_at >= 0 && ctx->fused_launches++ == ctx->debug_timeout_at) {
-    // test hook (CXK_DEBUG_FUSED_TIMEOUT_AT=k at cxk_create): the k-th factor launch reports what a
-    // wait that ran out reports -- the tagged failure word on the device and the pinned host word
-    CXK_TRY(hipMemcpyAsync(ctx->d_fail.p + 1, &ctx->asm_tag, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    CXK_TRY(hipStreamSynchronize(ctx->stream));
-    *ctx->fx_flag = 1.0;
-  }
+  // test hook (CXK_DEBUG_FUSED_TIMEOUT_AT=k at cxk_create, or cxk_debug_fused_timeout_at): the k-th factor launch
+  if (ctx->debug_timeout_at >= 0 && ctx->fused_launches++ == ctx->debug_timeout_at &&
+      ctx->debug_timeout_site == CXK_DEBUG_FUSED_FACTOR && DebugReportTimeout(ctx))
+    return CXK_FAILURE;
   return CXK_SUCCESS;
 }
 
@@ -1380,6 +1406,7 @@ enum { kOpSum = 0, kOpMax = 1, kOpMin = 2 };
 // context's stream (RCCL) or complete on return (caller-supplied function).
 int ShardAllReduce(cxk_context* ctx, double* buf, size_t count, int op) {
   if (ctx->world <= 1 || count == 0) return CXK_SUCCESS;
+  ctx->collectives++;
   if (ctx->coll_fn) {
     CXK_DEMAND(ctx->coll_fn(ctx->coll_user, buf, (long)count, op, ctx->stream) == 0,
                "the caller-supplied all-reduce reported a failure");
@@ -1402,18 +1429,19 @@ long ExchangeCount(const cxk_context* ctx) { return (long)(ctx->n_xs + 3 * (int6
 // One sweep of a sharded context.  Bottom-up over this rank's subtrees (mode 0 factor [+ forward
 // substitution when with_rhs], mode 1 forward substitution), ONE sum all-reduce of what the
 // subtrees contribute to the replicated top of the tree --
-//   mode 0: [top slab entries | AW_T | AQc_T | forward values | <w,c> <c,Qc> | failure flag]
+//   mode 0: [top slab entries | AW_T | AQc_T | forward values | <w,c> <c,Qc> | failure flag | time-out count]
 //           (supernodal_assembler.cc:103-111,162-164 and block_triangular_operations.cc:209-215 are
 //            the sums that cross ranks here),
-//   mode 1: [forward values]  --
+//   mode 1: [forward values | time-out mark]  --
 // then the top on every rank (bit-identical: same data, same kernels) and, when `backward`, the
 // back-substitution down this rank's subtrees.
+int ShardedTop(cxk_context* ctx, int mode, bool rhs, bool backward);
 int ShardedTree(cxk_context* ctx, int mode, bool with_rhs, bool backward) {
   if (mode == 0 && with_rhs && backward && ctx->fused_tree && ctx->fused_shard && ctx->asm_pending.on &&
       ctx->asm_pending.with_rhs != 0)
     return LaunchFusedShard(ctx);
   if (ctx->use_ldlt && mode == 0) CXK_TRY(hipMemsetAsync(ctx->d_reg.p, 0, sizeof(int), ctx->stream));
-  const int nlev = ctx->nlev, cut = ctx->cut_level, top = ctx->top_level;
+  const int cut = ctx->cut_level;
   const bool rhs = with_rhs || mode != 0;
   for (int l = 0; l < cut; l++)
     if (LaunchSweep(ctx, l, l + 1, mode, false, rhs)) return CXK_FAILURE;
@@ -1431,13 +1459,21 @@ int ShardedTree(cxk_context* ctx, int mode, bool with_rhs, bool backward) {
     else
       exchange_unpack_matrix<<<GridFor(work, 256), 256, 0, ctx->stream>>>(a);
   } else if (ctx->n_xv > 0) {
+    a.tag = ctx->fx_flag ? ctx->shard_fused_tag : 0;  // (x[n_xv]: the time-out mark, ShardMark)
+    a.host_flag = ctx->fx_flag;
     exchange_pack_solve<<<GridFor((size_t)ctx->n_xv, 256), 256, 0, ctx->stream>>>(a);
     CXK_TRY(hipGetLastError());
-    if (ShardAllReduce(ctx, ctx->xbuf.p, (size_t)ctx->n_xv, kOpSum)) return CXK_FAILURE;
+    if (ShardAllReduce(ctx, ctx->xbuf.p, (size_t)ctx->n_xv + 1, kOpSum)) return CXK_FAILURE;
     exchange_unpack_solve<<<GridFor((size_t)ctx->n_xv, 256), 256, 0, ctx->stream>>>(a);
   }
   CXK_TRY(hipGetLastError());
-  // the replicated top: levels [cut, nlev)
+  return ShardedTop(ctx, mode, rhs, backward);
+}
+
+// The part of ShardedTree behind the exchange: the replicated top, levels [cut, nlev), and when
+// `backward` the way back down this rank's subtrees.
+int ShardedTop(cxk_context* ctx, int mode, bool rhs, bool backward) {
+  const int nlev = ctx->nlev, cut = ctx->cut_level, top = ctx->top_level;
   const bool chain = backward && rhs && ctx->chain_level < nlev && ctx->chain_level >= cut;
   const int up_end = chain ? ctx->chain_level : top;
   for (int l = cut; l < up_end; l++)
@@ -1458,6 +1494,84 @@ int ShardedTree(cxk_context* ctx, int mode, bool with_rhs, bool backward) {
       if (LaunchSweep(ctx, l, l + 1, 2, false, true)) return CXK_FAILURE;
     }
   return CXK_SUCCESS;
+}
+
+// A wait of this rank's kFusedShardTop ran out.  That launch ran behind the exchange, so no other rank
+// knows: this rank redoes its part on the level kernels without a collective -- the reduced exchange
+// buffer is still there (the top launch only reads it), the factor of its own subtrees is in the slab
+// (the top launch only reads that too), and the right-hand side is cb b + cq AQc + cw AW with the
+// coefficients of ctx->rhs_c.  Forward substitution down its subtrees again (the top launch may have
+// overwritten some of their y), the unpack, the top and the way back down: what ShardedTree does
+// around its all-reduce.
+int RedoShardTopOnLevels(cxk_context* ctx) {
+  if (DisableFusedTree(ctx)) return CXK_FAILURE;
+  const int N = ctx->md.N;
+  CXK_TRY(hipMemsetAsync(ctx->d_fail.p, 0, 3 * sizeof(int), ctx->stream));  // (the time-out mark with them)
+  build_rhs_comb<<<GridFor(N, 256), 256, 0, ctx->stream>>>(N, ctx->rhs_c[0], ctx->rhs_c[1], ctx->rhs_c[2], ctx->b.p,
+                                                           ctx->AQc.p, ctx->AW.p, ctx->y.p);
+  CXK_TRY(hipGetLastError());
+  for (int l = 0; l < ctx->cut_level; l++)
+    if (LaunchSweep(ctx, l, l + 1, 1, false, true)) return CXK_FAILURE;
+  ExchangeArgs a = MakeExchange(ctx, 0, 0, 0);
+  a.cb = ctx->rhs_c[0];
+  a.cq = ctx->rhs_c[1];
+  a.cw = ctx->rhs_c[2];
+  const size_t work = (size_t)std::max<int64_t>(std::max<int64_t>(ctx->n_xs, ctx->n_xv), 1);
+  exchange_unpack<<<GridFor(work, 256), 256, 0, ctx->stream>>>(a);
+  CXK_TRY(hipGetLastError());
+  return ShardedTop(ctx, 0, true, true);
+}
+
+extern "C" int SyncMailbox(cxk_context* ctx);  // (defined with the mailbox entry points)
+
+// Sharded contexts: what a time-out of a whole-tree launch means, settled once per factorization and the
+// same way on every rank.  Called with this rank's host word raised, or with the mailbox of the latest
+// factorization read and reporting failure.  Two marks that reach every rank tell the cases apart: the
+// exchange buffer's time-out count (ExchangeCount - 1: ShardPackTail, LaunchFusedShard), and d_fail[2] =
+// the launch's tag, which the solve exchanges and step reductions behind the launch set on every rank
+// when the launch's wait ran out on any (ShardMark).
+//   a mark: a wait of some rank's kFusedShardUp ran out (it travelled with the exchange), or one of its
+//        kFusedShardTop ran out and a solve sweep or step reduction went out behind it (it travelled with
+//        that): every rank's mailbox reports a failed factorization, every rank gives the whole-tree
+//        launch up (same collectives on the level kernels) and reports the time-out through
+//        cxk_fused_tree_timed_out -- the caller redoes its iteration on every rank.
+//   no mark, own word raised, no collective behind the launch: a wait of this rank's kFusedShardTop ran
+//        out and nothing has used it yet: RedoShardTopOnLevels, with no collective, and nothing is
+//        reported -- the other ranks cannot tell the difference.
+//   no mark, own word raised, collectives without a mark behind the launch (the step scalars: cxk_get_y
+//        and cxk_line_search settle first, SettleBeforeUnmarked): the same redo, so that the ranks stay
+//        in step, and a warning -- what those collectives carried came from the timed-out launch.
+int ResolveShardTimeout(cxk_context* ctx) {
+  if (ctx->world <= 1 || !ctx->fx_flag || ctx->shard_settled_seq == ctx->factor_seq) return CXK_SUCCESS;
+  const bool failed = ctx->mb && ctx->mb_seen >= ctx->factor_seq && ctx->mbv[10] != 0.0;
+  if (!failed && !FusedTimedOut(ctx)) return CXK_SUCCESS;  // (the success path: two host reads)
+  CXK_TRY(hipStreamSynchronize(ctx->stream));
+  const bool own = FusedTimedOut(ctx);
+  double up_count = 0;
+  int mark = 0;
+  CXK_TRY(hipMemcpy(&up_count, ctx->xbuf.p + ExchangeCount(ctx) - 1, sizeof(double), hipMemcpyDeviceToHost));
+  CXK_TRY(hipMemcpy(&mark, ctx->d_fail.p + 2, sizeof(int), hipMemcpyDeviceToHost));
+  ctx->shard_settled_seq = ctx->factor_seq;
+  if (up_count > 0 || (ctx->shard_fused_tag != 0 && mark == ctx->shard_fused_tag)) {
+    if (DisableFusedTree(ctx)) return CXK_FAILURE;
+    ctx->timeout_unreported = true;
+    CXK_TRY(hipMemsetAsync(ctx->d_fail.p + 1, 0, 2 * sizeof(int), ctx->stream));  // (settled: no mark goes out again)
+  } else if (own) {
+    if (ctx->collectives != ctx->shard_launch_collectives)
+      fprintf(stderr, "conex_kkt_hip: collectives without the time-out mark went out behind the timed-out "
+                      "whole-tree launch; what they carried from this rank is not trustworthy\n");
+    if (RedoShardTopOnLevels(ctx) || SyncMailbox(ctx)) return CXK_FAILURE;
+  }
+  return CXK_SUCCESS;
+}
+// Before a collective that carries no time-out mark: a launch still unsettled with nothing behind it yet is
+// settled first (the stream is waited for once per factorization, only by these entry points).
+int SettleBeforeUnmarked(cxk_context* ctx) {
+  if (ctx->world <= 1 || !ctx->fx_flag || ctx->shard_settled_seq == ctx->factor_seq ||
+      ctx->shard_fused_tag == 0 || ctx->collectives != ctx->shard_launch_collectives)
+    return CXK_SUCCESS;
+  CXK_TRY(hipStreamSynchronize(ctx->stream));
+  return ResolveShardTimeout(ctx);
 }
 
 int CheckReady(cxk_context* ctx) {
@@ -1548,7 +1662,8 @@ int DropTriple(cxk_context* ctx) {
 #define CXK_ENTER_KEEP(ctx)                     \
   if (CheckReady(ctx)) return CXK_FAILURE;      \
   (ctx)->calls++;                               \
-  DeviceGuard cxk_device_guard_((ctx)->device)
+  DeviceGuard cxk_device_guard_((ctx)->device); \
+  if (ResolveShardTimeout(ctx)) return CXK_FAILURE
 #define CXK_ENTER(ctx)   \
   CXK_ENTER_KEEP(ctx);   \
   if (FlushDeferred(ctx)) return CXK_FAILURE
@@ -2188,7 +2303,8 @@ static int FinalizeImpl(cxk_context* ctx) {
   CXK_TRY(ctx->sys_sc.alloc(2));
   CXK_TRY(ctx->red_out.alloc(4));
   CXK_TRY(ctx->scal_out.alloc(8));
-  CXK_TRY(ctx->d_fail.alloc(2, true));
+  // [flag, tag of a failed fused pivot or time-out, tag of a time-out some rank reported (ShardMark)]
+  CXK_TRY(ctx->d_fail.alloc(3, true));
   ctx->use_ldlt = false;
   for (const IntList& dv : ctx->dual_vars)
     if (!dv.empty()) ctx->use_ldlt = true;  // kkt_solver.cc:180-186
@@ -2493,11 +2609,15 @@ int ReduceStepInfoAndSync(cxk_context* ctx, int mode, const double* info, const 
   // sharded: every rank reduced its own constraints; ONE sum all-reduce of a (world x 4)-slot buffer
   // brings all partial results to every rank, which combines them in rank order (kernels_cone.hip.h:
   // sum / max for mode 0, min / max / sum / sum for mode 1 -- two or three collectives before)
-  if (ctx->step_slots.n != (size_t)4 * ctx->world) CXK_TRY(ctx->step_slots.alloc((size_t)4 * ctx->world));
-  step_slots_fill<<<1, 64, 0, ctx->stream>>>(ctx->rank, ctx->world, ctx->red_out.p, ctx->step_slots.p);
+  // (+ the time-out mark of the latest whole-tree launch: ShardMark)
+  const size_t nslots = (size_t)4 * ctx->world + 1;
+  if (ctx->step_slots.n != nslots) CXK_TRY(ctx->step_slots.alloc(nslots));
+  step_slots_fill<<<1, 64, 0, ctx->stream>>>(ctx->rank, ctx->world, ctx->red_out.p, ctx->step_slots.p, ctx->d_fail.p,
+                                             ctx->fx_flag ? ctx->shard_fused_tag : 0, ctx->fx_flag);
   CXK_TRY(hipGetLastError());
-  if (ShardAllReduce(ctx, ctx->step_slots.p, (size_t)4 * ctx->world, kOpSum)) return CXK_FAILURE;
-  step_slots_reduce<<<1, 64, 0, ctx->stream>>>(mode, ctx->world, ctx->step_slots.p, ctx->red_out.p);
+  if (ShardAllReduce(ctx, ctx->step_slots.p, nslots, kOpSum)) return CXK_FAILURE;
+  step_slots_reduce<<<1, 64, 0, ctx->stream>>>(mode, ctx->world, ctx->step_slots.p, ctx->red_out.p, ctx->d_fail.p,
+                                               ctx->shard_fused_tag);
   CXK_TRY(hipGetLastError());
   ctx->seq++;
   return SyncMailbox(ctx);
@@ -2518,12 +2638,9 @@ int cxk_factor_async(cxk_context* ctx) {
 int cxk_factor_status(cxk_context* ctx, int* ok) {
   CXK_ENTER(ctx);
   if (ctx->mb_seen < ctx->factor_seq && SyncMailbox(ctx)) return CXK_FAILURE;
+  if (ResolveShardTimeout(ctx)) return CXK_FAILURE;  // (sharded: settled the same way on every rank)
   if (ok) *ok = (ctx->mb ? (ctx->mbv[10] == 0.0) : 1) && !FusedTimedOut(ctx);
-  if (FusedTimedOut(ctx) && ctx->world > 1) {
-    // (sharded: the ranks must keep issuing the same collectives -- reported as a failed
-    // factorization, the slots are rebuilt by the next whole-tree launch)
-    ctx->timeout_pending = false;
-  } else if (FusedTimedOut(ctx)) {
+  if (FusedTimedOut(ctx) && ctx->world <= 1) {
     // not a property of the matrix: the caller learns it through cxk_fused_tree_timed_out and redoes
     // its iteration, which then runs on the level kernels
     if (DisableFusedTree(ctx)) return CXK_FAILURE;
@@ -2706,10 +2823,10 @@ int cxk_sync(cxk_context* ctx, int* factor_ok) {
   CXK_ENTER(ctx);
   if (SyncMailbox(ctx)) return CXK_FAILURE;
   CXK_TRY(hipStreamSynchronize(ctx->stream));  // the stream is idle: cheap, and later host-side copies rely on it
+  if (ResolveShardTimeout(ctx)) return CXK_FAILURE;  // (sharded: settled the same way on every rank)
   bool timed_out = false;
-  if (FusedTimedOut(ctx) && ctx->world > 1) {
-    timed_out = true;
-    ctx->timeout_pending = false;
+  if (ctx->world > 1) {
+    // (nothing left to settle: ResolveShardTimeout has, and a time-out every rank saw fails the mailbox)
   } else if (FusedTimedOut(ctx) && ctx->redo_call == ctx->calls - 1) {
     // the factor-and-solve was the last call before this one: redo it level by level instead of reporting a failure
     if (RedoFactorSolveOnLevels(ctx) || SyncMailbox(ctx)) return CXK_FAILURE;
@@ -2829,6 +2946,7 @@ int cxk_line_search(cxk_context* ctx, double dinf_upper_bound, double b_scaling,
   std::vector<double> out((size_t)2 * K);
   const double* pairs = ctx->info2.p;
   if (ctx->world > 1) {  // every rank evaluated its own linear constraints: gather the bounds
+    if (SettleBeforeUnmarked(ctx)) return CXK_FAILURE;
     CXK_DEMAND((size_t)2 * K <= ctx->shard_tmp.n, "internal error: shard scratch too small");
     masked_copy_pairs<<<GridFor((size_t)2 * K, 256), 256, 0, ctx->stream>>>(K, ctx->d_mask.p, ctx->info2.p, ctx->shard_tmp.p);
     CXK_TRY(hipGetLastError());
@@ -2902,6 +3020,7 @@ int cxk_get_y(cxk_context* ctx, double* yh) {
   // a rank holds y for its own subtrees and the top: assemble the whole vector (callers that run
   // the exchange themselves, without a communicator, get the local vector: cxk_get_valid_variables)
   if (ctx->world > 1 && (ctx->coll_fn || ctx->rccl.comm)) {
+    if (SettleBeforeUnmarked(ctx)) return CXK_FAILURE;
     masked_copy<<<GridFor(N, 256), 256, 0, ctx->stream>>>(N, ctx->d_count_mask.p, ctx->y.p, ctx->shard_tmp.p);
     CXK_TRY(hipGetLastError());
     if (ShardAllReduce(ctx, ctx->shard_tmp.p, (size_t)N, kOpSum)) return CXK_FAILURE;
@@ -3456,6 +3575,23 @@ int cxk_fused_tree_timed_out(cxk_context* ctx) {
 int cxk_debug_force_fused_timeout(cxk_context* ctx) {
   if (!ctx || !ctx->fx_flag || !ctx->fused_tree) return CXK_FAILURE;
   *ctx->fx_flag = 1.0;
+  return CXK_SUCCESS;
+}
+
+int cxk_debug_fused_timeout_at(cxk_context* ctx, int launch_index, int which) {
+  if (!ctx || !ctx->device_ready || !ctx->fx_flag || !ctx->fused_tree) return CXK_FAILURE;
+  const bool stream_ordered = (which & CXK_DEBUG_FUSED_STREAM_ORDERED) != 0;
+  which &= ~CXK_DEBUG_FUSED_STREAM_ORDERED;
+  // (behind the up launch, only a host word raised in time reaches the exchange: stream order is for the top)
+  if (stream_ordered && which != CXK_DEBUG_FUSED_SHARD_TOP) return CXK_FAILURE;
+  if (which != CXK_DEBUG_FUSED_FACTOR && which != CXK_DEBUG_FUSED_SHARD_UP && which != CXK_DEBUG_FUSED_SHARD_TOP)
+    return CXK_FAILURE;
+  // (a site this context never launches would never fire: refused, so that a test cannot pass vacuously)
+  if ((which == CXK_DEBUG_FUSED_FACTOR) != (ctx->world <= 1) || (ctx->world > 1 && !ctx->fused_shard))
+    return CXK_FAILURE;
+  ctx->debug_timeout_at = launch_index >= 0 ? ctx->fused_launches + launch_index : -1;
+  ctx->debug_timeout_site = which;
+  ctx->debug_stream_ordered = stream_ordered;
   return CXK_SUCCESS;
 }
 

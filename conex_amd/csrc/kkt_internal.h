@@ -274,10 +274,19 @@ struct cxk_context {
   bool no_triple = false;  // CXK_NO_TRIPLE=1 at cxk_create: the mu selection's solve and the Newton direction as two sweeps
   unsigned fused_gen = 0;
   double* fx_flag = nullptr;  // pinned host word the kernel sets when a wait ran out
-  int debug_timeout_at = -1, fused_launches = 0;  // CXK_DEBUG_FUSED_TIMEOUT_AT (test hook, LaunchFusedTreeSolve)
+  // test hook (cxk_debug_fused_timeout_at, CXK_DEBUG_FUSED_TIMEOUT_AT): the whole-tree factor launch number
+  // debug_timeout_at (counted in fused_launches) reports a wait that ran out after its launch `debug_timeout_site`
+  int debug_timeout_at = -1, debug_timeout_site = 0, fused_launches = 0;
   int fused_timeouts = 0;            // times that happened (the whole-tree launch is given up at the first)
   bool timeout_pending = false;      // seen (and the slots rebuilt) by MakeFusedTreeArgs, not yet acted on
   bool timeout_unreported = false;   // ... and cxk_fused_tree_timed_out has not told the caller yet
+  // sharded contexts: the factorization (factor_seq) whose time-outs ResolveShardTimeout has settled
+  long long shard_settled_seq = -1;
+  // ... the tag of its latest whole-tree factor launch (0: none), the collectives issued so far (ShardAllReduce)
+  // and their number when that launch's own all-reduce had gone out
+  int shard_fused_tag = 0;
+  long long collectives = 0, shard_launch_collectives = 0;
+  bool debug_stream_ordered = false;  // cxk_debug_fused_timeout_at: the host word raised by a host function on the stream
   // entry points called so far (CXK_ENTER), and the value at the end of the latest factor-and-solve: cxk_sync
   // redoes a timed-out factor-and-solve silently only when nothing was called between it and the sync
   long long calls = 0, redo_call = -1;

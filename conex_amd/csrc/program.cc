@@ -78,6 +78,7 @@ struct Program {
   int reference_identity = -1;  // -1: environment (CXK_REFERENCE_QUIRKS); see CONEX_HIP_SetReferenceIdentity
   // multi-GPU (one process per GPU, every rank builds the same program): see CONEX_HIP_SetCommunicator
   int shard_rank = 0, shard_world = 1;
+  int debug_timeout_at = -1, debug_timeout_site = 0;  // CONEX_HIP_DebugFusedTimeoutAt (test hook)
   bool have_unique_id = false;
   unsigned char unique_id[128] = {0};
   cxk_allreduce_fn allreduce_fn = nullptr;
@@ -205,6 +206,9 @@ int BuildContext(Program* p) {
     CONEX_DEMAND(id >= 0, "constraint rejected while building the device program");
   }
   CONEX_DEMAND(cxk_finalize(p->ctx) == CXK_SUCCESS, cxk_last_error(p->ctx));
+  if (p->debug_timeout_at >= 0)
+    CONEX_DEMAND(cxk_debug_fused_timeout_at(p->ctx, p->debug_timeout_at, p->debug_timeout_site) == CXK_SUCCESS,
+                 "CONEX_HIP_DebugFusedTimeoutAt: the context makes no such whole-tree launch");
   p->dirty = false;
   return 0;
 }
@@ -1142,6 +1146,17 @@ int CONEX_HIP_ReadKernelClocks(void* x, double* avg_ms, int* samples) {
   if (!p || !p->ctx || !avg_ms || !samples) return CONEX_FAILURE;
   if (cxk_sync(p->ctx, nullptr) != CXK_SUCCESS) return CONEX_FAILURE;  // folds the finished event pairs
   for (int k = 0; k < CXK_CLOCK_COUNT; k++) samples[k] = cxk_kernel_clock(p->ctx, k, 1, &avg_ms[k]);
+  return CONEX_SUCCESS;
+}
+
+/* not part of conex.h, test hook: cxk_debug_fused_timeout_at on the context the next solve builds (the
+ * launch_index-th whole-tree factor launch of that solve reports a wait that ran out behind its launch `which`) */
+int CONEX_HIP_DebugFusedTimeoutAt(void* x, int launch_index, int which) {
+  Program* p = static_cast<Program*>(x);
+  if (!p) return CONEX_FAILURE;
+  p->debug_timeout_at = launch_index;
+  p->debug_timeout_site = which;
+  p->dirty = true;
   return CONEX_SUCCESS;
 }
 

@@ -1188,7 +1188,7 @@ __device__ __forceinline__ void ShardPackItem(const FusedTreeArgs& A, int64_t it
 }
 
 // The buffer's tail: this rank's part of <w,c> and <c,Qc> (FusedScalars' sums; constraints of other
-// ranks hold zeros) and the failure flag -- read once every supernode of the launch has counted
+// ranks hold zeros), the failure flag and the time-out count -- read once every supernode of the launch has counted
 // itself done, so that a failed pivot anywhere in this rank's subtrees travels with the exchange.
 __device__ __forceinline__ void ShardPackTail(const FusedTreeArgs& A) {
   FusedScalars(A);
@@ -1216,8 +1216,12 @@ __device__ __forceinline__ void ShardPackTail(const FusedTreeArgs& A) {
     const int f1 = __hip_atomic_load(A.fail + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     A.x[o] = A.sys_sc[0];
     A.x[o + 1] = A.sys_sc[1];
-    A.x[o + 2] = (f0 != 0 || (A.tag != 0 && f1 == A.tag)) ? 1.0 : 0.0;
-    A.x[o + 3] = 0;
+    const bool tagged = A.tag != 0 && f1 == A.tag;
+    A.x[o + 2] = (f0 != 0 || tagged) ? 1.0 : 0.0;
+    // the time-out count: every rank learns that a wait of this launch ran out (ResolveShardTimeout).  A
+    // failed pivot of the first level writes the same tagged word; the host word, raised beside it by a
+    // wait that ran out, tells the two apart -- read only then, nothing more is read when nothing failed.
+    A.x[o + 3] = tagged && __hip_atomic_load(A.host_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0.0 ? 1.0 : 0.0;
   }
 }
 

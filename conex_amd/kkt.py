@@ -124,6 +124,7 @@ _SIGNATURES = {
     "cxk_chain_segments": (C.c_int, [C.c_void_p]),
     "cxk_fused_tree_timed_out": (C.c_int, [C.c_void_p]),
     "cxk_debug_force_fused_timeout": (C.c_int, [C.c_void_p]),
+    "cxk_debug_fused_timeout_at": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "cxk_set_iterative_refinement": (C.c_int, [C.c_void_p, C.c_int]),
 }
 
@@ -428,6 +429,12 @@ class KktContext:
         self._check(self.L.cxk_step_scalars(self.h, _dp(out)), "cxk_step_scalars")
         return out
 
+    def factor_status(self):
+        """1 when the latest factorization succeeded (cxk_factor_status)."""
+        ok = C.c_int(0)
+        self._check(self.L.cxk_factor_status(self.h, C.byref(ok)), "cxk_factor_status")
+        return ok.value
+
     def kkt_solve_async(self, inv_sqrt_mu, b_scaling=1.0, c_scaling=1.0):
         self._check(self.L.cxk_kkt_solve_async(self.h, inv_sqrt_mu, b_scaling, c_scaling),
                     "cxk_kkt_solve_async")
@@ -659,6 +666,14 @@ class KktContext:
 
     def debug_force_fused_timeout(self):
         self._check(self.L.cxk_debug_force_fused_timeout(self.h), "cxk_debug_force_fused_timeout")
+
+    # cxk_debug_fused_timeout_at's sites
+    DEBUG_FUSED_FACTOR, DEBUG_FUSED_SHARD_UP, DEBUG_FUSED_SHARD_TOP, DEBUG_FUSED_STREAM_ORDERED = 0, 1, 2, 16
+
+    def debug_fused_timeout_at(self, launch_index, which):
+        """Test hook: the launch_index-th whole-tree factor launch from now reports a wait that ran out
+        behind its launch `which` (DEBUG_FUSED_*)."""
+        self._check(self.L.cxk_debug_fused_timeout_at(self.h, launch_index, which), "cxk_debug_fused_timeout_at")
 
 
 def gemm_f64(A, B, C=None, ta=False, tb=False, alpha=1.0, beta=0.0, lower_only=False, splits=1,

@@ -412,8 +412,37 @@ int cxk_fused_tree(const cxk_context* ctx);
  * ONCE, so that the caller (the interior-point loop of program.cc) redoes its sequence instead of
  * giving up. */
 int cxk_fused_tree_timed_out(cxk_context* ctx);
+/* Sharded contexts (cxk_set_shard, world > 1) must take the same branch on every rank, so a time-out
+ * is settled the same way on all of them (the next entry point, cxk_factor_status or cxk_sync does it):
+ *   - a wait of a rank's up launch (its own subtrees, before the exchange) ran out: it travels with the
+ *     exchange buffer, so every rank reports a failed factorization, every rank's
+ *     cxk_fused_tree_timed_out returns 1, and every rank sweeps level by level from then on (the same
+ *     collectives as the whole-tree launches).  Nothing is redone silently.
+ *   - a wait of a rank's top launch (behind the exchange) ran out and a solve sweep or a step reduction
+ *     (eigenvalue query, PrepareStep) went out behind it: that collective carries a time-out mark in one
+ *     extra slot, and every rank reports it as above.
+ *   - a wait of a rank's top launch ran out and no collective went out behind it: that rank redoes its
+ *     top and the way back down its subtrees on the level kernels, from the exchange buffer it holds and
+ *     without a collective, and reports success; it sweeps level by level from then on.  cxk_get_y and
+ *     cxk_line_search, whose gathers carry no mark, settle such a launch first.  The step-scalar
+ *     all-reduce carries no mark either: when only it went out behind the launch the rank redoes the same
+ *     way and warns that what it sent came from the timed-out launch (the interior-point loop always
+ *     issues a step reduction before it asks for the factorization's outcome).
+ * A sharded context makes no solve-only whole-tree sweep. */
 /* test hook: pretend the latest whole-tree launch reported a wait that ran out */
 int cxk_debug_force_fused_timeout(cxk_context* ctx);
+/* test hook, one context at a time: the whole-tree factor launch number `launch_index` from now (0: the
+ * next one) reports, behind its launch `which`, what a wait that ran out reports -- the failure word
+ * d_fail[1] = the launch's tag on the device and the pinned host word -- and nothing else; no wait runs out.  which =
+ * CXK_DEBUG_FUSED_FACTOR (single GPU: the factor-and-solve launch; what CXK_DEBUG_FUSED_TIMEOUT_AT=k set
+ * at cxk_create does), CXK_DEBUG_FUSED_SHARD_UP or CXK_DEBUG_FUSED_SHARD_TOP (sharded: the launch before
+ * or after the exchange).  The host word is raised before the launching call returns; with
+ * CXK_DEBUG_FUSED_STREAM_ORDERED or'ed into CXK_DEBUG_FUSED_SHARD_TOP, by a host function on the stream
+ * instead, as late as a launch still running when the host goes on raises it.  launch_index < 0 disarms
+ * it.  Fails when the context makes no such launch. */
+enum { CXK_DEBUG_FUSED_FACTOR = 0, CXK_DEBUG_FUSED_SHARD_UP = 1, CXK_DEBUG_FUSED_SHARD_TOP = 2,
+       CXK_DEBUG_FUSED_STREAM_ORDERED = 16 };
+int cxk_debug_fused_timeout_at(cxk_context* ctx, int launch_index, int which);
 
 /* ---- timing / roofline accounting -------------------------------------- */
 /* algorithmic bytes and flops of one dense-LMI assembly launch (SURVEY 8d formulas) */

@@ -310,50 +310,56 @@ def test_sharded_equality_constraints_take_the_ldlt_path():
         assert np.linalg.norm(y - y_ref) <= 1e-10 * np.linalg.norm(y_ref)
 
 
+def _maximize(prob, rank, world, allreduce, hook=None):
+    """CONEX_Maximize of an LMI program (20 x 20 blocks) as rank `rank` of `world` (the all-reduce of a
+    ThreadRanks rank); hook = (launch_index, which): CONEX_HIP_DebugFusedTimeoutAt on this rank's program.
+    Returns (status, y, iterations)."""
+    import ctypes as C
+    import conex_api as ca
+    L = ca.api()
+    L.CONEX_HIP_SetAllReduce.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.CONEX_HIP_DebugFusedTimeoutAt.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    fn_t = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_void_p)
+    hip = C.CDLL("libamdhip64.so")
+    p = L.CONEX_CreateConeProgram()
+    keep = None
+    if world > 1:
+        def cb(user, dev, count, op, stream):
+            buf = np.empty(count)
+            hip.hipStreamSynchronize(C.c_void_p(stream))
+            hip.hipMemcpy(buf.ctypes.data_as(C.c_void_p), C.c_void_p(dev), C.c_size_t(8 * count), 2)
+            out = np.ascontiguousarray(allreduce(buf, op))
+            hip.hipMemcpy(C.c_void_p(dev), out.ctypes.data_as(C.c_void_p), C.c_size_t(8 * count), 1)
+            return 0
+        keep = fn_t(cb)
+        assert L.CONEX_HIP_SetAllReduce(p, rank, world, C.cast(keep, C.c_void_p), None) == 0
+    if hook is not None:
+        assert L.CONEX_HIP_DebugFusedTimeoutAt(p, hook[0], hook[1]) == 0
+    assert L.CONEX_SetNumberOfVariables(p, prob["num_vars"]) == 0
+    for c, cl in enumerate(prob["cliques"]):
+        a, cm = ca.colmajor(prob["A"][c]), ca.colmajor(prob["C"][c])
+        v = np.ascontiguousarray(cl, dtype=np.int64)
+        assert L.CONEX_AddSparseLMIConstraint(p, ca.dp(a), 20, 20, 20, ca.dp(cm), 20, 20,
+                                              v.ctypes.data_as(C.POINTER(C.c_long)), 20) == c
+    cfg = ca.default_config()
+    y = np.zeros(prob["num_vars"])
+    b = np.ascontiguousarray(prob["b"])
+    ok = L.CONEX_Maximize(p, ca.dp(b), len(b), C.byref(cfg), ca.dp(y), len(y))
+    st = ca.IterationStats()
+    L.CONEX_GetIterationStats(p, C.byref(st), -1)
+    L.CONEX_DeleteConeProgram(p)
+    return ok, y, st.iteration_number + 1
+
+
 @pytest.mark.gpu
 def test_sharded_conex_maximize_matches_single_gpu():
     """CONEX_Maximize with a communicator set runs the sharded IPM loop: every rank builds the same
     program, returns the same y, and that y is the single-GPU optimum."""
-    import ctypes as C
-    import conex_api as ca
     prob = syn.lmi_problem(K=100, n=20, m=20, branching=8, overlap=5, seed=21)
-    L = ca.api()
-    L.CONEX_HIP_SetAllReduce.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    fn_t = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_void_p)
-    hip = C.CDLL("libamdhip64.so")
-
-    def solve(rank, world, allreduce):
-        p = L.CONEX_CreateConeProgram()
-        keep = None
-        if world > 1:
-            def cb(user, dev, count, op, stream):
-                buf = np.empty(count)
-                hip.hipStreamSynchronize(C.c_void_p(stream))
-                hip.hipMemcpy(buf.ctypes.data_as(C.c_void_p), C.c_void_p(dev), C.c_size_t(8 * count), 2)
-                out = np.ascontiguousarray(allreduce(buf, op))
-                hip.hipMemcpy(C.c_void_p(dev), out.ctypes.data_as(C.c_void_p), C.c_size_t(8 * count), 1)
-                return 0
-            keep = fn_t(cb)
-            assert L.CONEX_HIP_SetAllReduce(p, rank, world, C.cast(keep, C.c_void_p), None) == 0
-        assert L.CONEX_SetNumberOfVariables(p, prob["num_vars"]) == 0
-        for c, cl in enumerate(prob["cliques"]):
-            a, cm = ca.colmajor(prob["A"][c]), ca.colmajor(prob["C"][c])
-            v = np.ascontiguousarray(cl, dtype=np.int64)
-            assert L.CONEX_AddSparseLMIConstraint(p, ca.dp(a), 20, 20, 20, ca.dp(cm), 20, 20,
-                                                  v.ctypes.data_as(C.POINTER(C.c_long)), 20) == c
-        cfg = ca.default_config()
-        y = np.zeros(prob["num_vars"])
-        b = np.ascontiguousarray(prob["b"])
-        ok = L.CONEX_Maximize(p, ca.dp(b), len(b), C.byref(cfg), ca.dp(y), len(y))
-        st = ca.IterationStats()
-        L.CONEX_GetIterationStats(p, C.byref(st), -1)
-        L.CONEX_DeleteConeProgram(p)
-        return ok, y, st.iteration_number + 1
-
-    ok0, y0, it0 = solve(0, 1, None)
+    ok0, y0, it0 = _maximize(prob, 0, 1, None)
     assert ok0 == 1
     world = 4
-    results = ThreadRanks(world).run(lambda r, ar: solve(r, world, ar))
+    results = ThreadRanks(world).run(lambda r, ar: _maximize(prob, r, world, ar))
     for ok, y, it in results:
         assert ok == 1 and abs(it - it0) <= 3
         assert np.array_equal(y, results[0][1])           # every rank returns the same vector
