@@ -12,6 +12,6 @@ used by the tests and ``bench.py``), :mod:`conex_amd.capi` (the ``CONEX_*`` tabl
 interfaces/python/ConexProgram.py).  There is no Python or CPU fallback: importing :mod:`conex_amd.kkt` raises if the library has
 not been built (``python __graft_entry__.py`` or ``make -C conex_amd/csrc``).
 """
-from .kkt import KktContext, load_library, LIB_PATH  # noqa: F401
+from .kkt import KktContext, load_library, lmi_kernel_names, LIB_PATH  # noqa: F401
 
-__all__ = ["KktContext", "load_library", "LIB_PATH"]
+__all__ = ["KktContext", "load_library", "lmi_kernel_names", "LIB_PATH"]

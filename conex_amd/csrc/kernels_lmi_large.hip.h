@@ -665,6 +665,12 @@ inline hipError_t LmiLargeReduceFinalizeLaunch(const LmiGroup& g, const Arena& a
   return hipGetLastError();
 }
 
+// K splits of the folded form's second product: the group's count, but at most one K step of kGemmBK each
+// over its n0 n long contraction
+inline int LmiFoldedSplits(int splits, int n, int n0) {
+  return std::max(1, std::min(splits, (int)(((int64_t)n0 * n + kGemmBK - 1) / kGemmBK)));
+}
+
 inline hipError_t LmiLargeSchurFolded(const LmiGroup& g, const Arena& ar, const LmiLargeWs& ws, hipStream_t st) {
   const int n = g.n, m1 = g.m + 1, n0 = ws.fold;
   const int64_t nn = (int64_t)n * n, per = (int64_t)n0 * n, stride = m1 * nn;
@@ -716,7 +722,7 @@ inline hipError_t LmiLargeSchurFolded(const LmiGroup& g, const Arena& ar, const 
   a.alpha = 1.0;
   a.beta = 0.0;
   a.lower_only = 1;
-  a.splits = std::max(1, std::min(ws.splits, (int)((per + kGemmBK - 1) / kGemmBK)));
+  a.splits = LmiFoldedSplits(ws.splits, n, n0);
   a.sCs = (int64_t)g.count * m1 * m1;
   if (a.splits > 1) a.C = ws.part;
   if ((e = LaunchGemm(a, true, false, g.count, st)) != hipSuccess) return e;

@@ -189,6 +189,198 @@ size_t LmiPrepareLds(int n, int m) {
 }
 size_t LmiTakeLds(int n) { return sizeof(double) * (size_t)(5 * n * n); }
 
+// ---- The kernel instance each per-constraint stage of an LMI group runs.  One chooser per stage: the
+// launch sites switch on its answer and cxk_lmi_kernels reports it, so the two cannot disagree.  The
+// choosers read only the group's shape and the flags fixed at create / initialize.
+enum LmiKernel : int {
+  // Schur complement (LaunchSchur)
+  kSchurGenericLiteral,
+  kSchurGenericSym,
+  kSchurMfma8,  // lmi_schur_mfma<N, false> at order N, two P images
+  kSchurMfma8Pad,  // ... at a smaller order, zero-padded
+  kSchurMfma12,
+  kSchurMfma12Pad,
+  kSchurMfma16,
+  kSchurMfma16Single,  // ... one P image
+  kSchurMfma16Pad,
+  kSchurMfma16PadSingle,
+  kSchurMfma20,
+  kSchurMfma20Single,
+  kSchurMfma20Pad,
+  kSchurMfma20PadSingle,
+  kSchurMfma24,
+  kSchurMfma24Single,
+  kSchurMfma24Pad,
+  kSchurMfma24PadSingle,
+  kSchurMfma24Folded,
+  kSchurMfma24FoldedSingle,
+  kSchurGemm,  // batched-GEMM assembly: full form, LDS-resident order, one K split
+  kSchurGemmSplit,
+  kSchurGemmLarge,
+  kSchurGemmLargeSplit,
+  kSchurGemmFolded,
+  kSchurGemmFoldedSplit,
+  kSchurGemmFoldedLarge,
+  kSchurGemmFoldedLargeSplit,
+  kSchurSparseSmall,
+  kSchurSparseSmallDenseC,
+  kSchurSparse,
+  kSchurSparseDenseC,
+  // PrepareStep (MODE 0) and the eigenvalue query (MODE 1): the same order of instances each
+  kPrepareRowsPacked,
+  kPrepareRowsExact,  // order 20, Apk null
+  kPrepareRowsOdd,
+  kPrepareRowsEven,
+  kPrepareGeneric20,
+  kPrepareGeneric,
+  kPrepareLarge,
+  kQueryRowsPacked,
+  kQueryRowsExact,
+  kQueryRowsOdd,
+  kQueryRowsEven,
+  kQueryGeneric20,
+  kQueryGeneric,
+  kQueryLarge,
+  // the affine update (PrepareStep with affine != 0)
+  kAffineGeneric20,
+  kAffineGeneric,
+  kAffineLarge,
+  // TakeStep
+  kTakeRows20,
+  kTakeRows20Pad,
+  kTakeRows32,
+  kTakeRows32Pad,
+  kTakeTaylor24,
+  kTakeTaylor24Pad,
+  kTakeTaylor32,
+  kTakeTaylor32Pad,
+  kTakeGeneric20,
+  kTakeGeneric,
+  kTakeLargePade,
+  kTakeLargeTaylor,
+  kLmiKernelCount
+};
+
+const char* const kLmiKernelNames[kLmiKernelCount] = {
+    "lmi_schur_generic literal",
+    "lmi_schur_generic symmetric",
+    "lmi_schur_mfma<8> exact two-images",
+    "lmi_schur_mfma<8> padded two-images",
+    "lmi_schur_mfma<12> exact two-images",
+    "lmi_schur_mfma<12> padded two-images",
+    "lmi_schur_mfma<16> exact two-images",
+    "lmi_schur_mfma<16> exact one-image",
+    "lmi_schur_mfma<16> padded two-images",
+    "lmi_schur_mfma<16> padded one-image",
+    "lmi_schur_mfma<20> exact two-images",
+    "lmi_schur_mfma<20> exact one-image",
+    "lmi_schur_mfma<20> padded two-images",
+    "lmi_schur_mfma<20> padded one-image",
+    "lmi_schur_mfma<24> exact two-images",
+    "lmi_schur_mfma<24> exact one-image",
+    "lmi_schur_mfma<24> padded two-images",
+    "lmi_schur_mfma<24> padded one-image",
+    "lmi_schur_mfma<24,folded> two-images",
+    "lmi_schur_mfma<24,folded> one-image",
+    "schur_gemm full lds",
+    "schur_gemm full lds split",
+    "schur_gemm full large",
+    "schur_gemm full large split",
+    "schur_gemm folded lds",
+    "schur_gemm folded lds split",
+    "schur_gemm folded large",
+    "schur_gemm folded large split",
+    "lmi_schur_sparse small",
+    "lmi_schur_sparse small dense-C",
+    "lmi_schur_sparse hbm",
+    "lmi_schur_sparse hbm dense-C",
+    "lmi_prepare_rows<0,20,exact> packed",
+    "lmi_prepare_rows<0,20,exact> unpacked",
+    "lmi_prepare_rows<0,20> odd",
+    "lmi_prepare_rows<0,20> even",
+    "lmi_prepare_generic<0,20>",
+    "lmi_prepare_generic<0,0>",
+    "LmiLargePrepare<0>",
+    "lmi_prepare_rows<1,20,exact> packed",
+    "lmi_prepare_rows<1,20,exact> unpacked",
+    "lmi_prepare_rows<1,20> odd",
+    "lmi_prepare_rows<1,20> even",
+    "lmi_prepare_generic<1,20>",
+    "lmi_prepare_generic<1,0>",
+    "LmiLargePrepare<1>",
+    "lmi_prepare_generic<0,20> affine",
+    "lmi_prepare_generic<0,0> affine",
+    "LmiLargePrepare<0> affine",
+    "lmi_take_step_rows<20> exact",
+    "lmi_take_step_rows<20> padded",
+    "lmi_take_step_rows<32> exact",
+    "lmi_take_step_rows<32> padded",
+    "lmi_take_step_rows_taylor<24> exact",
+    "lmi_take_step_rows_taylor<24> padded",
+    "lmi_take_step_rows_taylor<32> exact",
+    "lmi_take_step_rows_taylor<32> padded",
+    "lmi_take_step_generic<20>",
+    "lmi_take_step_generic<0>",
+    "LmiLargeTakeStep pade",
+    "LmiLargeTakeStep taylor",
+};
+
+bool IsSchurMfma(LmiKernel k) { return k >= kSchurMfma8 && k <= kSchurMfma24FoldedSingle; }
+bool IsSchurGemm(LmiKernel k) { return k >= kSchurGemm && k <= kSchurGemmFoldedLargeSplit; }
+bool IsSchurSparse(LmiKernel k) { return k >= kSchurSparseSmall && k <= kSchurSparseDenseC; }
+bool IsPrepareRows(LmiKernel k) {
+  return (k >= kPrepareRowsPacked && k <= kPrepareRowsEven) || (k >= kQueryRowsPacked && k <= kQueryRowsEven);
+}
+bool IsTakeRows(LmiKernel k) { return k >= kTakeRows20 && k <= kTakeTaylor32Pad; }
+
+LmiKernel LmiSchurKernel(const Group& g) {
+  if (g.sparse) return (LmiKernel)((g.sp_small ? kSchurSparseSmall : kSchurSparse) + (g.sp_cdense ? 1 : 0));
+  if (g.schur_gemm) {  // (fold and split counts as LmiLargeSchur reads them: MakeLargeWs, LmiFoldedSplits)
+    const bool fold = g.Aleft.n != 0;
+    const int splits = fold ? LmiFoldedSplits(g.splits, g.n, g.n / g.herm_d) : g.splits;
+    return (LmiKernel)(kSchurGemm + (fold ? 4 : 0) + (g.large ? 2 : 0) + (splits > 1 ? 1 : 0));
+  }
+  if (g.mfma) {
+    const LmiMfmaInstance inst = LmiMfmaChoose(g.n, g.m, g.herm_d);
+    if (inst.folded) return inst.single ? kSchurMfma24FoldedSingle : kSchurMfma24Folded;
+    const bool pad = g.Apad.p != nullptr;
+    switch (inst.order) {
+      case 8: return pad ? kSchurMfma8Pad : kSchurMfma8;
+      case 12: return pad ? kSchurMfma12Pad : kSchurMfma12;
+      case 16: return (LmiKernel)(kSchurMfma16 + (pad ? 2 : 0) + (inst.single ? 1 : 0));
+      case 20: return (LmiKernel)(kSchurMfma20 + (pad ? 2 : 0) + (inst.single ? 1 : 0));
+      default: return (LmiKernel)(kSchurMfma24 + (pad ? 2 : 0) + (inst.single ? 1 : 0));
+    }
+  }
+  return g.literal ? kSchurGenericLiteral : kSchurGenericSym;
+}
+
+// mode 0 PrepareStep, 1 the eigenvalue query, 2 the affine update
+LmiKernel LmiPrepareKernel(const cxk_context* ctx, const Group& g, int mode) {
+  const int base = mode == 0 ? kPrepareRowsPacked : kQueryRowsPacked;
+  if (g.large) return mode == 2 ? kAffineLarge : (LmiKernel)(base + 6);
+  if (mode != 2 && !ctx->prepare_lds && !g.literal && LmiPrepareRowsSupports(g.n, g.m, g.herm_d, g.sparse)) {
+    if (g.n == 20) return (LmiKernel)(base + (g.Apk.p ? 0 : 1));
+    return (LmiKernel)(base + ((g.n & 1) ? 2 : 3));
+  }
+  if (mode == 2) return g.n == 20 ? kAffineGeneric20 : kAffineGeneric;
+  return (LmiKernel)(base + (g.n == 20 ? 4 : 5));
+}
+
+bool TakeStepLdsSwitch() {
+  static const bool on = getenv("CXK_TAKE_STEP_LDS") != nullptr;  // A/B switch (tests, timing)
+  return on;
+}
+
+LmiKernel LmiTakeKernel(const Group& g) {
+  if (g.large) return g.herm_d ? kTakeLargeTaylor : kTakeLargePade;
+  if (LmiTakeStepRowsSupports(g.n) && !TakeStepLdsSwitch() && !g.literal) {
+    if (g.herm_d == 0) return g.n <= 20 ? (g.n == 20 ? kTakeRows20 : kTakeRows20Pad) : (g.n == 32 ? kTakeRows32 : kTakeRows32Pad);
+    return g.n <= 24 ? (g.n == 24 ? kTakeTaylor24 : kTakeTaylor24Pad) : (g.n == 32 ? kTakeTaylor32 : kTakeTaylor32Pad);
+  }
+  return g.n == 20 ? kTakeGeneric20 : kTakeGeneric;
+}
+
 
 hipError_t RaiseTopDenseLimits() {
   for (const void* kf : {reinterpret_cast<const void*>(&tree_top_dense<32>), reinterpret_cast<const void*>(&tree_top_dense<40>),
@@ -398,10 +590,10 @@ hipError_t LaunchLmiSparseKernel(Group& g, const LmiGroup& d, const Arena& ar, c
   }
 }
 
-hipError_t LaunchLmiSchurSparse(Group& g, const Arena& ar, hipStream_t st) {
+hipError_t LaunchLmiSchurSparse(Group& g, LmiKernel kern, const Arena& ar, hipStream_t st) {
   const LmiGroup d = MakeLmi(g);
   const int n = g.n;
-  if (g.sp_small) return LaunchLmiSparseKernel<true>(g, d, ar, nullptr, st);
+  if (kern == kSchurSparseSmall || kern == kSchurSparseSmallDenseC) return LaunchLmiSparseKernel<true>(g, d, ar, nullptr, st);
   double* X = nullptr;
   if (g.sp_cdense) {
     const int64_t nn = (int64_t)n * n;
@@ -447,13 +639,14 @@ int LaunchSchur(cxk_context* ctx) {
       case CXK_LMI: {
         hipEvent_t e0 = nullptr, e1 = nullptr;
         const bool sample = ClockSample(ctx, CXK_CLOCK_ASSEMBLY, &e0, &e1);
+        const LmiKernel kern = LmiSchurKernel(g);
         // (lmi_schur_mfma carries the pair on its dispatch instead: no marker packets)
-        if (sample && !(g.mfma && !g.sparse && !g.schur_gemm)) CXK_TRY(hipEventRecord(e0, ctx->stream));
-        if (g.sparse) {
-          CXK_TRY(LaunchLmiSchurSparse(g, ar, ctx->stream));
-        } else if (g.schur_gemm) {
+        if (sample && !IsSchurMfma(kern)) CXK_TRY(hipEventRecord(e0, ctx->stream));
+        if (IsSchurSparse(kern)) {
+          CXK_TRY(LaunchLmiSchurSparse(g, kern, ar, ctx->stream));
+        } else if (IsSchurGemm(kern)) {
           CXK_TRY(LmiLargeSchur(MakeLmi(g), ar, MakeLargeWs(g), ctx->stream));
-        } else if (g.mfma) {
+        } else if (IsSchurMfma(kern)) {
           LmiGroup lg = MakeLmi(g);
           if (g.Apad.p) {  // the order runs on the next instance up (masked W loads in the kernel)
             const int np = LmiMfmaPaddedOrder(g.n);
@@ -464,7 +657,7 @@ int LaunchSchur(cxk_context* ctx) {
         } else {
           lmi_schur_generic<<<count, 256, LmiGenericLds(g.n), ctx->stream>>>(MakeLmi(g), ar);
         }
-        if (sample && !(g.mfma && !g.sparse && !g.schur_gemm)) CXK_TRY(hipEventRecord(e1, ctx->stream));
+        if (sample && !IsSchurMfma(kern)) CXK_TRY(hipEventRecord(e1, ctx->stream));
         break;
       }
       case CXK_LINEAR:
@@ -3125,29 +3318,38 @@ static int PrepareStepImpl(cxk_context* ctx, int affine, double c_weight, double
     ctx->y_deferred = false;
   }
   ctx->lanczos_calls++;
-  bool rows_only = NonEmptyGroups(ctx) == 1 && !affine && !ctx->prepare_lds;
+  // (CXK_PREPARE_LDS at cxk_create, an A/B switch for tests and timing, keeps every group off the rows kernel)
+  const int pmode = affine ? 2 : 0;
+  bool rows_only = NonEmptyGroups(ctx) == 1;
   for (const Group& g : ctx->groups)
     if (!g.ids.empty())
-      rows_only = rows_only && g.type == CXK_LMI && !g.large && !g.literal && LmiPrepareRowsSupports(g.n, g.m, g.herm_d, g.sparse);
+      rows_only = rows_only && g.type == CXK_LMI && IsPrepareRows(LmiPrepareKernel(ctx, g, pmode));
   const StepClock clk = BeginStepClock(ctx, CXK_CLOCK_PREPARE, rows_only);
   for (Group& g : ctx->groups) {
     const int cnt = (int)g.ids.size();
     if (cnt == 0) continue;
-    if (g.type == CXK_LMI && g.large)
-      CXK_TRY(LmiLargePrepare(MakeLmi(g), sa, MakeLargeWs(g), 0, ctx->stream));
-    else if (g.type == CXK_LMI) {
-      const bool lds_kernel = ctx->prepare_lds;  // A/B switch (tests, timing): CXK_PREPARE_LDS at cxk_create
-      if (!affine && !lds_kernel && !g.literal && LmiPrepareRowsSupports(g.n, g.m, g.herm_d, g.sparse))
-      {
-        if (g.n == 20)
+    if (g.type == CXK_LMI) {
+      switch (LmiPrepareKernel(ctx, g, pmode)) {
+        case kPrepareLarge:
+        case kAffineLarge:
+          CXK_TRY(LmiLargePrepare(MakeLmi(g), sa, MakeLargeWs(g), 0, ctx->stream));
+          break;
+        case kPrepareRowsPacked:
+        case kPrepareRowsExact:  // (the instance reads g.Apk when there is one)
           CXK_LAUNCH_CLOCKED(clk, (lmi_prepare_rows<0, 20, true>), (cnt + 3) / 4 + (tail.slots ? 1 + tail.ny : 0), 256, MakeLmi(g), sa, tail);
-        else  // (an even order below 20 on the same instance)
+          break;
+        case kPrepareRowsOdd:
+        case kPrepareRowsEven:  // (an order below 20 on the same instance)
           CXK_LAUNCH_CLOCKED(clk, (lmi_prepare_rows<0, 20, false>), (cnt + 3) / 4 + (tail.slots ? 1 + tail.ny : 0), 256, MakeLmi(g), sa, tail);
+          break;
+        case kPrepareGeneric20:
+        case kAffineGeneric20:
+          lmi_prepare_generic<0, 20><<<cnt, 256, LmiPrepareLds(g.n, g.m), ctx->stream>>>(MakeLmi(g), sa);
+          break;
+        default:  // kPrepareGeneric, kAffineGeneric
+          lmi_prepare_generic<0, 0><<<cnt, 256, LmiPrepareLds(g.n, g.m), ctx->stream>>>(MakeLmi(g), sa);
+          break;
       }
-      else if (g.n == 20)
-        lmi_prepare_generic<0, 20><<<cnt, 256, LmiPrepareLds(g.n, g.m), ctx->stream>>>(MakeLmi(g), sa);
-      else
-        lmi_prepare_generic<0, 0><<<cnt, 256, LmiPrepareLds(g.n, g.m), ctx->stream>>>(MakeLmi(g), sa);
     }
     else if (g.type == CXK_LINEAR)
       linear_prepare<0><<<cnt, 256, sizeof(double) * g.m, ctx->stream>>>(MakeVec(g), sa);
@@ -3196,36 +3398,46 @@ static int LaunchTakeStep(cxk_context* ctx, double e_weight, double step_size, c
     sa.skip_if = ctx->d_fail.p;
     sa.skip_tag = ctx->fail_tag;
   }
-  static const bool take_lds_kernel = getenv("CXK_TAKE_STEP_LDS") != nullptr;  // A/B switch (tests, timing)
-  bool rows_only = NonEmptyGroups(ctx) == 1 && !take_lds_kernel;
+  bool rows_only = NonEmptyGroups(ctx) == 1;
   for (const Group& g : ctx->groups)
-    if (!g.ids.empty()) rows_only = rows_only && g.type == CXK_LMI && !g.large && !g.literal && LmiTakeStepRowsSupports(g.n);
+    if (!g.ids.empty()) {
+      const LmiKernel k = g.type == CXK_LMI ? LmiTakeKernel(g) : kTakeGeneric;
+      rows_only = rows_only && IsTakeRows(k);
+    }
   const StepClock clk = BeginStepClock(ctx, CXK_CLOCK_TAKE, rows_only);
   for (Group& g : ctx->groups) {
     const int cnt = (int)g.ids.size();
     if (cnt == 0) continue;
-    if (g.type == CXK_LMI && g.large)
-      CXK_TRY(LmiLargeTakeStep(MakeLmi(g), sa, MakeLargeWs(g), ctx->stream));
-    else if (g.type == CXK_LMI) {
-      const bool lds_kernel = take_lds_kernel;
-      if (LmiTakeStepRowsSupports(g.n) && !lds_kernel && !g.literal) {
-        const int blocks = (cnt + 3) / 4;
-        if (g.herm_d == 0) {
-          if (g.n <= 20)
-            CXK_LAUNCH_CLOCKED(clk, (lmi_take_step_rows<20>), blocks, 256, MakeLmi(g), sa);
-          else
-            CXK_LAUNCH_CLOCKED(clk, (lmi_take_step_rows<32>), blocks, 256, MakeLmi(g), sa);
-        } else {
-          if (g.n <= 24)
-            CXK_LAUNCH_CLOCKED(clk, (lmi_take_step_rows_taylor<24>), blocks, 256, MakeLmi(g), sa);
-          else
-            CXK_LAUNCH_CLOCKED(clk, (lmi_take_step_rows_taylor<32>), blocks, 256, MakeLmi(g), sa);
-        }
+    if (g.type == CXK_LMI) {
+      const int blocks = (cnt + 3) / 4;
+      switch (LmiTakeKernel(g)) {
+        case kTakeLargePade:
+        case kTakeLargeTaylor:  // (Pade or Taylor by g.herm_d inside)
+          CXK_TRY(LmiLargeTakeStep(MakeLmi(g), sa, MakeLargeWs(g), ctx->stream));
+          break;
+        case kTakeRows20:
+        case kTakeRows20Pad:
+          CXK_LAUNCH_CLOCKED(clk, (lmi_take_step_rows<20>), blocks, 256, MakeLmi(g), sa);
+          break;
+        case kTakeRows32:
+        case kTakeRows32Pad:
+          CXK_LAUNCH_CLOCKED(clk, (lmi_take_step_rows<32>), blocks, 256, MakeLmi(g), sa);
+          break;
+        case kTakeTaylor24:
+        case kTakeTaylor24Pad:
+          CXK_LAUNCH_CLOCKED(clk, (lmi_take_step_rows_taylor<24>), blocks, 256, MakeLmi(g), sa);
+          break;
+        case kTakeTaylor32:
+        case kTakeTaylor32Pad:
+          CXK_LAUNCH_CLOCKED(clk, (lmi_take_step_rows_taylor<32>), blocks, 256, MakeLmi(g), sa);
+          break;
+        case kTakeGeneric20:
+          lmi_take_step_generic<20><<<cnt, 256, LmiTakeLds(g.n), ctx->stream>>>(MakeLmi(g), sa);
+          break;
+        default:  // kTakeGeneric
+          lmi_take_step_generic<0><<<cnt, 256, LmiTakeLds(g.n), ctx->stream>>>(MakeLmi(g), sa);
+          break;
       }
-      else if (g.n == 20)
-        lmi_take_step_generic<20><<<cnt, 256, LmiTakeLds(g.n), ctx->stream>>>(MakeLmi(g), sa);
-      else
-        lmi_take_step_generic<0><<<cnt, 256, LmiTakeLds(g.n), ctx->stream>>>(MakeLmi(g), sa);
     }
     else if (g.type == CXK_LINEAR)
       linear_take_step<<<GridFor((size_t)cnt * g.n, 256), 256, 0, ctx->stream>>>(MakeVec(g), sa);
@@ -3257,29 +3469,34 @@ static int SlackEigenvaluesImpl(cxk_context* ctx, double c_weight, double* out, 
   if (with_tail && MakeStepTail(ctx, 1, &tail)) return CXK_FAILURE;
   if (rule) tail.rule = *rule;
   ctx->lanczos_calls++;
-  bool rows_only = NonEmptyGroups(ctx) == 1 && !ctx->prepare_lds;
+  bool rows_only = NonEmptyGroups(ctx) == 1;
   for (const Group& g : ctx->groups)
     if (!g.ids.empty())
-      rows_only = rows_only && g.type == CXK_LMI && !g.large && !g.literal && LmiPrepareRowsSupports(g.n, g.m, g.herm_d, g.sparse);
+      rows_only = rows_only && g.type == CXK_LMI && IsPrepareRows(LmiPrepareKernel(ctx, g, 1));
   const StepClock clk = BeginStepClock(ctx, CXK_CLOCK_QUERY, rows_only);
   for (Group& g : ctx->groups) {
     const int cnt = (int)g.ids.size();
     if (cnt == 0) continue;
-    if (g.type == CXK_LMI && g.large)
-      CXK_TRY(LmiLargePrepare(MakeLmi(g), sa, MakeLargeWs(g), 1, ctx->stream));
-    else if (g.type == CXK_LMI) {
-      const bool lds_kernel = ctx->prepare_lds;
-      if (!lds_kernel && !g.literal && LmiPrepareRowsSupports(g.n, g.m, g.herm_d, g.sparse))
-      {
-        if (g.n == 20)
+    if (g.type == CXK_LMI) {
+      switch (LmiPrepareKernel(ctx, g, 1)) {
+        case kQueryLarge:
+          CXK_TRY(LmiLargePrepare(MakeLmi(g), sa, MakeLargeWs(g), 1, ctx->stream));
+          break;
+        case kQueryRowsPacked:
+        case kQueryRowsExact:
           CXK_LAUNCH_CLOCKED(clk, (lmi_prepare_rows<1, 20, true>), (cnt + 3) / 4 + (tail.slots ? 1 : 0), 256, MakeLmi(g), sa, tail);
-        else  // (an even order below 20 on the same instance)
+          break;
+        case kQueryRowsOdd:
+        case kQueryRowsEven:  // (an order below 20 on the same instance)
           CXK_LAUNCH_CLOCKED(clk, (lmi_prepare_rows<1, 20, false>), (cnt + 3) / 4 + (tail.slots ? 1 : 0), 256, MakeLmi(g), sa, tail);
+          break;
+        case kQueryGeneric20:
+          lmi_prepare_generic<1, 20><<<cnt, 256, LmiPrepareLds(g.n, g.m), ctx->stream>>>(MakeLmi(g), sa);
+          break;
+        default:  // kQueryGeneric
+          lmi_prepare_generic<1, 0><<<cnt, 256, LmiPrepareLds(g.n, g.m), ctx->stream>>>(MakeLmi(g), sa);
+          break;
       }
-      else if (g.n == 20)
-        lmi_prepare_generic<1, 20><<<cnt, 256, LmiPrepareLds(g.n, g.m), ctx->stream>>>(MakeLmi(g), sa);
-      else
-        lmi_prepare_generic<1, 0><<<cnt, 256, LmiPrepareLds(g.n, g.m), ctx->stream>>>(MakeLmi(g), sa);
     }
     else if (g.type == CXK_LINEAR)
       linear_prepare<1><<<cnt, 256, sizeof(double) * g.m, ctx->stream>>>(MakeVec(g), sa);
@@ -3605,6 +3822,25 @@ int cxk_count_lmi_kernel(const cxk_context* ctx, int which) {
   }
   return k;
 }
+
+int cxk_lmi_kernels(const cxk_context* ctx, int constraint, int out[5]) {
+  if (!ctx || !ctx->device_ready || !out || constraint < 0 || constraint >= (int)ctx->cons.size()) return CXK_FAILURE;
+  const ConstraintRec& c = ctx->cons[constraint];
+  if (c.type != CXK_LMI || !ctx->owned[constraint]) return CXK_FAILURE;
+  const Group& g = ctx->groups[c.group];
+  out[CXK_LMI_STAGE_SCHUR] = LmiSchurKernel(g);
+  out[CXK_LMI_STAGE_PREPARE] = LmiPrepareKernel(ctx, g, 0);
+  out[CXK_LMI_STAGE_QUERY] = LmiPrepareKernel(ctx, g, 1);
+  out[CXK_LMI_STAGE_TAKE] = LmiTakeKernel(g);
+  out[CXK_LMI_STAGE_AFFINE] = LmiPrepareKernel(ctx, g, 2);
+  return CXK_SUCCESS;
+}
+
+const char* cxk_lmi_kernel_name(int code) {
+  return code >= 0 && code < kLmiKernelCount ? kLmiKernelNames[code] : nullptr;
+}
+
+int cxk_lmi_kernel_count(void) { return kLmiKernelCount; }
 
 int cxk_assembly_work(const cxk_context* ctx, double* bytes, double* flops) {
   if (!ctx || !ctx->finalized) return CXK_FAILURE;

@@ -18,6 +18,14 @@ namespace cxk {
 int LmiMfmaPaddedOrder(int n);
 bool LmiMfmaSupports(int n, int m, int herm_d = 0);
 
+// The instance a supported shape runs on (LaunchLmiSchurMfma launches exactly this one): template
+// order, the folded Hermitian form, and one P image instead of two when two do not fit LDS.
+struct LmiMfmaInstance {
+  int order;
+  bool folded, single;
+};
+LmiMfmaInstance LmiMfmaChoose(int n, int m, int herm_d);
+
 // ConstructSchurComplementSystem(DenseLMIConstraint*) for every member of the group
 // (dense_lmi_constraint.cc:72-103); `cus` = multiprocessors of the device the stream runs on.
 // ev_start / ev_stop (both or neither): HIP events attached to the dispatch (hipExtLaunchKernel), whose

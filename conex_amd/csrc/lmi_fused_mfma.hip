@@ -726,6 +726,12 @@ bool SupportsT(int m) {
          MfmaLds<N, H>(m, 1) <= kLdsPerCu;
 }
 
+// two P images where they fit LDS, one otherwise
+template <int N, bool H>
+bool SingleT(int m) {
+  return MfmaLds<N, H>(m) > kLdsPerCu;
+}
+
 template <int N, bool H>
 hipError_t LaunchT(const LmiGroup& g, const Arena& ar, int cus, hipStream_t stream, hipEvent_t ev_start,
                    hipEvent_t ev_stop) {
@@ -738,7 +744,7 @@ hipError_t LaunchT(const LmiGroup& g, const Arena& ar, int cus, hipStream_t stre
   int grid = g.count < cus ? g.count : cus;
   const int need = (g.count + kDestSlots - 1) / kDestSlots;  // at most kDestSlots constraints per workgroup
   if (grid < need) grid = need;
-  const int single = MfmaLds<N, H>(g.m) > kLdsPerCu ? 1 : 0;
+  const int single = SingleT<N, H>(g.m) ? 1 : 0;
   const size_t lds = MfmaLds<N, H>(g.m, single);
   if (ev_start && ev_stop)
     // the events ride on the dispatch itself (its own begin / end time stamps, what rocprofv3
@@ -773,12 +779,27 @@ bool LmiMfmaSupports(int n, int m, int herm_d) {
   return false;
 }
 
+LmiMfmaInstance LmiMfmaChoose(int n, int m, int herm_d) {
+  if (Folded(n, m, herm_d)) return {24, true, SingleT<24, true>(m)};
+  const int order = LmiMfmaPaddedOrder(n);
+  bool single = false;
+  switch (order) {
+    case 8: single = SingleT<8, false>(m); break;
+    case 12: single = SingleT<12, false>(m); break;
+    case 16: single = SingleT<16, false>(m); break;
+    case 20: single = SingleT<20, false>(m); break;
+    case 24: single = SingleT<24, false>(m); break;
+  }
+  return {order, false, single};
+}
+
 // g.A / g.a_stride: [A_1 .. A_m | C] per member at the PADDED order; g.n, g.W: the order itself.
 hipError_t LaunchLmiSchurMfma(const LmiGroup& g, const Arena& ar, int cus, hipStream_t stream, hipEvent_t ev_start,
                               hipEvent_t ev_stop) {
   if (g.count <= 0) return hipSuccess;
-  if (Folded(g.n, g.m, g.herm_d)) return LaunchT<24, true>(g, ar, cus, stream, ev_start, ev_stop);
-  switch (LmiMfmaPaddedOrder(g.n)) {
+  const LmiMfmaInstance inst = LmiMfmaChoose(g.n, g.m, g.herm_d);
+  if (inst.folded) return LaunchT<24, true>(g, ar, cus, stream, ev_start, ev_stop);
+  switch (inst.order) {
     case 8: return LaunchT<8, false>(g, ar, cus, stream, ev_start, ev_stop);
     case 12: return LaunchT<12, false>(g, ar, cus, stream, ev_start, ev_stop);
     case 16: return LaunchT<16, false>(g, ar, cus, stream, ev_start, ev_stop);

@@ -90,6 +90,10 @@ _SIGNATURES = {
     "cxk_assembly_work": (C.c_int, [C.c_void_p, c_double_p, c_double_p]),
     "cxk_count_sparse_lmi": (C.c_int, [C.c_void_p]),
     "cxk_count_lmi_kernel": (C.c_int, [C.c_void_p, C.c_int]),
+    "cxk_lmi_kernels": (C.c_int, [C.c_void_p, C.c_int, c_int_p]),
+    "cxk_lmi_kernel_name": (C.c_char_p, [C.c_int]),
+    "cxk_lmi_kernel_count": (C.c_int, []),
+    "cxk_get_step_info": (C.c_int, [C.c_void_p, c_double_p]),
     "cxk_fused_assembly": (C.c_int, [C.c_void_p]),
     "cxk_fused_tree": (C.c_int, [C.c_void_p]),
     "cxk_comm_init_rccl_solo": (C.c_int, [C.c_void_p]),
@@ -145,6 +149,16 @@ def load_library():
         fn.argtypes = args
     _LIB = L
     return L
+
+
+# stages of cxk_lmi_kernels, in the order of its output (CXK_LMI_STAGE_*)
+LMI_STAGES = ("schur", "prepare", "query", "take", "affine")
+
+
+def lmi_kernel_names():
+    """Every kernel instance name cxk_lmi_kernels can report, in code order."""
+    L = load_library()
+    return [L.cxk_lmi_kernel_name(c).decode() for c in range(L.cxk_lmi_kernel_count())]
 
 
 def _colmajor(a):
@@ -630,6 +644,18 @@ class KktContext:
         """Constraints whose Schur block comes from kernel `which` (cxk_count_lmi_kernel): 0 literal,
         1 DPP + MFMA rows, 2 persistent MFMA, 3 GEMM pipeline, 4 sparse."""
         return self.L.cxk_count_lmi_kernel(self.h, which)
+
+    def lmi_kernels(self, i):
+        """{stage: kernel instance name} of LMI / Hermitian constraint i (cxk_lmi_kernels)."""
+        out = (C.c_int * 5)()
+        self._check(self.L.cxk_lmi_kernels(self.h, i, out), "cxk_lmi_kernels")
+        return {s: self.L.cxk_lmi_kernel_name(out[j]).decode() for j, s in enumerate(LMI_STAGES)}
+
+    def step_info(self):
+        """Per-constraint (normsqrd, norminfd) of the last prepare_step, shape (K, 2) (cxk_get_step_info)."""
+        out = np.zeros(2 * self.K)
+        self._check(self.L.cxk_get_step_info(self.h, _dp(out)), "cxk_get_step_info")
+        return out.reshape(self.K, 2)
 
     def assembly_work(self):
         b = C.c_double()

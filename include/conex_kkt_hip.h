@@ -383,6 +383,22 @@ int cxk_count_sparse_lmi(const cxk_context* ctx);
  * pipeline (orders beyond LDS and mid-size orders), 4 sparse evaluation. */
 int cxk_count_lmi_kernel(const cxk_context* ctx, int which);
 
+/* The kernel instance each per-constraint stage of LMI / Hermitian constraint `constraint` runs, as
+ * codes 0 .. cxk_lmi_kernel_count() - 1 in out[stage] (stages below).  The launches choose through
+ * the same functions.  Fails for a constraint of another type, one not owned by this rank, or before
+ * initialize. */
+enum {
+  CXK_LMI_STAGE_SCHUR = 0,   /* Schur complement assembly */
+  CXK_LMI_STAGE_PREPARE = 1, /* PrepareStep */
+  CXK_LMI_STAGE_QUERY = 2,   /* the weighted slack eigenvalue query */
+  CXK_LMI_STAGE_TAKE = 3,    /* TakeStep */
+  CXK_LMI_STAGE_AFFINE = 4   /* PrepareStep's affine update */
+};
+int cxk_lmi_kernels(const cxk_context* ctx, int constraint, int out[5]);
+/* name of a code of cxk_lmi_kernels (null outside the range): kernel, template order, variant */
+const char* cxk_lmi_kernel_name(int code);
+int cxk_lmi_kernel_count(void);
+
 /* Columns of the dense range at the top of the elimination tree (0 = none): when the last levels
  * hold a supernode of 33..64 columns and at most 64 columns in total, BlockCholeskyInPlace and
  * the block solves (block_triangular_operations.cc:114-219) restricted to those levels run as one
