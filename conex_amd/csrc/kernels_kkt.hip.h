@@ -2153,6 +2153,7 @@ __global__ void refine_add(int N, const double* __restrict__ ysave, double* __re
 // unpack: after the caller's sum all-reduce the buffer holds the complete assembled-and-updated
 //         top; write it back, rebuild the right-hand side of top variables and latch `fail`.
 // ---------------------------------------------------------------------------------------
+#endif  // CXK_DEVICE_FUNCTIONS_ONLY (the arguments and the mark are types and device functions: every unit)
 struct ExchangeArgs {
   int64_t n_xs;
   int n_xv;
@@ -2197,6 +2198,7 @@ __device__ __forceinline__ void ShardMarkSeen(double mark, int* fail, int tag) {
   }
 }
 
+#ifndef CXK_DEVICE_FUNCTIONS_ONLY
 __global__ void __launch_bounds__(256) exchange_pack(ExchangeArgs a) {
   const int64_t gid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;

@@ -1,6 +1,6 @@
 // Shared by the translation units of the cxk_* path: the context, its host-side types and the
 // functions that cross between them.  kkt_plans.hip builds the symbolic plans (tree structure,
-// partition, index tables: host code only), kkt_context.hip holds the launches and the C-ABI.
+// partition, index tables: host code only); the launches and the C-ABI are the units kkt_launch.h lists.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -22,7 +22,7 @@
 #include <vector>
 
 #include "../../include/conex_kkt_hip.h"
-#include "kernels_kkt.hip.h"      // record types, FactorPlan (kkt_plans.hip defines CXK_DEVICE_FUNCTIONS_ONLY first)
+#include "kernels_kkt.hip.h"      // record types, FactorPlan (every unit but kkt_tree_launch.hip defines CXK_DEVICE_FUNCTIONS_ONLY first)
 #include "kernels_kkt_top.hip.h"  // TopDenseArgs
 #include "lmi_types.h"
 #include "symbolic.h"
@@ -405,9 +405,9 @@ constexpr int kChainMaxLevels = 1 << 30;  // no limit: the kernel keeps the last
 constexpr int kSplitTopLevels = 8;  // tops of at most this many levels may be swept level by level
 
 int Fail(cxk_context* ctx, const char* msg);
-// two-shape chains tree_chain_lean is compiled for (kkt_context.hip, LaunchChain)
+// two-shape chains tree_chain_lean is compiled for (kkt_tree_launch.hip, LaunchChain)
 bool ChainPairCompiled(int sa, int sb);
-// dynamic-LDS limit of the tree_top_dense instances, raised on the current device (kkt_context.hip)
+// dynamic-LDS limit of the tree_top_dense instances, raised on the current device (kkt_tree_launch.hip)
 hipError_t RaiseTopDenseLimits();
 
 // kkt_plans.hip

@@ -1,0 +1,142 @@
+// What the translation units of the cxk_* path call in one another.  Every kernel is compiled in
+// exactly one unit; a unit that needs a kernel it does not own goes through a host function of the owner:
+//   kkt_cone_launch.hip  the per-cone stages (Schur, PrepareStep, eigenvalue query, TakeStep), the mailbox
+//   kkt_tree_launch.hip  assembly gather, right-hand sides, the elimination-tree sweeps, the exchange kernels
+//   kkt_shard.hip        sharded sweeps, collectives, communicator and exchange entry points
+//   kkt_qr.hip           the host QR mode
+//   kkt_context.hip      everything else of the C-ABI (no kernel launch of its own)
+// Every unit but kkt_tree_launch.hip defines CXK_DEVICE_FUNCTIONS_ONLY before including this.
+#pragma once
+#include "kkt_internal.h"
+
+namespace cxk {
+struct MuRuleArgs;  // kernels_cone.hip.h
+}
+
+namespace cxk_host {
+
+enum { kOpSum = 0, kOpMax = 1, kOpMin = 2 };  // ShardAllReduce, cxk_allreduce_fn
+
+constexpr int kSparseCParts = 64;  // slices of the <w,c>, <c,Qc> sums of a dense C beyond LDS orders
+
+// A function only the units of the cxk_* path call in one another: not part of the library's dynamic symbols.
+#define CXK_LOCAL __attribute__((visibility("hidden")))
+
+// The current HIP device is per-thread state: every entry point binds the context's device for
+// its own duration and restores the caller's (another thread, a second context on another GPU,
+// or a host framework that switched devices in between would otherwise launch on the wrong one).
+struct DeviceGuard {
+  int prev = -1;
+  bool switched = false;
+  explicit DeviceGuard(int want) {
+    if (want < 0) return;
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    if (prev != want) switched = hipSetDevice(want) == hipSuccess;
+  }
+  ~DeviceGuard() {
+    if (switched && prev >= 0) (void)hipSetDevice(prev);
+  }
+  DeviceGuard(const DeviceGuard&) = delete;
+  DeviceGuard& operator=(const DeviceGuard&) = delete;
+};
+
+// Raises the dynamic-LDS limit of kernels that may be launched with more than the default 64 KB.
+CXK_LOCAL inline hipError_t RaiseDynamicLds(std::initializer_list<const void*> kernels) {
+  for (const void* k : kernels) {
+    hipFuncAttributes attr;
+    hipError_t e = hipFuncGetAttributes(&attr, k);
+    if (e != hipSuccess) return e;
+    // static + dynamic LDS must stay within the 160 KB of a CU
+    const int dyn = std::min((int)kLdsLimit, 160 * 1024 - (int)attr.sharedSizeBytes);
+    e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, dyn);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+// The environment switches of cxk_finalize, read once per call (FinalizeImpl).
+struct FinalizeSwitches {
+  bool quirks_off = false;      // CXK_REFERENCE_QUIRKS=0: the two corrections instead of the reference as written
+  int chain_segments = -1;      // CXK_CHAIN_SEGMENTS: 0 keeps the reference's order, P asks for P segments
+  int sparse_lmi = -1;          // CXK_SPARSE_LMI=0 / 1 forces sparse evaluation never / always (tests)
+  int gemm_min_n = 9;           // CXK_GEMM_MIN_N: smallest LDS-resident order on the batched-GEMM assembly
+  bool schur_generic = false;   // CXK_LMI_SCHUR=generic: the LDS-resident literal kernel (comparison runs, tests)
+  bool no_herm_fold = false;    // CXK_NO_HERM_FOLD
+  bool no_packed_slack = false; // CXK_NO_PACKED_SLACK
+  int gram_splits = 0;          // CXK_GRAM_SPLITS: K splits of the GEMM assembly (0: chosen by shape)
+};
+
+// ---- kkt_context.hip
+int GridFor(size_t work, int block);
+int CheckReady(cxk_context* ctx);
+int FlushDeferred(cxk_context* ctx, bool keep_scalars = false, bool keep_y = false);
+
+// ---- kkt_cone_launch.hip
+CXK_LOCAL hipError_t RaiseConeLdsLimits();
+CXK_LOCAL int GroupConstraints(cxk_context* ctx, const FinalizeSwitches& sw);     // finalize: constraints of one shape form a group
+CXK_LOCAL int UploadGroup(cxk_context* ctx, Group& g, const FinalizeSwitches& sw);  // finalize: one group's data and work space
+bool ClockSample(cxk_context* ctx, int slot, hipEvent_t* e0, hipEvent_t* e1);
+CXK_LOCAL int LaunchSetIdentity(cxk_context* ctx);
+int LaunchSchur(cxk_context* ctx);
+// the bounds of every linear constraint on the line search's step (y0 = ctx->y2, y1 = ctx->y) into info2
+CXK_LOCAL int LaunchLinearLineSearch(cxk_context* ctx, double dinf_upper_bound, double c_scaling);
+int FlushDirection(cxk_context* ctx);
+CXK_LOCAL bool StepTailOk(const cxk_context* ctx, int affine);
+CXK_LOCAL int PrepareStepImpl(cxk_context* ctx, int affine, double c_weight, double e_weight, double* info, bool take, int* took,
+                    const double* cw_from = nullptr, double cw_scale = 1.0);
+CXK_LOCAL int LaunchTakeStep(cxk_context* ctx, double e_weight, double step_size, const double* step_from, bool skip_on_fail = false);
+CXK_LOCAL int SlackEigenvaluesImpl(cxk_context* ctx, double c_weight, double* out, const MuRuleArgs* rule);
+// the eigenvalue query with the selection of the barrier parameter (into ctx->mu_dev) in its launch; nobody waits
+CXK_LOCAL int SelectMuAsync(cxk_context* ctx, double c_weight, double divergence_upper_bound, int rank, double prev, double lb,
+                            double ub);
+
+// ---- kkt_tree_launch.hip
+CXK_LOCAL hipError_t RaiseTreeLdsLimits();
+int LaunchGather(cxk_context* ctx, bool with_rhs, double k, double bs, double cs);
+int LaunchSweep(cxk_context* ctx, int lb, int le, int mode, bool then_backward, bool with_rhs);
+int LaunchBackPair(cxk_context* ctx, const cxk_context::BackPair& bp);
+int LaunchChain(cxk_context* ctx, int mode);
+int LaunchTreeCore(cxk_context* ctx, int mode, bool with_rhs, bool backward);
+int LaunchTree(cxk_context* ctx, int mode, bool with_rhs, bool backward);
+int MakeFusedTreeArgs(cxk_context* ctx, FusedTreeArgs* out);
+int DebugReportTimeout(cxk_context* ctx);
+bool FusedTimedOut(const cxk_context* ctx);
+int DisableFusedTree(cxk_context* ctx);
+int RedoFactorSolveOnLevels(cxk_context* ctx);
+int LaunchStepScalars(cxk_context* ctx);
+// y <- k (bs b + cs AQc) - 2 AW (k from the device when k_from) / y <- cb b + cq AQc + cw AW; fail: the word to clear
+CXK_LOCAL int LaunchBuildRhs(cxk_context* ctx, double k, double bs, double cs, int* fail, const double* k_from = nullptr);
+CXK_LOCAL int LaunchBuildRhsComb(cxk_context* ctx, double cb, double cq, double cw, int* fail);
+CXK_LOCAL int LaunchMaskedCopy(cxk_context* ctx, int n, const double* in, double* out);       // counted variables, zeros elsewhere
+CXK_LOCAL int LaunchMaskedCopyPairs(cxk_context* ctx, int K, const double* in, double* out);  // owned constraints' pairs
+CXK_LOCAL int LaunchCopyDoubles(cxk_context* ctx, int n, const double* src, double* dst);
+enum ExchangeKernel { kExchangePack, kExchangeUnpack, kExchangeUnpackMatrix, kExchangePackSolve, kExchangeUnpackSolve };
+// (right-hand side cb b + cq AQc + cw AW)
+CXK_LOCAL int LaunchExchange(cxk_context* ctx, ExchangeKernel which, double cb, double cq, double cw);
+
+// ---- kkt_shard.hip
+int ShardAllReduce(cxk_context* ctx, double* buf, size_t count, int op);
+long ExchangeCount(const cxk_context* ctx);
+int ShardedTree(cxk_context* ctx, int mode, bool with_rhs, bool backward);
+int ResolveShardTimeout(cxk_context* ctx);
+int SettleBeforeUnmarked(cxk_context* ctx);
+
+// ---- kkt_qr.hip
+int QrFactor(cxk_context* ctx);
+int QrSolve(cxk_context* ctx);
+
+}  // namespace cxk_host
+
+extern "C" {  // kkt_cone_launch.hip
+int SyncMailbox(cxk_context* ctx);  // waits until everything enqueued so far has run and the mailbox carries its results
+bool TakeStepFromDeviceOk(const cxk_context* ctx);
+}
+
+#define CXK_ENTER_KEEP(ctx)                     \
+  if (CheckReady(ctx)) return CXK_FAILURE;      \
+  (ctx)->calls++;                               \
+  DeviceGuard cxk_device_guard_((ctx)->device); \
+  if (ResolveShardTimeout(ctx)) return CXK_FAILURE
+#define CXK_ENTER(ctx)   \
+  CXK_ENTER_KEEP(ctx);   \
+  if (FlushDeferred(ctx)) return CXK_FAILURE
