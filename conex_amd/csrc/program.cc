@@ -27,6 +27,7 @@
 #include "../../include/conex.h"
 #include "../../include/conex_kkt_hip.h"
 #include "mu_rule.h"
+#include "solve_route.h"
 
 namespace {
 
@@ -125,6 +126,13 @@ int RankOf(const Cone& c) {
   }
 }
 
+// The first min(cols, m) columns of a column-major rows x cols matrix in a zero-padded rows x m one.
+std::vector<double> PaddedColumns(const std::vector<double>& A, int rows, int cols, int m) {
+  std::vector<double> out((size_t)rows * m, 0.0);
+  std::copy(A.begin(), A.begin() + (size_t)rows * std::max(0, std::min(cols, m)), out.begin());
+  return out;
+}
+
 // Upload the builder state into a fresh device context (Initialize, cone_program.cc:78-112).
 int BuildContext(Program* p) {
   if (p->ctx) {
@@ -151,40 +159,25 @@ int BuildContext(Program* p) {
     int id = -1;
     const int m = static_cast<int>(c.vars.size());
     switch (c.kind) {
-      case kLmi: {
-        if (c.hermitian) {
-          const size_t sz = (size_t)c.order * c.order * c.hyper;
-          std::vector<double> A((size_t)m * sz, 0.0), C(sz, 0.0);
-          for (int v = 0; v < m && v < (int)c.mats.size(); v++)
-            if (!c.mats[v].empty()) std::copy(c.mats[v].begin(), c.mats[v].begin() + sz, A.begin() + v * sz);
-          if (!c.affine.empty()) std::copy(c.affine.begin(), c.affine.begin() + sz, C.begin());
-          id = cxk_add_hermitian(p->ctx, c.order, c.hyper, m, A.data(), C.data(), c.vars.data());
-          break;
-        }
-        const size_t nn = (size_t)c.order * c.order;
-        std::vector<double> A((size_t)m * nn, 0.0), C(nn, 0.0);
+      case kLmi: {  // (hyper is 1 for a DenseLMIConstraint)
+        const size_t sz = (size_t)c.order * c.order * c.hyper;
+        std::vector<double> A((size_t)m * sz, 0.0), C(sz, 0.0);
         for (int v = 0; v < m && v < (int)c.mats.size(); v++)
-          if (!c.mats[v].empty()) std::copy(c.mats[v].begin(), c.mats[v].begin() + nn, A.begin() + v * nn);
-        if (!c.affine.empty()) std::copy(c.affine.begin(), c.affine.begin() + nn, C.begin());
-        id = cxk_add_lmi(p->ctx, c.order, m, A.data(), C.data(), c.vars.data());
+          if (!c.mats[v].empty()) std::copy(c.mats[v].begin(), c.mats[v].begin() + sz, A.begin() + v * sz);
+        if (!c.affine.empty()) std::copy(c.affine.begin(), c.affine.begin() + sz, C.begin());
+        id = c.hermitian ? cxk_add_hermitian(p->ctx, c.order, c.hyper, m, A.data(), C.data(), c.vars.data())
+                         : cxk_add_lmi(p->ctx, c.order, m, A.data(), C.data(), c.vars.data());
         break;
       }
-      case kLinear: {
-        std::vector<double> A((size_t)c.order * m, 0.0);
-        for (int j = 0; j < m && j < c.cols; j++)
-          std::copy(c.A.begin() + (size_t)j * c.order, c.A.begin() + (size_t)(j + 1) * c.order,
-                    A.begin() + (size_t)j * c.order);
-        id = cxk_add_linear(p->ctx, c.order, m, A.data(), c.c.data(), c.vars.data());
+      case kLinear:
+        id = cxk_add_linear(p->ctx, c.order, m, PaddedColumns(c.A, c.order, c.cols, m).data(), c.c.data(),
+                            c.vars.data());
         break;
-      }
       case kSoc: {
-        const int len = c.order + 1;
-        std::vector<double> A((size_t)len * m, 0.0), cc(len, 0.0);
-        for (int j = 0; j < m && j < c.cols; j++)
-          std::copy(c.A.begin() + (size_t)j * len, c.A.begin() + (size_t)(j + 1) * len,
-                    A.begin() + (size_t)j * len);
+        std::vector<double> cc(c.order + 1, 0.0);
         std::copy(c.c.begin(), c.c.end(), cc.begin());
-        id = cxk_add_soc(p->ctx, c.order, m, A.data(), cc.data(), c.vars.data());
+        id = cxk_add_soc(p->ctx, c.order, m, PaddedColumns(c.A, c.order + 1, c.cols, m).data(), cc.data(),
+                         c.vars.data());
         break;
       }
       case kQuadCost:
@@ -194,14 +187,10 @@ int BuildContext(Program* p) {
         id = cxk_add_quadratic(p->ctx, c.order, m, c.Q.empty() ? nullptr : c.Q.data(), c.A.data(), c.c.data(),
                                c.vars.data());
         break;
-      case kEquality: {
-        std::vector<double> A((size_t)c.order * m, 0.0);
-        for (int j = 0; j < m && j < c.cols; j++)
-          std::copy(c.A.begin() + (size_t)j * c.order, c.A.begin() + (size_t)(j + 1) * c.order,
-                    A.begin() + (size_t)j * c.order);
-        id = cxk_add_equality(p->ctx, c.order, m, A.data(), c.c.data(), c.vars.data());
+      case kEquality:
+        id = cxk_add_equality(p->ctx, c.order, m, PaddedColumns(c.A, c.order, c.cols, m).data(), c.c.data(),
+                              c.vars.data());
         break;
-      }
     }
     CONEX_DEMAND(id >= 0, "constraint rejected while building the device program");
   }
@@ -258,22 +247,460 @@ Config FromApi(const CONEX_SolverConfiguration* c) {  // interfaces/conex.cc:65-
   return o;
 }
 
+// ---------------------------------------------------------------- conex::Solve cone_program.cc:235-533
+// SolveProgram at the end of this section reads as the list of its stages.  Which device calls an
+// iteration makes is decided once per iteration by cxk_route::Choose (solve_route.h).
+
+using Clock = std::chrono::steady_clock;
+double MsSince(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
+
+// How a stage, and with it an iteration, ends.
+enum class Outcome {
+  kNext,           // go on: the next stage, the next iteration
+  kRedo,           // the same iteration again, from the state it started with
+  kRetryCold,      // the warm start was aborted: counts as an iteration, the next one starts from identity
+  kCenteringDone,  // stop: the final centering budget is exhausted
+  kConverged,      // stop
+  kFailed,         // CONEX_Maximize returns 0
+  kFatal           // CONEX_Maximize returns 1, as the reference's CONEX_DEMAND does
+};
+
+// What a solve fixes before its first iteration, and its instruments.
+struct Solve {
+  Program* p;
+  const Config& cfg;
+  bool timers;   // CONEX_ENABLE_TIMER=1 (the reference's compile-time macro of debug_macros.h:18-52 as an
+                 // environment switch): device time of the four phases the reference brackets, per iteration
+  bool profile;  // CONEX_PROFILE=1: wall time of set-up, of the iteration loop and of the host side of each
+                 // device call on stderr
+  cxk_context* ctx = nullptr;
+  int N = 0, rankK = 0, initial_centering_steps = 0;
+  double phase_prev[CXK_PHASE_COUNT] = {0, 0, 0, 0, 0};
+  double prof_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  Clock::time_point t_loop;
+};
+enum ProfSlot { kProfAssemble, kProfFactorAsync, kProfMu, kProfFactorStatus, kProfDirection, kProfPrepare,
+                kProfScalars, kProfTakeStep };
+const char* const kProfName[8] = {"assemble", "factor_async", "mu selection", "factor_status",
+                                  "newton_direction", "prepare_step", "step_scalars", "take_step"};
+
+// call(), its host wall time added to the slot under CONEX_PROFILE
+template <class F>
+inline auto Timed(Solve& sv, ProfSlot slot, F&& call) -> decltype(call()) {
+  if (!sv.profile) return call();
+  const auto t0 = Clock::now();
+  const auto r = call();
+  sv.prof_ms[slot] += MsSince(t0);
+  return r;
+}
+
+// Everything the loop carries from one iteration to the next.  An iteration starts from a copy;
+// redoing it is assigning the copy back.
+struct Iterate {
+  double inv_sqrt_mu = 0, inv_sqrt_mu_max = 0;
+  double b_scaling = 1, c_scaling = 1;  // Program's, written back where SolveProgram leaves the loop
+  int centering_steps = 0;
+  bool warmstart_aborted = false;
+  double cx = 1, by = -1, kkt_error = 0;
+};
+
+// What one iteration's stages hand each other.
+struct Pass {
+  int i = 0;
+  bool warm_first = false;  // first iteration of a warm start: it may yet be aborted
+  bool initial_centering = false, final_centering = false, update_mu = false;
+  cxk_route::Route route{};
+  double selected = -1;  // host mu selection: the new inv_sqrt_mu, or not positive
+  double info[2] = {0, 0};
+  int took_step = 0;
+};
+
+bool EnvSwitchOn(const char* name) {
+  const char* e = getenv(name);
+  return e != nullptr && atoi(e) != 0;
+}
+
+// Initialize :78-112, then context, solver mode, refinement, timers, cost and the first iterate
+Outcome SetUp(Solve& sv, Iterate* st) {
+  Program* p = sv.p;
+  const Config& cfg = sv.cfg;
+  const auto t_start = Clock::now();
+  if (!p->initialized || p->dirty || cfg.initialization_mode == 0) {
+    if (p->dirty || !p->ctx) {
+      // "Sparsity Analysis(us)" of cone_program.cc:95-109: symbolic analysis + upload, host wall time
+      const auto t_sp = Clock::now();
+      if (BuildContext(p)) return Outcome::kFailed;
+      if (sv.timers)
+        printf("Sparsity Analysis(us): %.0f, \n",
+               std::chrono::duration<double, std::micro>(Clock::now() - t_sp).count());
+    }
+    if (cfg.initialization_mode == 0) {
+      p->b_scaling = 1;
+      p->c_scaling = 1;
+      if (cxk_set_identity(p->ctx)) return Outcome::kFailed;
+    }
+    p->initialized = true;
+  }
+  cxk_context* ctx = sv.ctx = p->ctx;
+  cxk_phase_timers(ctx, sv.timers ? 1 : 0);
+  if (cxk_set_solver_mode(ctx, cfg.kkt_solver)) return Outcome::kFailed;  // solver->SetSolverMode(config.kkt_solver) :305
+  if (sv.timers) cxk_phase_read(ctx, sv.phase_prev, 1);  // start this solve's phase totals from zero
+  for (int k = 0; k < CXK_PHASE_COUNT; k++) sv.phase_prev[k] = 0;
+  // solver.SetIterativeRefinementIterations(config.iterative_refinement_iterations)
+  if (cxk_set_iterative_refinement(ctx, cfg.iterative_refinement_iterations > 0 ? cfg.iterative_refinement_iterations : 0))
+    return Outcome::kFailed;
+  if (sv.profile) fprintf(stderr, "conex profile: set-up (symbolic analysis, plans, upload) %.2f ms\n", MsSince(t_start));
+  sv.t_loop = Clock::now();
+  p->sqrt_inv_mu.assign(std::max(cfg.max_iterations, 1), 0.0);
+  p->num_iter = 0;
+  p->stats_ready = true;
+  if (Verbose()) printf("\n");
+
+  sv.N = cxk_system_size(ctx);
+  std::vector<double> bin(p->num_vars);
+  for (int i = 0; i < p->num_vars; i++) bin[i] = -p->linear_cost[i];
+  if (cxk_set_cost(ctx, bin.data())) return Outcome::kFailed;
+
+  for (const Cone& c : p->cones) sv.rankK += RankOf(c);
+  sv.initial_centering_steps = cfg.initial_centering_steps_coldstart;
+  if (cfg.initialization_mode) {
+    PRINTSTATUS("Warmstarting...");
+    sv.initial_centering_steps = cfg.initial_centering_steps_warmstart;
+  }
+  st->inv_sqrt_mu_max = cfg.inv_sqrt_mu_max;
+  st->b_scaling = p->b_scaling;
+  st->c_scaling = p->c_scaling;
+  return Outcome::kNext;
+}
+
+// Whether this iteration centers, whether it selects a new mu, and whether the centering budget ends the loop
+Outcome DecideCentering(const Solve& sv, Pass* it, Iterate* st) {
+  const Config& cfg = sv.cfg;
+  it->initial_centering = it->i < sv.initial_centering_steps;
+  it->final_centering = (st->inv_sqrt_mu >= st->inv_sqrt_mu_max) || (st->kkt_error > cfg.kkt_error_tolerance) ||
+                        it->i >= (cfg.max_iterations - cfg.final_centering_steps);
+  it->update_mu = (it->i == 0) || !(it->initial_centering || it->final_centering) || st->warmstart_aborted;
+  st->warmstart_aborted = false;
+  if (it->final_centering && st->centering_steps >= cfg.final_centering_steps) return Outcome::kCenteringDone;
+  return Outcome::kNext;
+}
+
+// solver->Assemble() :338-341, and the first iteration's rescaling of b and c
+Outcome AssembleAndRescale(Solve& sv, const Pass& it, Iterate* st) {
+  const Config& cfg = sv.cfg;
+  cxk_context* ctx = sv.ctx;
+  cxk_phase_mark(ctx, CXK_PHASE_ASSEMBLE);
+  if (Timed(sv, kProfAssemble, [&] { return cxk_assemble(ctx); })) return Outcome::kFailed;
+  if (it.i < 1 && cfg.enable_rescaling) {
+    if (cfg.initialization_mode == 0) {
+      double sc[6];
+      if (cxk_step_scalars(ctx, sc)) return Outcome::kFailed;
+      st->b_scaling = 1.0 / (1 + std::sqrt(sc[2]));
+      st->c_scaling = 1.0 / (1 + std::sqrt(sc[3]));
+    }
+    double mu_target = 1.0 / (st->inv_sqrt_mu_max * st->inv_sqrt_mu_max);
+    mu_target *= (st->b_scaling * st->c_scaling);
+    st->inv_sqrt_mu_max = 1.0 / std::sqrt(mu_target);
+  }
+  return Outcome::kNext;
+}
+
+// The route of this iteration.  Both capabilities are asked behind this iteration's assembly and never
+// kept: a timed-out whole-tree launch switches the context to its level kernels, and the triple
+// right-hand side wants the assembly still waiting to ride in the factorization.
+cxk_route::Route ChooseRoute(const Solve& sv, const Pass& it) {
+  cxk_route::Inputs in{};
+  in.update_mu = it.update_mu;
+  in.line_search = sv.cfg.enable_line_search != 0;
+  in.quadratic_costs = sv.p->contains_quadratic_costs;
+  in.timers = sv.timers;
+  in.warm_first = it.warm_first;
+  in.device_mu_supported = cxk_device_mu_supported(sv.ctx) == 1;
+  in.triple_supported = cxk_triple_supported(sv.ctx) == 1;
+  return cxk_route::Choose(in);
+}
+
+// solver->Factor() :360.  The LLT flag travels back with the first host round trip of this
+// iteration (mu selection or PrepareStep); everything enqueued in between only overwrites
+// scratch state (y, the step temporaries) -- the PrepareStep kernels of the cones that keep
+// w^{1/2} in W (second-order, quadratic) and every TakeStep kernel read the flag on the device
+// and leave W alone when it is set -- so acting on the flag there is equivalent.
+// One upward pass serves the factorization and the first solve of the iteration: the
+// right-hand side of the mu selection (ComputeMuFromDivergence) when mu is updated without a
+// line search -- all three right-hand sides the Newton direction for ANY mu is a combination of
+// when the device selects it --, the Newton direction itself when mu stays (its value is final
+// before Factor()).
+Outcome EnqueueFactorization(Solve& sv, const Pass& it, Iterate* st) {
+  using cxk_route::Factor;
+  cxk_context* ctx = sv.ctx;
+  cxk_phase_mark(ctx, CXK_PHASE_FACTOR);  // (a fused first solve of the iteration rides in the factor sweep)
+  if (it.route.factor == Factor::kDirection) {
+    if (!it.initial_centering) st->centering_steps++;
+    ApplyLimits(&st->inv_sqrt_mu, std::sqrt(1.0 / (1e-15 + sv.cfg.maximum_mu)), st->inv_sqrt_mu_max);
+  }
+  const double bs = st->b_scaling, cs = st->c_scaling, mu = st->inv_sqrt_mu;
+  const int failed = Timed(sv, kProfFactorAsync, [&] {
+    switch (it.route.factor) {
+      case Factor::kTriple: return cxk_factor_solve_triple_async(ctx, bs, cs);
+      case Factor::kSolve: return cxk_factor_solve_async(ctx, -bs, cs, 0.0);
+      case Factor::kDirection: return cxk_factor_direction_async(ctx, mu, bs, cs);
+      default: return cxk_factor_async(ctx);
+    }
+  });
+  return failed ? Outcome::kFailed : Outcome::kNext;
+}
+
 // ComputeMuFromDivergence cone_program.cc:173-214
-int MuFromDivergence(Program* p, const Config& cfg, int rankK, double* out, bool solved_already = false) {
-  cxk_context* ctx = p->ctx;
-  const double bs = p->b_scaling, cs = p->c_scaling;
+int MuFromDivergence(const Solve& sv, const Iterate& st, bool solved_already, double* out) {
+  cxk_context* ctx = sv.ctx;
   // y = AQc*cs - b*bs ; SolveInPlace (already done when the factorization carried this right-hand side)
-  if (!solved_already && cxk_solve_rhs(ctx, -bs, cs, 0.0)) return 1;
+  if (!solved_already && cxk_solve_rhs(ctx, -st.b_scaling, st.c_scaling, 0.0)) return 1;
   double e4[4];
-  if (cxk_weighted_slack_eigenvalues(ctx, cs, e4)) return 1;
+  if (cxk_weighted_slack_eigenvalues(ctx, st.c_scaling, e4)) return 1;
   Wse mp;
   mp.lmin = e4[0];
   mp.lmax = e4[1];
   mp.frob = e4[2];
   mp.trace = e4[3];
-  const double inv = cxk_mu::SelectFromDivergence(cfg.divergence_upper_bound, rankK, mp);
-  *out = inv;
+  *out = cxk_mu::SelectFromDivergence(sv.cfg.divergence_upper_bound, sv.rankK, mp);
   return 0;
+}
+
+double MuLowerBound(const Config& cfg) { return std::sqrt(1.0 / (1e-15 + cfg.maximum_mu)); }
+
+// The selection of mu.  On the device (cxk_select_mu_async): the eigenvalue query's launch evaluates
+// the rule itself, the Newton direction and PrepareStep read inv_sqrt_mu from device memory, and the
+// host learns it, with everything else, from the one mailbox at the end of the iteration.  On the
+// host: it->selected, which AdoptMu takes once the factorization is known to have succeeded.
+Outcome SelectMu(Solve& sv, Pass* it, const Iterate& st) {
+  using cxk_route::Mu;
+  const Config& cfg = sv.cfg;
+  cxk_context* ctx = sv.ctx;
+  if (it->route.mu == Mu::kKept) return Outcome::kNext;
+  cxk_phase_mark(ctx, CXK_PHASE_OTHER);  // mu selection: untimed in the reference
+  if (it->route.mu == Mu::kDevice) {
+    const int failed = Timed(sv, kProfMu, [&] {
+      return cxk_select_mu_async(ctx, st.c_scaling, cfg.divergence_upper_bound, sv.rankK, st.inv_sqrt_mu,
+                                 MuLowerBound(cfg), st.inv_sqrt_mu_max);
+    });
+    return failed ? Outcome::kFailed : Outcome::kNext;
+  }
+  double temp = -1;
+  if (cfg.enable_line_search) {  // cone_program.cc:376-384
+    if (cxk_line_search(ctx, cfg.dinf_upper_bound, st.b_scaling, st.c_scaling, &temp)) return Outcome::kFailed;
+    if (temp < 0) temp = st.inv_sqrt_mu;
+  }
+  if (temp < 0) {
+    if (sv.p->contains_quadratic_costs) {
+      fprintf(stderr, "%s line %d: Solver terminating with error: line-search failed.\n", __FILE__, __LINE__);
+      return Outcome::kFatal;
+    }
+    if (Timed(sv, kProfMu, [&] { return MuFromDivergence(sv, st, it->route.mu_solve_done, &temp); }))
+      return Outcome::kFailed;
+  }
+  it->selected = temp;
+  return Outcome::kNext;
+}
+
+// :386-392 the host's selection, or half the current value; the limits (on the device: part of the rule)
+void AdoptMu(const Solve& sv, const Pass& it, Iterate* st) {
+  using cxk_route::Mu;
+  if (it.route.mu == Mu::kHost) {
+    if (it.selected > 0)
+      st->inv_sqrt_mu = it.selected;
+    else
+      st->inv_sqrt_mu *= .5;
+  }
+  if (it.route.mu != Mu::kDevice) ApplyLimits(&st->inv_sqrt_mu, MuLowerBound(sv.cfg), st->inv_sqrt_mu_max);
+}
+
+// What became of this iteration's factorization.  Called once per iteration, behind the host round
+// trip the route names (free there: the stream has been waited for).
+Outcome ReadFactorOutcome(Solve& sv, const Pass& it, Iterate* st) {
+  cxk_context* ctx = sv.ctx;
+  int ok = 0;
+  if (Timed(sv, kProfFactorStatus, [&] { return cxk_factor_status(ctx, &ok); })) return Outcome::kFailed;
+  if (ok) return Outcome::kNext;
+  // a wait inside the whole-tree launch ran out (shared device): nothing wrong with the matrix,
+  // the context has switched to its level kernels -- the same iteration again (W is untouched:
+  // every kernel that would have changed it looked at the failure flag first)
+  if (cxk_fused_tree_timed_out(ctx) == 1) return Outcome::kRedo;
+  if (it.warm_first) {
+    PRINTSTATUS("Aborting warmstart...");
+    cxk_set_identity(ctx);
+    st->warmstart_aborted = true;
+    return Outcome::kRetryCold;
+  }
+  sv.p->solved = 0;
+  PRINTSTATUS("Factorization failed.");
+  return Outcome::kFailed;
+}
+
+// The Newton direction :409-413 where the factorization did not carry it, and the step scalars
+Outcome NewtonDirection(Solve& sv, const Pass& it, const Iterate& st) {
+  using cxk_route::Direction;
+  cxk_context* ctx = sv.ctx;
+  cxk_phase_mark(ctx, CXK_PHASE_SOLVE);
+  if (it.route.direction == Direction::kDeviceMu) {
+    if (Timed(sv, kProfDirection, [&] { return cxk_newton_direction_device_mu(ctx, st.b_scaling, st.c_scaling); }))
+      return Outcome::kFailed;
+  } else if (it.route.direction == Direction::kHost) {
+    if (Timed(sv, kProfDirection,
+              [&] { return cxk_newton_direction(ctx, st.inv_sqrt_mu, st.b_scaling, st.c_scaling); }))
+      return Outcome::kFailed;
+  }
+  // by / cx of :439-446 need y only: same round trip
+  if (Timed(sv, kProfScalars, [&] { return cxk_step_scalars_async(ctx); })) return Outcome::kFailed;
+  return Outcome::kNext;
+}
+
+// PrepareStep :417.  Where the route allows, TakeStep is enqueued behind it with the step rule of
+// :417-418 evaluated on the device: the host round trip no longer separates them.
+Outcome PrepareStep(Solve& sv, Pass* it, Iterate* st) {
+  using Call = cxk_route::Step;
+  cxk_context* ctx = sv.ctx;
+  const double e_weight = 1, c_weight = st->inv_sqrt_mu * st->c_scaling;
+  cxk_phase_mark(ctx, CXK_PHASE_UPDATE);
+  const int failed = Timed(sv, kProfPrepare, [&] {
+    switch (it->route.step) {
+      case Call::kPrepareTakeDeviceMu:  // (the host learns the device's inv_sqrt_mu here)
+        return cxk_prepare_take_step_device_mu(ctx, st->c_scaling, e_weight, it->info, &it->took_step,
+                                               &st->inv_sqrt_mu);
+      case Call::kPrepareTake: return cxk_prepare_take_step(ctx, c_weight, e_weight, it->info, &it->took_step);
+      default: return cxk_prepare_step(ctx, 0, c_weight, e_weight, it->info);
+    }
+  });
+  return failed ? Outcome::kFailed : Outcome::kNext;
+}
+
+// The step scalars, then TakeStep :418-436 where PrepareStep's launch has not taken it -- or, on the first
+// iteration of a warm start that is too far from the central path, a cold start instead of the step
+Outcome TakeStep(Solve& sv, const Pass& it, Iterate* st, double sc[6]) {
+  cxk_context* ctx = sv.ctx;
+  double step_size = 2.0 / (it.info[1] * it.info[1]);
+  if (step_size > 1) step_size = 1;
+  if (Timed(sv, kProfScalars, [&] { return cxk_step_scalars(ctx, sc); })) return Outcome::kFailed;
+  if (it.warm_first && it.info[1] >= sv.cfg.warmstart_abort_threshold) {
+    PRINTSTATUS("Aborting warmstart...");
+    cxk_set_identity(ctx);
+    st->warmstart_aborted = true;
+  } else if (!it.took_step) {
+    if (Timed(sv, kProfTakeStep, [&] { return cxk_take_step(ctx, 0, 1.0, step_size); })) return Outcome::kFailed;
+  }
+  return Outcome::kNext;
+}
+
+// The iteration's line of the log, its statistics, and whether the loop has converged :439-470
+Outcome Report(Solve& sv, const Pass& it, const double sc[6], Iterate* st) {
+  Program* p = sv.p;
+  cxk_phase_mark(sv.ctx, CXK_PHASE_OTHER);
+  if (sv.timers) {  // "Assemble(us): 12, Factor(us): 40, ..." as the reference's END_TIMER prints them
+    double us[CXK_PHASE_COUNT];
+    if (cxk_phase_read(sv.ctx, us, 0) == CXK_SUCCESS) {
+      static const char* const names[4] = {"Assemble", "Factor", "Solve", "Update"};
+      for (int k = 0; k < 4; k++) printf("%s(us): %.0f, ", names[k], us[k] - sv.phase_prev[k]);
+      for (int k = 0; k < CXK_PHASE_COUNT; k++) sv.phase_prev[k] = us[k];
+    }
+  }
+  const double inv_sqrt_mu = st->inv_sqrt_mu, b_scaling = st->b_scaling, c_scaling = st->c_scaling;
+  const double d_2 = std::sqrt(std::fabs(it.info[0]));
+  const double d_inf = std::fabs(it.info[1]);
+  st->by = sc[0] * 1.0 / (inv_sqrt_mu * c_scaling);
+  st->cx = 2 * sc[4] + sc[1] - inv_sqrt_mu * sc[5] * c_scaling;
+  st->cx /= (inv_sqrt_mu * b_scaling);
+  double mu = 1.0 / inv_sqrt_mu;
+  mu *= mu;
+  const double s_dot_x = mu * (sv.rankK - d_2 * d_2) / (b_scaling * c_scaling);
+  mu = mu / (c_scaling * b_scaling);
+  REPORT(mu, mu);
+  REPORT(d_2, d_2);
+  REPORT(d_inf, d_inf);
+  if (!p->contains_quadratic_costs) {
+    REPORT(by, st->by);
+    REPORT(cx, st->cx);
+    st->kkt_error = std::fabs(st->cx - st->by - s_dot_x) / s_dot_x;
+    REPORT(kkt_error, st->kkt_error);
+  }
+  p->num_iter = it.i + 1;
+  p->sqrt_inv_mu[it.i] = inv_sqrt_mu;
+  if (Verbose()) printf("\n");
+  if ((it.final_centering || inv_sqrt_mu >= st->inv_sqrt_mu_max) && d_inf <= sv.cfg.final_centering_tolerance)
+    return Outcome::kConverged;
+  return Outcome::kNext;
+}
+
+// One iteration of :330-470 on the route chosen behind its assembly
+Outcome Iteration(Solve& sv, int i, Iterate* st) {
+  using cxk_route::OutcomeRead;
+  Pass it;
+  it.i = i;
+  it.warm_first = i == 0 && sv.cfg.initialization_mode == 1;
+  if (Verbose()) printf(i < 10 ? "i:  %d, " : "i: %d, ", i);
+  Outcome o;
+  if ((o = DecideCentering(sv, &it, st)) != Outcome::kNext) return o;
+  if ((o = AssembleAndRescale(sv, it, st)) != Outcome::kNext) return o;
+  it.route = ChooseRoute(sv, it);
+  if ((o = EnqueueFactorization(sv, it, st)) != Outcome::kNext) return o;
+  if ((o = SelectMu(sv, &it, *st)) != Outcome::kNext) return o;
+  if (it.route.outcome_read == OutcomeRead::kAfterMuSelection &&
+      (o = ReadFactorOutcome(sv, it, st)) != Outcome::kNext)
+    return o;
+  AdoptMu(sv, it, st);
+  if ((o = NewtonDirection(sv, it, *st)) != Outcome::kNext) return o;
+  if ((o = PrepareStep(sv, &it, st)) != Outcome::kNext) return o;
+  if (it.route.outcome_read == OutcomeRead::kAfterPrepare &&
+      (o = ReadFactorOutcome(sv, it, st)) != Outcome::kNext)
+    return o;
+  double sc[6];
+  if ((o = TakeStep(sv, it, st, sc)) != Outcome::kNext) return o;
+  return Report(sv, it, sc, st);
+}
+
+// Behind the loop :472-533: y, the infeasibility flags, the dual variables, the status line
+Outcome WrapUp(Solve& sv, const Iterate& st, bool max_iters_reached, double* yout) {
+  Program* p = sv.p;
+  const Config& cfg = sv.cfg;
+  cxk_context* ctx = sv.ctx;
+  const int m = p->num_vars;
+  if (sv.profile) fprintf(stderr, "conex profile: loop left after %.2f ms\n", MsSince(sv.t_loop));
+  std::vector<double> y(sv.N, 0.0);
+  if (cxk_get_y(ctx, y.data())) return Outcome::kFailed;
+  for (int i = 0; i < m; i++) yout[i] = y[i];
+  if (sv.profile) {
+    fprintf(stderr, "conex profile: %d iterations in %.2f ms (%.3f ms each)\n", p->num_iter, MsSince(sv.t_loop),
+            MsSince(sv.t_loop) / std::max(p->num_iter, 1));
+    for (int k = 0; k < 8; k++)
+      fprintf(stderr, "conex profile:   host time in %-18s %.3f ms per iteration\n", kProfName[k],
+              sv.prof_ms[k] / std::max(p->num_iter, 1));
+  }
+  double mu = 1.0 / st.inv_sqrt_mu;
+  mu *= mu;
+  if (mu > cfg.infeasibility_threshold) {
+    PRINTSTATUS("Infeasible Or Unbounded!!.");
+    p->solved = 0;
+    p->primal_infeasible = st.cx * st.inv_sqrt_mu <= -.5;
+    p->dual_infeasible = st.by * st.inv_sqrt_mu >= .5;
+  } else {
+    p->solved = 1;
+  }
+  if (cfg.prepare_dual_variables) {  // :500-516
+    int ok = 0;
+    if (cxk_assemble(ctx) || cxk_factor(ctx, &ok)) return Outcome::kFailed;
+    if (cxk_solve_rhs(ctx, st.inv_sqrt_mu * st.b_scaling, 0.0, -1.0)) return Outcome::kFailed;
+    double info[2];
+    if (cxk_prepare_step(ctx, 1, 0.0, 0.0, info)) return Outcome::kFailed;
+  }
+  if (p->solved) {
+    for (int i = 0; i < m; i++) yout[i] /= st.inv_sqrt_mu;
+    for (int i = 0; i < m; i++) yout[i] /= st.c_scaling;
+    if (max_iters_reached) {
+      p->solved = 0;
+      PRINTSTATUS("Terminating at maximum iteration limit.");
+    } else {
+      PRINTSTATUS("Solved.");
+    }
+  }
+  return Outcome::kNext;
 }
 
 // conex::Solve cone_program.cc:235-533. Returns the solved flag (1 = solved).
@@ -283,344 +710,39 @@ int SolveProgram(Program* p, const Config& cfg, double* yout) {
             "Must enable line search and disable rescaling for problems with quadratic costs.");
     return 1;  // the reference's CONEX_DEMAND returns 1 here too
   }
-  const int m = p->num_vars;
   p->solved = 0;
   p->primal_infeasible = 0;
   p->dual_infeasible = 0;
-  bool max_iters_reached = true;
   if (p->cones.empty()) {  // empty program :265-270
-    for (int i = 0; i < m; i++) yout[i] = -p->linear_cost[i] * std::numeric_limits<double>::infinity();
+    for (int i = 0; i < p->num_vars; i++) yout[i] = -p->linear_cost[i] * std::numeric_limits<double>::infinity();
     return 0;
   }
-  // CONEX_PROFILE=1 in the environment: wall time of set-up, of the iteration loop and of the
-  // host side of each device call on stderr
-  const bool profile = getenv("CONEX_PROFILE") != nullptr;
-  double prof_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  static const char* const prof_name[8] = {"assemble", "factor_async", "mu selection", "factor_status",
-                                           "newton_direction", "prepare_step", "step_scalars", "take_step"};
-#define TIMED(slot, expr)                                                                  \
-  [&]() {                                                                                  \
-    if (!profile) return (expr);                                                           \
-    const auto t0_ = std::chrono::steady_clock::now();                                     \
-    const auto r_ = (expr);                                                                \
-    prof_ms[slot] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0_).count(); \
-    return r_;                                                                             \
-  }()
-  const auto t_start = std::chrono::steady_clock::now();
-  auto since = [](std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  };
-  // Initialize :78-112
-  if (!p->initialized || p->dirty || cfg.initialization_mode == 0) {
-    if (p->dirty || !p->ctx) {
-      // "Sparsity Analysis(us)" of cone_program.cc:95-109: symbolic analysis + upload, host wall time
-      const auto t_sp = std::chrono::steady_clock::now();
-      if (BuildContext(p)) return 0;
-      if (getenv("CONEX_ENABLE_TIMER") && atoi(getenv("CONEX_ENABLE_TIMER")) != 0)
-        printf("Sparsity Analysis(us): %.0f, \n",
-               std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_sp).count());
-    }
-    if (cfg.initialization_mode == 0) {
-      p->b_scaling = 1;
-      p->c_scaling = 1;
-      if (cxk_set_identity(p->ctx)) return 0;
-    }
-    p->initialized = true;
-  }
-  cxk_context* ctx = p->ctx;
-  // CONEX_ENABLE_TIMER=1 (the reference's compile-time macro of debug_macros.h:18-52 as an
-  // environment switch): device time of the four phases the reference brackets, per iteration
-  const bool timers = getenv("CONEX_ENABLE_TIMER") != nullptr && atoi(getenv("CONEX_ENABLE_TIMER")) != 0;
-  cxk_phase_timers(ctx, timers ? 1 : 0);
-  if (cxk_set_solver_mode(ctx, cfg.kkt_solver)) return 0;  // solver->SetSolverMode(config.kkt_solver) :305
-  double phase_prev[CXK_PHASE_COUNT] = {0, 0, 0, 0, 0};
-  if (timers) {  // start this solve's phase totals from zero
-    cxk_phase_read(ctx, phase_prev, 1);
-    for (int k = 0; k < CXK_PHASE_COUNT; k++) phase_prev[k] = 0;
-  }
-  // solver.SetIterativeRefinementIterations(config.iterative_refinement_iterations)
-  if (cxk_set_iterative_refinement(ctx, cfg.iterative_refinement_iterations > 0 ? cfg.iterative_refinement_iterations : 0))
-    return 0;
-  if (profile) fprintf(stderr, "conex profile: set-up (symbolic analysis, plans, upload) %.2f ms\n", since(t_start));
-  const auto t_loop = std::chrono::steady_clock::now();
-  p->sqrt_inv_mu.assign(std::max(cfg.max_iterations, 1), 0.0);
-  p->num_iter = 0;
-  p->stats_ready = true;
-  if (Verbose()) printf("\n");
+  Solve sv{p, cfg, EnvSwitchOn("CONEX_ENABLE_TIMER"), getenv("CONEX_PROFILE") != nullptr};
+  Iterate st;
+  if (SetUp(sv, &st) != Outcome::kNext) return 0;
 
-  const int N = cxk_system_size(ctx);
-  std::vector<double> bin(m);
-  for (int i = 0; i < m; i++) bin[i] = -p->linear_cost[i];
-  if (cxk_set_cost(ctx, bin.data())) return 0;
-
-  double inv_sqrt_mu_max = cfg.inv_sqrt_mu_max;
-  double cx = 1, by = -1, kkt_error = 0;
-  double inv_sqrt_mu = 0, e_weight = 1, c_weight = 0, step_size = 1;
-  int rankK = 0;
-  for (const Cone& c : p->cones) rankK += RankOf(c);
-  int centering_steps = 0;
-  bool warmstart_aborted = false;
-  int initial_centering_steps = cfg.initial_centering_steps_coldstart;
-  int initial_centering = 1;
-  double& c_scaling = p->c_scaling;
-  double& b_scaling = p->b_scaling;
-  if (cfg.initialization_mode) {
-    PRINTSTATUS("Warmstarting...");
-    initial_centering_steps = cfg.initial_centering_steps_warmstart;
-  }
-
-  for (int i = 0; i < cfg.max_iterations; i++) {
-    // (state an iteration changes before it knows its factorization's outcome: restored by a redo)
-    const double redo_mu = inv_sqrt_mu, redo_mu_max = inv_sqrt_mu_max, redo_bs = b_scaling, redo_cs = c_scaling;
-    const int redo_centering = centering_steps;
-    const bool redo_aborted = warmstart_aborted;
-#define REDO_ITERATION()                  \
-  {                                       \
-    inv_sqrt_mu = redo_mu;                \
-    inv_sqrt_mu_max = redo_mu_max;        \
-    b_scaling = redo_bs;                  \
-    c_scaling = redo_cs;                  \
-    centering_steps = redo_centering;     \
-    warmstart_aborted = redo_aborted;     \
-    i--;                                  \
-    continue;                             \
-  }
-    if (i >= initial_centering_steps) initial_centering = 0;
-    if (Verbose()) printf(i < 10 ? "i:  %d, " : "i: %d, ", i);
-    const bool final_centering = (inv_sqrt_mu >= inv_sqrt_mu_max) ||
-                                 (kkt_error > cfg.kkt_error_tolerance) ||
-                                 i >= (cfg.max_iterations - cfg.final_centering_steps);
-    const bool update_mu = (i == 0) || !(initial_centering || final_centering) || warmstart_aborted;
-    warmstart_aborted = false;
-    if (final_centering) {
-      if (centering_steps >= cfg.final_centering_steps) {
-        max_iters_reached = (i >= cfg.max_iterations - 1);
-        break;
-      }
-    }
-    cxk_phase_mark(ctx, CXK_PHASE_ASSEMBLE);
-    if (TIMED(0, cxk_assemble(ctx))) return 0;
-    if (i < 1 && cfg.enable_rescaling) {
-      if (cfg.initialization_mode == 0) {
-        double sc[6];
-        if (cxk_step_scalars(ctx, sc)) return 0;
-        b_scaling = 1.0 / (1 + std::sqrt(sc[2]));
-        c_scaling = 1.0 / (1 + std::sqrt(sc[3]));
-      }
-      double mu_target = 1.0 / (inv_sqrt_mu_max * inv_sqrt_mu_max);
-      mu_target *= (b_scaling * c_scaling);
-      inv_sqrt_mu_max = 1.0 / std::sqrt(mu_target);
-    }
-    // solver->Factor() :360.  The LLT flag travels back with the next host round trip of this
-    // iteration (mu selection or PrepareStep); everything enqueued in between only overwrites
-    // scratch state (y, the step temporaries) -- the PrepareStep kernels of the cones that keep
-    // w^{1/2} in W (second-order, quadratic) and every TakeStep kernel read the flag on the device
-    // and leave W alone when it is set -- so acting on the flag there is equivalent.
-    // One upward pass serves the factorization and the first solve of the iteration: the
-    // right-hand side of the mu selection (ComputeMuFromDivergence) when mu is updated without a
-    // line search, the Newton direction itself when mu stays (its value is final before Factor()).
-    const bool fuse_mu_solve = update_mu && !cfg.enable_line_search;
-    const bool fuse_direction = !update_mu;
-    cxk_phase_mark(ctx, CXK_PHASE_FACTOR);  // (a fused first solve of the iteration rides in the factor sweep)
-    if (fuse_direction) {
-      if (initial_centering == 0) centering_steps++;
-      ApplyLimits(&inv_sqrt_mu, std::sqrt(1.0 / (1e-15 + cfg.maximum_mu)), inv_sqrt_mu_max);
-    }
-    // (the barrier parameter selected on the device, below: known before the factorization is enqueued, so
-    // that it can carry the three right-hand sides the Newton direction for ANY mu is a combination of)
-    const bool mu_on_device = fuse_mu_solve && !p->contains_quadratic_costs && !timers &&
-                              !(i == 0 && cfg.initialization_mode == 1) && cxk_device_mu_supported(ctx) == 1;
-    if (fuse_mu_solve && mu_on_device && cxk_triple_supported(ctx) == 1) {
-      if (TIMED(1, cxk_factor_solve_triple_async(ctx, b_scaling, c_scaling))) return 0;
-    } else if (fuse_mu_solve) {
-      if (TIMED(1, cxk_factor_solve_async(ctx, -b_scaling, c_scaling, 0.0))) return 0;
-    } else if (fuse_direction) {
-      if (TIMED(1, cxk_factor_direction_async(ctx, inv_sqrt_mu, b_scaling, c_scaling))) return 0;
-    } else {
-      if (TIMED(1, cxk_factor_async(ctx))) return 0;
-    }
-    enum { kOk, kRetry, kFailed, kRedo };
-    auto factor_outcome = [&]() -> int {
-      int ok = 0;
-      if (TIMED(3, cxk_factor_status(ctx, &ok))) return kFailed;
-      if (ok) return kOk;
-      // a wait inside the whole-tree launch ran out (shared device): nothing wrong with the matrix,
-      // the context has switched to its level kernels -- the same iteration again (W is untouched:
-      // every kernel that would have changed it looked at the failure flag first)
-      if (cxk_fused_tree_timed_out(ctx) == 1) return kRedo;
-      if (i == 0 && cfg.initialization_mode == 1) {
-        PRINTSTATUS("Aborting warmstart...");
-        cxk_set_identity(ctx);
-        warmstart_aborted = true;
-        return kRetry;
-      }
-      p->solved = 0;
-      PRINTSTATUS("Factorization failed.");
-      return kFailed;
-    };
-    // The selection of mu on the device (cxk_select_mu_async): the eigenvalue query's launch evaluates
-    // the rule below itself, the Newton direction and PrepareStep read inv_sqrt_mu from device memory,
-    // and the host learns it, with everything else, from the one mailbox at the end of the iteration.
-    const double mu_lb = std::sqrt(1.0 / (1e-15 + cfg.maximum_mu));
-    if (mu_on_device) {
-      cxk_phase_mark(ctx, CXK_PHASE_OTHER);
-      if (TIMED(2, cxk_select_mu_async(ctx, c_scaling, cfg.divergence_upper_bound, rankK, inv_sqrt_mu, mu_lb,
-                                       inv_sqrt_mu_max)))
-        return 0;
-    } else if (update_mu) {
-      cxk_phase_mark(ctx, CXK_PHASE_OTHER);  // mu selection: untimed in the reference
-      double temp = -1;
-      if (cfg.enable_line_search) {  // cone_program.cc:376-384
-        if (cxk_line_search(ctx, cfg.dinf_upper_bound, b_scaling, c_scaling, &temp)) return 0;
-        if (temp < 0) temp = inv_sqrt_mu;
-      }
-      if (temp < 0) {
-        if (p->contains_quadratic_costs) {
-          fprintf(stderr, "%s line %d: Solver terminating with error: line-search failed.\n", __FILE__,
-                  __LINE__);
-          return 1;
-        }
-        if (TIMED(2, MuFromDivergence(p, cfg, rankK, &temp, fuse_mu_solve))) return 0;
-      }
-      {
-        const int fo = factor_outcome();  // free: the mu selection above has waited for the stream
-        if (fo == kRedo) REDO_ITERATION();
-        if (fo == kRetry) continue;
-        if (fo == kFailed) return 0;
-      }
-      if (temp > 0)
-        inv_sqrt_mu = temp;
-      else
-        inv_sqrt_mu *= .5;
-    }
-    if (!mu_on_device) ApplyLimits(&inv_sqrt_mu, mu_lb, inv_sqrt_mu_max);  // (on the device: part of the rule)
-
-    cxk_phase_mark(ctx, CXK_PHASE_SOLVE);
-    if (mu_on_device) {
-      if (TIMED(4, cxk_newton_direction_device_mu(ctx, b_scaling, c_scaling))) return 0;
-    } else if (!fuse_direction && TIMED(4, cxk_newton_direction(ctx, inv_sqrt_mu, b_scaling, c_scaling))) {
-      return 0;
-    }
-    if (TIMED(6, cxk_step_scalars_async(ctx))) return 0;  // by / cx of :439-446 need y only: same round trip
-    e_weight = 1;
-    c_weight = inv_sqrt_mu * c_scaling;
-    double info[2];
-    cxk_phase_mark(ctx, CXK_PHASE_UPDATE);
-    // When the factorization's outcome is already known (mu was updated: the flag came back with the
-    // mu selection) and no warm-start check is pending, TakeStep is enqueued behind PrepareStep with
-    // the step rule below evaluated on the device: the host round trip no longer separates them.
-    int took_step = 0;
-    const bool step_on_device = update_mu && !(i == 0 && cfg.initialization_mode == 1);
-    if (mu_on_device) {
-      // (the first host round trip of this iteration: the factorization's outcome arrives with it)
-      if (TIMED(5, cxk_prepare_take_step_device_mu(ctx, c_scaling, e_weight, info, &took_step, &inv_sqrt_mu)))
-        return 0;
-      c_weight = inv_sqrt_mu * c_scaling;
-      const int fo = factor_outcome();
-      if (fo == kRedo) REDO_ITERATION();
-      if (fo == kRetry) continue;
-      if (fo == kFailed) return 0;
-    } else if (step_on_device) {
-      if (TIMED(5, cxk_prepare_take_step(ctx, c_weight, e_weight, info, &took_step))) return 0;
-    } else if (TIMED(5, cxk_prepare_step(ctx, 0, c_weight, e_weight, info))) {
-      return 0;
-    }
-    if (!update_mu) {
-      const int fo = factor_outcome();
-      if (fo == kRedo) REDO_ITERATION();
-      if (fo == kRetry) continue;
-      if (fo == kFailed) return 0;
-    }
-    step_size = 2.0 / (info[1] * info[1]);
-    if (step_size > 1) step_size = 1;
-    double sc[6];
-    if (TIMED(6, cxk_step_scalars(ctx, sc))) return 0;
-    if (i == 0 && cfg.initialization_mode == 1 && info[1] >= cfg.warmstart_abort_threshold) {
-      PRINTSTATUS("Aborting warmstart...");
-      cxk_set_identity(ctx);
-      warmstart_aborted = true;
-    } else if (!took_step) {
-      if (TIMED(7, cxk_take_step(ctx, 0, e_weight, step_size))) return 0;
-    }
-    cxk_phase_mark(ctx, CXK_PHASE_OTHER);
-    if (timers) {  // "Assemble(us): 12, Factor(us): 40, ..." as the reference's END_TIMER prints them
-      double us[CXK_PHASE_COUNT];
-      if (cxk_phase_read(ctx, us, 0) == CXK_SUCCESS) {
-        static const char* const names[4] = {"Assemble", "Factor", "Solve", "Update"};
-        for (int k = 0; k < 4; k++) printf("%s(us): %.0f, ", names[k], us[k] - phase_prev[k]);
-        for (int k = 0; k < CXK_PHASE_COUNT; k++) phase_prev[k] = us[k];
-      }
-    }
-    const double d_2 = std::sqrt(std::fabs(info[0]));
-    const double d_inf = std::fabs(info[1]);
-    by = sc[0] * 1.0 / (inv_sqrt_mu * c_scaling);
-    cx = 2 * sc[4] + sc[1] - inv_sqrt_mu * sc[5] * c_scaling;
-    cx /= (inv_sqrt_mu * b_scaling);
-    double mu = 1.0 / inv_sqrt_mu;
-    mu *= mu;
-    const double s_dot_x = mu * (rankK - d_2 * d_2) / (b_scaling * c_scaling);
-    mu = mu / (c_scaling * b_scaling);
-    REPORT(mu, mu);
-    REPORT(d_2, d_2);
-    REPORT(d_inf, d_inf);
-    if (!p->contains_quadratic_costs) {
-      REPORT(by, by);
-      REPORT(cx, cx);
-      kkt_error = std::fabs(cx - by - s_dot_x) / s_dot_x;
-      REPORT(kkt_error, kkt_error);
-    }
-    p->num_iter = i + 1;
-    p->sqrt_inv_mu[i] = inv_sqrt_mu;
-    if (Verbose()) printf("\n");
-    if (final_centering || inv_sqrt_mu >= inv_sqrt_mu_max) {
-      if (d_inf <= cfg.final_centering_tolerance) {
-        max_iters_reached = false;
-        break;
-      }
+  int i = 0;
+  Outcome o = Outcome::kNext;  // (still kNext behind the loop: it ran out of iterations)
+  while (o == Outcome::kNext && i < cfg.max_iterations) {
+    const Iterate start = st;
+    o = Iteration(sv, i, &st);
+    if (o == Outcome::kRedo) {
+      st = start;
+      o = Outcome::kNext;
+    } else if (o == Outcome::kRetryCold) {
+      i++;
+      o = Outcome::kNext;
+    } else if (o == Outcome::kNext) {
+      i++;
     }
   }
-  if (profile) fprintf(stderr, "conex profile: loop left after %.2f ms\n", since(t_loop));
-  std::vector<double> y(N, 0.0);
-  if (cxk_get_y(ctx, y.data())) return 0;
-  for (int i = 0; i < m; i++) yout[i] = y[i];
-  if (profile) {
-    fprintf(stderr, "conex profile: %d iterations in %.2f ms (%.3f ms each)\n", p->num_iter, since(t_loop),
-            since(t_loop) / std::max(p->num_iter, 1));
-    for (int k = 0; k < 8; k++)
-      fprintf(stderr, "conex profile:   host time in %-18s %.3f ms per iteration\n", prof_name[k],
-              prof_ms[k] / std::max(p->num_iter, 1));
-  }
-#undef TIMED
-
-  double mu = 1.0 / inv_sqrt_mu;
-  mu *= mu;
-  if (mu > cfg.infeasibility_threshold) {
-    PRINTSTATUS("Infeasible Or Unbounded!!.");
-    p->solved = 0;
-    p->primal_infeasible = cx * inv_sqrt_mu <= -.5;
-    p->dual_infeasible = by * inv_sqrt_mu >= .5;
-  } else {
-    p->solved = 1;
-  }
-  if (cfg.prepare_dual_variables) {  // :500-516
-    int ok = 0;
-    if (cxk_assemble(ctx) || cxk_factor(ctx, &ok)) return 0;
-    if (cxk_solve_rhs(ctx, inv_sqrt_mu * b_scaling, 0.0, -1.0)) return 0;
-    double info[2];
-    if (cxk_prepare_step(ctx, 1, 0.0, 0.0, info)) return 0;
-  }
-  if (p->solved) {
-    for (int i = 0; i < m; i++) yout[i] /= inv_sqrt_mu;
-    for (int i = 0; i < m; i++) yout[i] /= c_scaling;
-  }
-  if (p->solved) {
-    if (max_iters_reached) {
-      p->solved = 0;
-      PRINTSTATUS("Terminating at maximum iteration limit.");
-    } else {
-      PRINTSTATUS("Solved.");
-    }
-  }
+  p->b_scaling = st.b_scaling;
+  p->c_scaling = st.c_scaling;
+  if (o == Outcome::kFatal) return 1;
+  if (o == Outcome::kFailed) return 0;
+  const bool max_iters_reached =
+      o == Outcome::kNext || (o == Outcome::kCenteringDone && i >= cfg.max_iterations - 1);
+  if (WrapUp(sv, st, max_iters_reached, yout) != Outcome::kNext) return 0;
   return p->solved;
 }
 
