@@ -141,6 +141,14 @@ size_t LmiPrepareLds(int n, int m) {
   return sizeof(double) * (size_t)(3 * n * n + 6 * n + 2 * (n / 2 + 2) + m + 8);
 }
 size_t LmiTakeLds(int n) { return sizeof(double) * (size_t)(5 * n * n); }
+// Dynamic LDS of the second-order and quadratic cone kernels: what the launch sites ask for and what
+// GroupConstraints admits a cone by, so that an admitted cone can be launched at every stage.
+size_t SocSchurLds(int n, int m, bool staged) { return sizeof(double) * (size_t)(n + 1) * (size_t)(staged ? 2 * m + 4 : m + 2); }
+size_t SocPrepareLds(int n, int m) { return sizeof(double) * ((size_t)m + 3 * ((size_t)n + 1)); }
+size_t SocTakeLds(int n) { return sizeof(double) * 4 * ((size_t)n + 1); }
+size_t QuadSchurLds(int n, int m) { return sizeof(double) * (2 * (size_t)n + (size_t)m + 4); }
+size_t QuadPrepareLds(int n, int m) { return sizeof(double) * ((size_t)m + 4 * ((size_t)n + 1)); }
+size_t QuadTakeLds(int n) { return sizeof(double) * 3 * ((size_t)n + 1); }
 
 // ---- The kernel instance each per-constraint stage of an LMI group runs.  One chooser per stage: the
 // launch sites switch on its answer and cxk_lmi_kernels reports it, so the two cannot disagree.  The
@@ -293,6 +301,14 @@ hipError_t RaiseConeLdsLimits() {
         reinterpret_cast<const void*>(&lmi_take_step_generic<0>),
         reinterpret_cast<const void*>(&soc_schur<true>),
         reinterpret_cast<const void*>(&soc_schur<false>),
+        // a long thin cone ((n + 1) x (m + 2) within LDS, n in the thousands) passes 64 KB in its step kernels too
+        reinterpret_cast<const void*>(&soc_prepare<0>),
+        reinterpret_cast<const void*>(&soc_prepare<1>),
+        reinterpret_cast<const void*>(&soc_take_step),
+        reinterpret_cast<const void*>(&quad_schur),
+        reinterpret_cast<const void*>(&quad_prepare<0>),
+        reinterpret_cast<const void*>(&quad_prepare<1>),
+        reinterpret_cast<const void*>(&quad_take_step),
     });
   });
 }
@@ -483,8 +499,8 @@ int LaunchSchur(cxk_context* ctx) {
       {
         // one wavefront per cone, up to four cones per workgroup; the cone's data staged in LDS when
         // four staged images fit, read in place otherwise
-        const size_t staged = sizeof(double) * (size_t)(g.n + 1) * (2 * g.m + 4);
-        const size_t plain = sizeof(double) * (size_t)(g.n + 1) * (g.m + 2);
+        const size_t staged = SocSchurLds(g.n, g.m, true);
+        const size_t plain = SocSchurLds(g.n, g.m, false);
         if (4 * staged <= kLdsLimit) {
           soc_schur<true><<<(count + 3) / 4, 256, 4 * staged, ctx->stream>>>(MakeVec(g), ar);
         } else {
@@ -497,7 +513,7 @@ int LaunchSchur(cxk_context* ctx) {
         static_schur<<<count, 64, 0, ctx->stream>>>(MakeStatic(g), ar);
         break;
       case CXK_QUAD:
-        quad_schur<<<count, 64, sizeof(double) * (size_t)(2 * g.n + g.m + 4), ctx->stream>>>(MakeQuad(g), ar);
+        quad_schur<<<count, 64, QuadSchurLds(g.n, g.m), ctx->stream>>>(MakeQuad(g), ar);
         break;
       case CXK_OCT:
         oct_schur<<<count, 64, 0, ctx->stream>>>(MakeOct(g), ar);
@@ -532,11 +548,22 @@ int GroupConstraints(cxk_context* ctx, const FinalizeSwitches& sw) {
                                  "the large-order kernels use tr(W A_i W A_j) = tr(P_i P_j), which needs A_i = A_i^T");
       }
     }
-    if (c.type == CXK_SOC)
+    if (c.type == CXK_SOC) {
       // soc_schur keeps a cone's (n + 1) x (m + 2) image in LDS (CONEX_NewLorentzConeConstraint makes a
       // cone's matrix as wide as its largest variable index: thousands of columns are possible there)
-      CXK_DEMAND(sizeof(double) * (size_t)(c.n + 1) * (size_t)(c.m + 2) <= kLdsLimit,
+      CXK_DEMAND(SocSchurLds(c.n, c.m, false) <= kLdsLimit,
                  "a second-order cone whose (dimension + 1) x (variables + 2) image exceeds LDS (160 KB) is not supported");
+      // soc_take_step keeps four vectors of the cone in LDS, soc_prepare three and y: with one variable
+      // they, not the image above, are what has to fit
+      CXK_DEMAND(SocTakeLds(c.n) <= kLdsLimit && SocPrepareLds(c.n, c.m) <= kLdsLimit,
+                 "a second-order cone whose step kernels need more than the 163 328 B of LDS (four vectors of dimension + 1) is "
+                 "not supported");
+    }
+    if (c.type == CXK_QUAD)
+      // quad_prepare keeps y and four vectors of the cone in LDS; quad_schur and quad_take_step need less
+      CXK_DEMAND(QuadPrepareLds(c.n, c.m) <= kLdsLimit && QuadSchurLds(c.n, c.m) <= kLdsLimit && QuadTakeLds(c.n) <= kLdsLimit,
+                 "a quadratic cone whose step kernels need more than the 163 328 B of LDS (variables + four vectors of "
+                 "dimension + 1) is not supported");
     auto key = std::make_tuple(c.type, c.n, c.m, c.herm_d + (c.sparse ? 16 : 0) + (c.type == CXK_LMI && !c.symmetric ? 32 : 0) +
                                                      (c.type == CXK_QUAD && !c.Q.empty() ? 64 : 0));
     auto it = gmap.find(key);
@@ -1049,10 +1076,9 @@ int LaunchPrepareGroups(cxk_context* ctx, int pmode, const StepArgs& sa, const S
     else if (g.type == CXK_LINEAR)
       linear_prepare<MODE><<<cnt, 256, sizeof(double) * g.m, ctx->stream>>>(MakeVec(g), sa);
     else if (g.type == CXK_SOC)
-      soc_prepare<MODE><<<cnt, 64, sizeof(double) * (size_t)(g.m + 3 * (g.n + 1)), ctx->stream>>>(
-          MakeVec(g), sa);
+      soc_prepare<MODE><<<cnt, 64, SocPrepareLds(g.n, g.m), ctx->stream>>>(MakeVec(g), sa);
     else if (g.type == CXK_QUAD)
-      quad_prepare<MODE><<<cnt, 64, sizeof(double) * (size_t)(g.m + 4 * (g.n + 1)), ctx->stream>>>(MakeQuad(g), sa);
+      quad_prepare<MODE><<<cnt, 64, QuadPrepareLds(g.n, g.m), ctx->stream>>>(MakeQuad(g), sa);
     else if (g.type == CXK_OCT)
       oct_prepare<MODE><<<cnt, 64, sizeof(double) * (size_t)g.m, ctx->stream>>>(MakeOct(g), sa);
   }
@@ -1169,9 +1195,9 @@ int LaunchTakeStep(cxk_context* ctx, double e_weight, double step_size, const do
     else if (g.type == CXK_LINEAR)
       linear_take_step<<<GridFor((size_t)cnt * g.n, 256), 256, 0, ctx->stream>>>(MakeVec(g), sa);
     else if (g.type == CXK_SOC)
-      soc_take_step<<<cnt, 64, sizeof(double) * (size_t)(4 * (g.n + 1)), ctx->stream>>>(MakeVec(g), sa);
+      soc_take_step<<<cnt, 64, SocTakeLds(g.n), ctx->stream>>>(MakeVec(g), sa);
     else if (g.type == CXK_QUAD)
-      quad_take_step<<<cnt, 64, sizeof(double) * (size_t)(3 * (g.n + 1)), ctx->stream>>>(MakeQuad(g), sa);
+      quad_take_step<<<cnt, 64, QuadTakeLds(g.n), ctx->stream>>>(MakeQuad(g), sa);
     else if (g.type == CXK_OCT)
       oct_take_step<<<cnt, 64, 0, ctx->stream>>>(MakeOct(g), sa);
   }

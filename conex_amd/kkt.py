@@ -94,6 +94,7 @@ _SIGNATURES = {
     "cxk_lmi_kernel_name": (C.c_char_p, [C.c_int]),
     "cxk_lmi_kernel_count": (C.c_int, []),
     "cxk_get_step_info": (C.c_int, [C.c_void_p, c_double_p]),
+    "cxk_line_search": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_double, c_double_p]),
     "cxk_fused_assembly": (C.c_int, [C.c_void_p]),
     "cxk_fused_tree": (C.c_int, [C.c_void_p]),
     "cxk_comm_init_rccl_solo": (C.c_int, [C.c_void_p]),
@@ -494,6 +495,14 @@ class KktContext:
 
     def take_step(self, step_size, e_weight=1.0, affine=0):
         self._check(self.L.cxk_take_step(self.h, affine, e_weight, step_size), "cxk_take_step")
+
+    def line_search(self, dinf_upper_bound, b_scaling=1.0, c_scaling=1.0):
+        """ComputeMuFromLineSearch with the current factorization and cost (cxk_line_search): the admissible
+        inv_sqrt_mu, or -1 (an empty interval, or a cone without line-search support).  Overwrites y."""
+        out = np.zeros(1)
+        self._check(self.L.cxk_line_search(self.h, dinf_upper_bound, b_scaling, c_scaling, _dp(out)),
+                    "cxk_line_search")
+        return float(out[0])
 
     def weighted_slack_eigenvalues(self, y, c_weight):
         if y is not None:
