@@ -377,6 +377,13 @@ struct cxk_context {
   DevBuf<double> tail_slots;  // two sets of 4 per constraint, armed with kTailSentinel, used in turn
   int tail_parity = 0;
   DevBuf<double> mu_dev;      // [1] inv_sqrt_mu as selected on the device (cxk_select_mu_async)
+  // cxk_solve_block (kkt_solve_block.hip): the permuted block in chunks of columns, the forward-solve slots of every
+  // chunk, the device image of a host block, the permutation; allocated on first use, grown to the widest block seen
+  struct SolveBlock {
+    DevBuf<double> xp, slots, stage;
+    DevBuf<int> pinv;
+    int chunks = 0;
+  } solve_block;
 };
 
 #define CXK_TRY(expr)                                                                       \

@@ -131,6 +131,9 @@ _SIGNATURES = {
     "cxk_debug_force_fused_timeout": (C.c_int, [C.c_void_p]),
     "cxk_debug_fused_timeout_at": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "cxk_set_iterative_refinement": (C.c_int, [C.c_void_p, C.c_int]),
+    "cxk_solve_block": (C.c_int, [C.c_void_p, c_double_p, C.c_int, C.c_int]),
+    "cxk_solve_block_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    "cxk_solve_block_chunk_width": (C.c_int, []),
 }
 
 
@@ -186,6 +189,7 @@ class KktContext:
         if rc != 0:
             raise KktError(f"cxk_create failed for device {device} (no usable HIP device?)")
         self.h = h
+        self.stream = stream
         self.num_vars = num_vars
         self.cons = []
 
@@ -419,6 +423,50 @@ class KktContext:
         y = np.ascontiguousarray(y, dtype=np.float64).copy()
         self._check(self.L.cxk_solve_inplace(self.h, _dp(y)), "cxk_solve_inplace")
         return y
+
+    def solve_block(self, Y):
+        """Y <- K^-1 Y for a block of right-hand sides with the stored factor (cxk_solve_block).
+
+        A numpy array of shape (N, nrhs), any memory order (1-D: one column), is solved into a new array.
+        A torch float64 tensor of shape (N, nrhs) on the context's device is solved IN PLACE through its
+        data_ptr() and returned; it must be stored column-major (``t.T.contiguous().T``).  The solve is
+        enqueued on the context's stream: when that is not torch's current stream, both are waited for."""
+        if hasattr(Y, "data_ptr") and hasattr(Y, "is_contiguous"):
+            return self._solve_block_torch(Y)
+        Y = np.asarray(Y)
+        if Y.dtype.kind not in "fiu":
+            raise ValueError(f"solve_block: expected real numbers, got dtype {Y.dtype}")
+        one = Y.ndim == 1
+        if Y.ndim not in (1, 2):
+            raise ValueError(f"solve_block: expected a 1-D or 2-D array, got {Y.ndim} dimensions")
+        B = Y.reshape(-1, 1) if one else Y
+        if B.shape[0] != self.N or B.shape[1] < 1:
+            raise ValueError(f"solve_block: expected shape ({self.N}, nrhs) with nrhs >= 1, got {Y.shape}")
+        F = np.array(B, dtype=np.float64, order="F")  # a new array, column-major
+        self._check(self.L.cxk_solve_block(self.h, _dp(F), F.shape[0], F.shape[1]), "cxk_solve_block")
+        return F[:, 0].copy() if one else F
+
+    def _solve_block_torch(self, t):
+        import torch
+        if t.dtype != torch.float64:
+            raise ValueError(f"solve_block: expected a float64 tensor, got {t.dtype}")
+        if not t.is_cuda:
+            raise ValueError("solve_block: the tensor must live on the GPU (pass a numpy array for host data)")
+        if t.dim() != 2 or t.shape[0] != self.N or t.shape[1] < 1:
+            raise ValueError(f"solve_block: expected shape ({self.N}, nrhs) with nrhs >= 1, got {tuple(t.shape)}")
+        if t.stride(0) != 1 or (t.shape[1] > 1 and t.stride(1) < t.shape[0]):
+            raise ValueError("solve_block: the tensor must be stored column-major (strides (1, ld) with ld >= N), "
+                             "for example t.T.contiguous().T")
+        ld = int(t.stride(1)) if t.shape[1] > 1 else int(t.shape[0])
+        cur = torch.cuda.current_stream(t.device)
+        shared = self.stream is not None and int(self.stream) == int(cur.cuda_stream)
+        if not shared:
+            cur.synchronize()
+        self._check(self.L.cxk_solve_block_device(self.h, C.c_void_p(t.data_ptr()), ld, int(t.shape[1])),
+                    "cxk_solve_block_device")
+        if not shared:
+            self.sync()
+        return t
 
     def set_cost(self, b):
         b = np.ascontiguousarray(np.asarray(b, dtype=np.float64).ravel())

@@ -190,6 +190,17 @@ int cxk_kkt_solve_async(cxk_context* ctx, double inv_sqrt_mu, double b_scaling,
 int cxk_sync(cxk_context* ctx, int* factor_ok);
 /* SolveInPlace on a host vector of length N (copy in, solve, copy out). */
 int cxk_solve_inplace(cxk_context* ctx, double* y);
+/* Y <- K^-1 Y for nrhs columns with the factor of the latest factorization.  Y is N x nrhs, column-major with
+ * leading dimension ld >= N, in the ORIGINAL variable order (cxk_solve_inplace's convention).  The plain factor
+ * solve: level-scheduled block substitution, cxk_solve_block_chunk_width() columns per workgroup, the factor read
+ * once per chunk; column j of the result depends on column j of the input only, runs are bit-reproducible.
+ * Leaves y, W, the slab, the residuals and the three solutions of cxk_factor_solve_triple_async alone.  Refused
+ * (cxk_last_error names the reason): no successful factorization yet, nrhs < 1, ld < N, a null pointer, a sharded
+ * context, QR solver mode, cxk_set_iterative_refinement > 0.  Waits only where the outcome of the latest
+ * factorization has not been read yet. */
+int cxk_solve_block(cxk_context* ctx, double* Y_host, int ld, int nrhs);        /* copies in, solves, copies out, waits */
+int cxk_solve_block_device(cxk_context* ctx, double* Y_dev, int ld, int nrhs);  /* device pointer, enqueued on the context's stream, does not wait */
+int cxk_solve_block_chunk_width(void);
 /* (sharded context with a communicator: a COLLECTIVE -- a sum all-reduce of N doubles assembles the
  * whole vector, so every rank must call it, in the same order relative to its other cxk_* calls) */
 int cxk_get_y(cxk_context* ctx, double* y /* N, original variable order */);
