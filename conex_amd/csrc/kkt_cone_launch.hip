@@ -14,6 +14,7 @@
 #include "kernels_lmi_rows.hip.h"
 #include "kernels_lmi_large.hip.h"
 #include "kernels_quad.hip.h"
+#include "kernels_soc_stream.hip.h"
 
 namespace cxk_host {
 
@@ -77,6 +78,18 @@ VecGroup MakeVec(Group& g) {
   d.T1 = g.T1.p;
   d.T2 = g.T2.p;
   d.ids = g.dids.p;
+  return d;
+}
+SocStreamGroup MakeSocStream(Group& g) {
+  SocStreamGroup d;
+  const size_t per = g.ids.size() * ((size_t)g.n + 1);
+  d.v = MakeVec(g);
+  d.WA = g.ws_main.p;
+  d.s = g.st_vec.p;
+  d.wc = g.st_vec.p + per;
+  d.ms = g.st_vec.p + 2 * per;
+  d.dets = g.st_det.p;
+  d.Gf = g.ws_gf.p;
   return d;
 }
 StaticGroup MakeStatic(Group& g) {
@@ -441,6 +454,41 @@ hipError_t LaunchLmiSchurSparse(Group& g, LmiKernel kern, const Arena& ar, hipSt
   return LaunchLmiSparseKernel<false>(g, d, ar, X, st);
 }
 
+// The Schur complement of a group of streamed second-order cones: vectors, apply, Gram (the batched GEMM with
+// SYRK-shaped output, split along len when that is long), mirror.  Stream order is the only dependency.
+hipError_t LaunchSocStreamSchur(Group& g, const Arena& ar, hipStream_t st) {
+  const SocStreamGroup d = MakeSocStream(g);
+  const int cnt = d.v.count, len = d.v.len, m = d.v.m;
+  soc_stream_vectors<<<cnt, kSocStreamBlock, 0, st>>>(d, ar);
+  if (m == 0 || g.st_stages == 1) return hipGetLastError();
+  soc_stream_apply<<<(unsigned)((size_t)cnt * m), kSocStreamBlock, 0, st>>>(d, ar);
+  if (g.st_stages == 2) return hipGetLastError();
+  const int64_t mm = (int64_t)m * m;
+  constexpr int kMaxBatch = 65535;  // gridDim.z
+  for (int b0 = 0; b0 < cnt; b0 += kMaxBatch) {
+    const int nb = std::min(kMaxBatch, cnt - b0);
+    GemmArgs a{};
+    a.M = a.N = m;
+    a.K = len;
+    a.A = a.B = d.WA + (size_t)b0 * len * m;
+    a.lda = a.ldb = len;
+    a.sA1 = a.sB1 = (int64_t)len * m;
+    a.C = d.Gf + (size_t)b0 * mm;
+    a.ldc = m;
+    a.sC1 = mm;
+    a.inner = 1;
+    a.alpha = 2.0;
+    a.beta = 0.0;
+    a.lower_only = 1;
+    a.splits = g.splits;
+    a.sCs = (int64_t)std::min(cnt, kMaxBatch) * mm;
+    const hipError_t e = LaunchGemmSplitK(a, true, false, nb, g.ws_part.p, st);
+    if (e != hipSuccess) return e;
+  }
+  soc_stream_mirror<<<GridFor((size_t)cnt * mm, kSocStreamBlock), kSocStreamBlock, 0, st>>>(d, ar);
+  return hipGetLastError();
+}
+
 // A hipEvent pair for this launch of a clock slot's kernels, when it is one of the sampled ones.
 bool ClockSample(cxk_context* ctx, int slot, hipEvent_t* e0, hipEvent_t* e1) {
   *e0 = *e1 = nullptr;
@@ -496,7 +544,13 @@ int LaunchSchur(cxk_context* ctx) {
         linear_schur<<<count, 256, 0, ctx->stream>>>(MakeVec(g), ar);
         break;
       case CXK_SOC:
-      {
+      if (g.streamed) {
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        const bool sample = ClockSample(ctx, CXK_CLOCK_ASSEMBLY, &e0, &e1);
+        if (sample) CXK_TRY(hipEventRecord(e0, ctx->stream));
+        CXK_TRY(LaunchSocStreamSchur(g, ar, ctx->stream));
+        if (sample) CXK_TRY(hipEventRecord(e1, ctx->stream));
+      } else {
         // one wavefront per cone, up to four cones per workgroup; the cone's data staged in LDS when
         // four staged images fit, read in place otherwise
         const size_t staged = SocSchurLds(g.n, g.m, true);
@@ -529,8 +583,11 @@ int GroupConstraints(cxk_context* ctx, const FinalizeSwitches& sw) {
   const int K = (int)ctx->cons.size();
   std::map<std::tuple<int, int, int, int>, int> gmap;
   ctx->groups.clear();
+  // second-order cones beyond LDS: refused, or held in HBM (cxk_set_streamed_cones, else CXK_STREAMED_CONES)
+  const bool stream_on = ctx->streamed_cones >= 0 ? ctx->streamed_cones != 0 : sw.streamed_cones;
   for (int i = 0; i < K; i++) {
     ConstraintRec& c = ctx->cons[i];
+    c.streamed = false;
     if (!ctx->owned[i]) continue;
     if (c.type == CXK_LMI) {
       // sparse evaluation when it pays (CXK_SPARSE_LMI=0 / 1 forces never / always: tests)
@@ -549,6 +606,16 @@ int GroupConstraints(cxk_context* ctx, const FinalizeSwitches& sw) {
       }
     }
     if (c.type == CXK_SOC) {
+      c.streamed = stream_on && !(SocSchurLds(c.n, c.m, false) <= kLdsLimit && SocTakeLds(c.n) <= kLdsLimit &&
+                                  SocPrepareLds(c.n, c.m) <= kLdsLimit);
+    }
+    if (c.type == CXK_SOC && c.streamed) {
+      // held in HBM (kernels_soc_stream.hip.h): what remains is the int indexing of the kernels and of the GEMM
+      CXK_DEMAND((int64_t)(c.n + 1) * std::max(c.m, 1) <= INT_MAX - 1024,
+                 "a streamed second-order cone whose (dimension + 1) x variables entries exceed the int range is not supported");
+      CXK_DEMAND((int64_t)c.m * c.m <= INT_MAX,
+                 "a streamed second-order cone whose variables x variables Schur block exceeds the int range is not supported");
+    } else if (c.type == CXK_SOC) {
       // soc_schur keeps a cone's (n + 1) x (m + 2) image in LDS (CONEX_NewLorentzConeConstraint makes a
       // cone's matrix as wide as its largest variable index: thousands of columns are possible there)
       CXK_DEMAND(SocSchurLds(c.n, c.m, false) <= kLdsLimit,
@@ -565,7 +632,7 @@ int GroupConstraints(cxk_context* ctx, const FinalizeSwitches& sw) {
                  "a quadratic cone whose step kernels need more than the 163 328 B of LDS (variables + four vectors of "
                  "dimension + 1) is not supported");
     auto key = std::make_tuple(c.type, c.n, c.m, c.herm_d + (c.sparse ? 16 : 0) + (c.type == CXK_LMI && !c.symmetric ? 32 : 0) +
-                                                     (c.type == CXK_QUAD && !c.Q.empty() ? 64 : 0));
+                                                     (c.type == CXK_QUAD && !c.Q.empty() ? 64 : 0) + (c.streamed ? 128 : 0));
     auto it = gmap.find(key);
     if (it == gmap.end()) {
       it = gmap.emplace(key, (int)ctx->groups.size()).first;
@@ -577,6 +644,7 @@ int GroupConstraints(cxk_context* ctx, const FinalizeSwitches& sw) {
       ctx->groups.back().sparse = c.sparse;
       ctx->groups.back().literal = c.type == CXK_LMI && !c.symmetric;
       ctx->groups.back().has_q = c.type == CXK_QUAD && !c.Q.empty();
+      ctx->groups.back().streamed = c.streamed;
     }
     c.group = it->second;
     c.member = (int)ctx->groups[it->second].ids.size();
@@ -724,6 +792,19 @@ int UploadGroup(cxk_context* ctx, Group& g, const FinalizeSwitches& sw) {
     CXK_TRY(g.ws_main.alloc(cnt * 8 * nn));  // step temporaries; C W and W C W during assembly
     CXK_TRY(g.ws_part.alloc(cnt * 2 * kSparseCParts));
     CXK_TRY(g.ws_piv.alloc(cnt * (size_t)g.n));
+  }
+  if (g.streamed) {
+    const size_t len = (size_t)g.n + 1, m = (size_t)g.m;
+    CXK_DEMAND(cnt * std::max<size_t>(m, (len + kSocStreamRowTile - 1) / kSocStreamRowTile) <= (size_t)INT_MAX,
+               "a group of streamed second-order cones with more than 2^31 columns or row tiles is not supported");
+    g.splits = SocStreamSplits((int)len, g.m, (long long)cnt);
+    g.st_stages = sw.soc_stream_stages;
+    if (sw.gram_splits > 0) g.splits = sw.gram_splits;  // (comparison runs)
+    CXK_TRY(g.ws_main.alloc(cnt * len * m));
+    CXK_TRY(g.st_vec.alloc(3 * cnt * len));
+    CXK_TRY(g.st_det.alloc(cnt));
+    CXK_TRY(g.ws_gf.alloc(cnt * m * m));
+    CXK_TRY(g.ws_part.alloc(g.splits > 1 ? (size_t)g.splits * std::min<size_t>(cnt, 65535) * m * m : 0));
   }
   if (g.schur_gemm) {
     const size_t nn = (size_t)g.n * g.n, m1 = (size_t)g.m + 1;
@@ -1075,6 +1156,12 @@ int LaunchPrepareGroups(cxk_context* ctx, int pmode, const StepArgs& sa, const S
     }
     else if (g.type == CXK_LINEAR)
       linear_prepare<MODE><<<cnt, 256, sizeof(double) * g.m, ctx->stream>>>(MakeVec(g), sa);
+    else if (g.type == CXK_SOC && g.streamed) {
+      const SocStreamGroup d = MakeSocStream(g);
+      const int tiles = (g.n + 1 + kSocStreamRowTile - 1) / kSocStreamRowTile;
+      soc_stream_slack<<<(unsigned)((size_t)cnt * tiles), kSocStreamBlock, 0, ctx->stream>>>(d, sa, tiles);
+      soc_stream_prepare<MODE><<<cnt, kSocStreamBlock, 0, ctx->stream>>>(d, sa);
+    }
     else if (g.type == CXK_SOC)
       soc_prepare<MODE><<<cnt, 64, SocPrepareLds(g.n, g.m), ctx->stream>>>(MakeVec(g), sa);
     else if (g.type == CXK_QUAD)
@@ -1194,6 +1281,8 @@ int LaunchTakeStep(cxk_context* ctx, double e_weight, double step_size, const do
     }
     else if (g.type == CXK_LINEAR)
       linear_take_step<<<GridFor((size_t)cnt * g.n, 256), 256, 0, ctx->stream>>>(MakeVec(g), sa);
+    else if (g.type == CXK_SOC && g.streamed)
+      soc_stream_take_step<<<cnt, kSocStreamBlock, 0, ctx->stream>>>(MakeSocStream(g), sa);
     else if (g.type == CXK_SOC)
       soc_take_step<<<cnt, 64, SocTakeLds(g.n), ctx->stream>>>(MakeVec(g), sa);
     else if (g.type == CXK_QUAD)

@@ -100,6 +100,8 @@ static FinalizeSwitches ReadFinalizeSwitches() {
   sw.no_herm_fold = getenv("CXK_NO_HERM_FOLD") != nullptr;
   sw.no_packed_slack = getenv("CXK_NO_PACKED_SLACK") != nullptr;
   if ((v = getenv("CXK_GRAM_SPLITS"))) sw.gram_splits = std::max(1, atoi(v));
+  if ((v = getenv("CXK_STREAMED_CONES"))) sw.streamed_cones = atoi(v) != 0;
+  if ((v = getenv("CXK_SOC_STREAM_STAGES"))) sw.soc_stream_stages = atoi(v);
   return sw;
 }
 
@@ -451,6 +453,19 @@ int cxk_set_reference_identity(cxk_context* ctx, int on) {
   if (!ctx || ctx->finalized) return CXK_FAILURE;
   ctx->reference_identity = on != 0;
   return CXK_SUCCESS;
+}
+
+int cxk_set_streamed_cones(cxk_context* ctx, int on) {
+  if (!ctx) return CXK_FAILURE;
+  CXK_DEMAND(!ctx->finalized, "cxk_set_streamed_cones: the context is finalized (the choice is made by cxk_finalize)");
+  ctx->streamed_cones = on != 0;
+  return CXK_SUCCESS;
+}
+int cxk_count_streamed_cones(const cxk_context* ctx) {
+  if (!ctx || !ctx->finalized) return -1;
+  int k = 0;
+  for (size_t i = 0; i < ctx->cons.size(); i++) k += ctx->owned[i] && ctx->cons[i].streamed;
+  return k;
 }
 
 int cxk_finalize(cxk_context* ctx) {

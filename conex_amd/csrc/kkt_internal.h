@@ -41,6 +41,7 @@ struct ConstraintRec {
   std::vector<double> Q;  // CXK_QUAD: n x n inner-product matrix, empty = identity
   int group = -1, member = -1;
   bool sparse = false;  // LMI evaluated from its nonzeros (kernels_lmi_sparse.hip.h)
+  bool streamed = false;  // second-order cone beyond LDS, held in HBM (kernels_soc_stream.hip.h)
   // every A_i and C equals its transpose.  The fast kernels use tr(W A_i W A_j) = tr(P_i P_j),
   // P = A W, which needs that; anything else takes the literal kernels (dense_lmi_constraint.cc:72-88)
   bool symmetric = true;
@@ -113,6 +114,12 @@ struct Group {
   bool sp_small = false;           // W (and X) of a constraint fit in LDS
   DevBuf<int> sp_eptr, sp_erc, sp_pptr, sp_pvar, sp_pairs;
   DevBuf<double> sp_eval, sp_pval;
+  // second-order cones beyond LDS (cxk_set_streamed_cones): the kernels of kernels_soc_stream.hip.h; WA in ws_main,
+  // the Gram product's output in ws_gf and its split partials in ws_part (`splits` of them)
+  bool streamed = false;
+  DevBuf<double> st_vec;   // s, Q(s) c, the slack: three vectors per cone
+  DevBuf<double> st_det;   // det(s) per cone
+  int st_stages = 0;       // CXK_SOC_STREAM_STAGES: 1 / 2 = the assembly stops after the vectors / the apply stage (timing runs)
 };
 
 
@@ -144,6 +151,7 @@ struct cxk_context {
   Layout lay_ref;
   int chain_segments = -1;  // cxk_set_chain_segments: -1 automatic / environment, 0 off, P segments
   int segments = 0;         // segments in use (0: the reference's order)
+  int streamed_cones = -1;  // cxk_set_streamed_cones: -1 the environment's CXK_STREAMED_CONES (else off), 0 off, 1 on
   std::vector<Group> groups;
   std::vector<int64_t> g_off, r_off;
   std::vector<unsigned char> owned;      // constraint i assembled/updated by this rank

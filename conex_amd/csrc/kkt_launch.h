@@ -65,6 +65,8 @@ struct FinalizeSwitches {
   bool no_herm_fold = false;    // CXK_NO_HERM_FOLD
   bool no_packed_slack = false; // CXK_NO_PACKED_SLACK
   int gram_splits = 0;          // CXK_GRAM_SPLITS: K splits of the GEMM assembly (0: chosen by shape)
+  bool streamed_cones = false;  // CXK_STREAMED_CONES=1: second-order cones beyond LDS run from HBM (cxk_set_streamed_cones)
+  int soc_stream_stages = 0;    // CXK_SOC_STREAM_STAGES=1 / 2: their assembly stops after that stage (timing runs: wrong results)
 };
 
 // ---- kkt_context.hip

@@ -77,6 +77,7 @@ struct Program {
   bool dirty = true;
   int device = 0;
   int reference_identity = -1;  // -1: environment (CXK_REFERENCE_QUIRKS); see CONEX_HIP_SetReferenceIdentity
+  int streamed_cones = 1;       // second-order cones beyond LDS run from HBM; see CONEX_HIP_SetStreamedCones
   // multi-GPU (one process per GPU, every rank builds the same program): see CONEX_HIP_SetCommunicator
   int shard_rank = 0, shard_world = 1;
   int debug_timeout_at = -1, debug_timeout_site = 0;  // CONEX_HIP_DebugFusedTimeoutAt (test hook)
@@ -144,6 +145,9 @@ int BuildContext(Program* p) {
     return 1;
   }
   if (p->reference_identity >= 0) cxk_set_reference_identity(p->ctx, p->reference_identity);
+  // the reference takes a second-order cone of any size (CONEX_NewLorentzConeConstraint makes every cone as wide
+  // as the program): none is refused for its size here either
+  cxk_set_streamed_cones(p->ctx, p->streamed_cones);
   if (p->shard_world > 1) {
     if (cxk_set_shard(p->ctx, p->shard_rank, p->shard_world)) return 1;
     if (p->allreduce_fn) {
@@ -1288,6 +1292,17 @@ int CONEX_HIP_SetReferenceIdentity(void* x, int on) {
   Program* p = static_cast<Program*>(x);
   if (!p) return CONEX_FAILURE;
   p->reference_identity = on != 0;
+  p->dirty = true;
+  return CONEX_SUCCESS;
+}
+
+/* not part of conex.h: 1 (the default) = a second-order cone larger than LDS is held in HBM and runs on the
+ * streamed kernels (conex_kkt_hip.h, cxk_set_streamed_cones); 0 = such a cone is refused when the program is
+ * initialized, as the cxk_* interface does by default */
+int CONEX_HIP_SetStreamedCones(void* x, int on) {
+  Program* p = static_cast<Program*>(x);
+  if (!p) return CONEX_FAILURE;
+  p->streamed_cones = on != 0;
   p->dirty = true;
   return CONEX_SUCCESS;
 }

@@ -127,6 +127,8 @@ _SIGNATURES = {
     "cxk_kernel_clock": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_double_p]),
     "cxk_set_chain_segments": (C.c_int, [C.c_void_p, C.c_int]),
     "cxk_chain_segments": (C.c_int, [C.c_void_p]),
+    "cxk_set_streamed_cones": (C.c_int, [C.c_void_p, C.c_int]),
+    "cxk_count_streamed_cones": (C.c_int, [C.c_void_p]),
     "cxk_fused_tree_timed_out": (C.c_int, [C.c_void_p]),
     "cxk_debug_force_fused_timeout": (C.c_int, [C.c_void_p]),
     "cxk_debug_fused_timeout_at": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
@@ -743,6 +745,15 @@ class KktContext:
 
     def chain_segments(self):
         return self.L.cxk_chain_segments(self.h)
+
+    def set_streamed_cones(self, on=True):
+        """Second-order cones larger than LDS are held in HBM and run by the streamed kernels instead of being
+        refused at initialize (before initialize; default: CXK_STREAMED_CONES in the environment, else refused)."""
+        self._check(self.L.cxk_set_streamed_cones(self.h, int(bool(on))), "cxk_set_streamed_cones")
+
+    def count_streamed_cones(self):
+        """Constraints this context owns that run on the streamed second-order cone kernels."""
+        return self.L.cxk_count_streamed_cones(self.h)
 
     def fused_tree_timed_out(self):
         return bool(self.L.cxk_fused_tree_timed_out(self.h))

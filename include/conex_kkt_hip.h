@@ -121,6 +121,22 @@ int cxk_chain_segments(const cxk_context* ctx);
  * algorithm (tests/test_gpu_solver.py::test_reference_identity_reproduces_the_oracle_trajectory). */
 int cxk_set_reference_identity(cxk_context* ctx, int on);
 
+/* Second-order cones larger than LDS.  cxk_finalize admits a second-order cone to the LDS kernels when
+ * its (n + 1) x (m + 2) image, the four vectors of TakeStep and the m + 3 (n + 1) doubles of PrepareStep
+ * each fit the 163 328 B of a workgroup, and refuses any other.  Before cxk_finalize, on = 1: such a cone
+ * is not refused; it is held in HBM and run by the streamed kernels (kernels_soc_stream.hip.h: the O(len)
+ * maps on one striding workgroup per cone, G = 2 WA^T WA on the batched fp64 MFMA GEMM).  Cones that pass
+ * the three demands keep today's kernels and today's bits.  Every output, getter and setter of a
+ * streamed cone is that of any second-order cone; sharding, cxk_prepare_take_step and the device-selected
+ * barrier parameter take it as they take the others.
+ * Default (no call): the environment's CXK_STREAMED_CONES, else 0 = refuse.
+ * Two limits remain with the switch on, refused at cxk_finalize with a message naming them: (n + 1) m or
+ * m m beyond the int range; and the quadratic cone (cxk_add_quadratic), which keeps its LDS limits.
+ * cxk_count_streamed_cones: constraints this context owns that run on the streamed kernels (-1 before
+ * cxk_finalize; 0 on a host-only context, which chooses no kernels). */
+int cxk_set_streamed_cones(cxk_context* ctx, int on);
+int cxk_count_streamed_cones(const cxk_context* ctx);
+
 /* Initialize(): symbolic analysis (SupernodalKKTSolver ctor kkt_solver.cc:104-116),
  * Bind (kkt_solver.h:26-33), workspace carve + SetIdentity (cone_program.cc:78-112),
  * upload of constant data, construction of device index tables and level schedule.
