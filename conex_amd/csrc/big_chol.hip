@@ -26,7 +26,6 @@
 // lower-numbered ones, which the dispatcher starts first.
 #include <hip/hip_runtime.h>
 
-#define CXK_DEVICE_FUNCTIONS_ONLY
 #include "big_chol.h"
 #include "big_panel_solve.hip.h"
 

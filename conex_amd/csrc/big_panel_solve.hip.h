@@ -1,7 +1,7 @@
 // The register forward substitution with a factored 32 x 32 diagonal block that the blocked
 // factorizations of big supernodes share (kernels_kkt_big.hip.h: big_panel; big_chol.hip).
 #pragma once
-#include "kernels_kkt.hip.h"
+#include "dense_elim.hip.h"
 
 namespace cxk {
 

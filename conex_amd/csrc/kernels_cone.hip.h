@@ -12,6 +12,7 @@
 #include "device_utils.h"
 #include "kernels_lmi.hip.h"
 #include "mu_rule.h"
+#include "shard_mark.hip.h"
 
 namespace cxk {
 
@@ -520,7 +521,7 @@ __device__ __forceinline__ void MailboxPack(const MailboxArgs& m) {
 // after the sum every rank holds every rank's values and combines them in RANK ORDER
 // (step_slots_reduce): min / max / sum as the mode asks, the sums in one fixed order on every rank.
 // mode 0: {sum normsqrd, max norminfd}; mode 1: {min lambda_min, max lambda_max, sum frob, sum trace}.
-// Slot 4 world is the time-out mark (ShardMark, kernels_kkt.hip.h): a whole-tree launch of some rank whose wait ran
+// Slot 4 world is the time-out mark (ShardMark, shard_mark.hip.h): a whole-tree launch of some rank whose wait ran
 // out travels with the reduction to every rank.
 __global__ void step_slots_fill(int rank, int world, const double* __restrict__ red, double* __restrict__ slots,
                                 const int* __restrict__ fail, int tag, const double* host_flag) {
@@ -715,7 +716,7 @@ __device__ __forceinline__ void AgentStore(double* p, double v) {
   __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// step_scalars (kernels_kkt.hip.h, 1024 threads) on 256: thread r plays threads r, r + 256, r + 512,
+// step_scalars (kernels_kkt_vec.hip.h, 1024 threads) on 256: thread r plays threads r, r + 256, r + 512,
 // r + 768 -- the same fma chains, the same wave sums (wave (r >> 6) + 4 q of the 1024), the sixteen
 // wave totals added in the same order: the same bits.
 __device__ inline void StepScalarsOn256(int N, const double* __restrict__ b, const double* __restrict__ AQc,

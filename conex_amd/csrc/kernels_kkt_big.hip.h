@@ -15,7 +15,8 @@
 #include "big_chol.h"
 #include "big_panel_solve.hip.h"
 #include "kernels_gemm.hip.h"
-#include "kernels_kkt.hip.h"
+#include "kkt_records.h"
+#include "kkt_stamps.hip.h"
 
 namespace cxk {
 

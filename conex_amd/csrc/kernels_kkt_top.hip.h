@@ -22,28 +22,12 @@
 // ordered differently from the supernode-by-supernode form (updates from inside the range are
 // applied column by column instead of as one published block), i.e. results agree to rounding.
 #pragma once
-#include "kernels_kkt.hip.h"
+#include "dense_elim.hip.h"
+#include "device_utils.h"
+#include "kkt_records.h"   // FactorPlan, TopDenseArgs, kTop*
+#include "kkt_stamps.hip.h"
 
 namespace cxk {
-
-constexpr int kTopMaxSn = 16;
-constexpr int kTopMaxCols = 64;
-
-constexpr int kTopMaxImage = 4096;  // doubles: panels of the top, and (aliased) their update slots / the dense matrix
-constexpr int kTopRhsSrc = 8;       // external forward-solve sources per top row (fixed width)
-
-struct TopDenseArgs {
-  int nt, T;                         // supernodes, total columns
-  int ns[kTopMaxSn], nsep[kTopMaxSn], start[kTopMaxSn], row0[kTopMaxSn], base[kTopMaxSn];
-  long long diag_off[kTopMaxSn], offd_off[kTopMaxSn];
-  // consumer-ordered update slots of supernode k: target t (panel position tg_loc[tg_beg + t])
-  // reads upd[ubase + t * m + i], i < m.  Slots fed by supernodes INSIDE the top are never written
-  // while this kernel does the top (they stay 0.0 and subtract exactly).
-  int ubase[kTopMaxSn], m[kTopMaxSn], tg_beg[kTopMaxSn], ntg[kTopMaxSn], ubase_lds[kTopMaxSn], tg_lds[kTopMaxSn];
-  const int* top_off;                // [T*T]: image offset of L(r, j), j <= r, or -1
-  const int* rhs_src;                // [T * kTopRhsSrc]: updb slots from below the top feeding row r (padded
-                                     // with a slot that is always 0.0)
-};
 
 struct ElimNoSink {
   __device__ __forceinline__ void operator()(int, double) const {}

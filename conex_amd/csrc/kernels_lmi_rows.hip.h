@@ -16,8 +16,8 @@
 // the elimination order differs from an LU + triangular solves, so W agrees with the oracle to
 // rounding (tests/test_gpu_parity.py, <= 1e-11).
 #pragma once
+#include "dense_elim.hip.h"  // DppOperandFence
 #include "kernels_cone.hip.h"
-#include "kernels_kkt.hip.h"
 #include "kernels_lmi.hip.h"
 
 namespace cxk {

@@ -1,5 +1,5 @@
 // Block triangular solves with the stored supernodal factor for a BLOCK of right-hand sides
-// (cxk_solve_block): the level-scheduled forward and back substitution of kernels_kkt.hip.h with
+// (cxk_solve_block): the level-scheduled forward and back substitution of kernels_tree_level.hip.h with
 // kSbW columns per workgroup instead of one.
 //
 // Layout.  The right-hand sides live in a buffer of this feature's own, permuted and cut into chunks
@@ -21,7 +21,7 @@
 // (clamped) pivots on the diagonal; the off block holds D^-1 L^-1 P off.  Forward: transpositions, unit-lower
 // solve, publish, then D^-1.  Backward: separator terms, unit-lower-transposed solve, transpositions reversed.
 #pragma once
-#include "kernels_kkt.hip.h"
+#include "tree_supernode.hip.h"
 
 namespace cxk {
 

@@ -2,7 +2,6 @@
 // every cone type, the choosers that name the LMI kernel of each stage, the per-group stages of cxk_finalize
 // and the host mailbox.  Owns the kernels of kernels_cone / _oct / _quad / _lmi* (and mailbox_pack,
 // newton_from_three below).
-#define CXK_DEVICE_FUNCTIONS_ONLY  // kernels_kkt.hip.h: types and templates only (its plain kernels live in kkt_tree_launch.hip)
 #include <hip/hip_ext.h>
 #include "kkt_launch.h"
 #include "kernels_cone.hip.h"

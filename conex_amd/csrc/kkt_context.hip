@@ -3,7 +3,6 @@
 // Host side = structure + launches only.  All fp64 state (A_i, C, W, Schur blocks, the
 // supernodal slab, right-hand sides) lives in HBM for the lifetime of the context; per
 // Newton step only scalars cross PCIe.
-#define CXK_DEVICE_FUNCTIONS_ONLY  // no kernel is compiled or launched here (kkt_launch.h)
 #include "kkt_launch.h"
 #include "kernels_gemm.hip.h"  // GemmArgs, LaunchGemmSplitK (cxk_gemm_f64)
 

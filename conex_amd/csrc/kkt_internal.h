@@ -22,8 +22,7 @@
 #include <vector>
 
 #include "../../include/conex_kkt_hip.h"
-#include "kernels_kkt.hip.h"      // record types, FactorPlan (every unit but kkt_tree_launch.hip defines CXK_DEVICE_FUNCTIONS_ONLY first)
-#include "kernels_kkt_top.hip.h"  // TopDenseArgs
+#include "kkt_records.h"  // record and argument types, FactorPlan, TopDenseArgs: no device code
 #include "lmi_types.h"
 #include "symbolic.h"
 #include "tree_fused.h"

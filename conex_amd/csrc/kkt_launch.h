@@ -6,7 +6,6 @@
 //   kkt_qr.hip           the host QR mode
 //   kkt_solve_block.hip  the block of right-hand sides on the stored factor (cxk_solve_block) and its kernels
 //   kkt_context.hip      everything else of the C-ABI (no kernel launch of its own)
-// Every unit but kkt_tree_launch.hip defines CXK_DEVICE_FUNCTIONS_ONLY before including this.
 #pragma once
 #include "kkt_internal.h"
 

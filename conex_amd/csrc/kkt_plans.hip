@@ -2,7 +2,6 @@
 // partition of a sharded context, then every index table the kernels read -- gather lists, pull
 // lists in consumer order, level segments, the chain at the top, paired downward levels, the
 // records of the whole-tree launch, the dense top.  Host code only.
-#define CXK_DEVICE_FUNCTIONS_ONLY  // kernels_kkt.hip.h: types and templates only (the plain kernels live in kkt_tree_launch.hip)
 #include "kkt_internal.h"
 #include "big_chol.h"
 

@@ -1,5 +1,4 @@
 // kkt_solver = CONEX_QR_FACTORIZATION: the dense KKT matrix factored and solved on the host (host code only).
-#define CXK_DEVICE_FUNCTIONS_ONLY  // kernels_kkt.hip.h: types and templates only
 #include "kkt_launch.h"
 
 namespace cxk_host {

@@ -1,7 +1,6 @@
 // Sharded contexts (world > 1): the collectives, the sweeps around the exchange of the replicated top, what a
 // time-out of a whole-tree launch means across ranks, the RCCL communicator and the exchange entry points.
 // Owns comm_selftest_fill; the exchange kernels are kkt_tree_launch.hip's (LaunchExchange).
-#define CXK_DEVICE_FUNCTIONS_ONLY  // kernels_kkt.hip.h: types and templates only
 #include "kkt_launch.h"
 
 namespace cxk_host {

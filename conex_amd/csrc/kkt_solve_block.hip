@@ -1,7 +1,6 @@
 // cxk_solve_block / cxk_solve_block_device: Y <- K^-1 Y for a block of right-hand sides with the stored
 // factor (kernels_solve_block.hip.h).  One gather launch, one launch per level up, one per level down, one
 // scatter launch; the work buffers belong to this feature and grow with the widest block seen.
-#define CXK_DEVICE_FUNCTIONS_ONLY  // (the plain kernels of kernels_kkt.hip.h live in kkt_tree_launch.hip)
 #include "kkt_launch.h"
 #include "kernels_solve_block.hip.h"
 

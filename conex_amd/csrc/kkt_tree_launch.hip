@@ -1,10 +1,13 @@
 // The launches of the elimination tree: assembly gather, right-hand sides, level / range / chain / dense-top
 // sweeps, the whole-tree launch with its time-out handling, iterative refinement, the step scalars and the
-// exchange kernels of sharded contexts.  Owns the plain kernels of kernels_kkt.hip.h and the instances of
-// its templates, kernels_kkt_big and kernels_kkt_top (and copy_doubles below).
+// exchange kernels of sharded contexts.  Owns the plain kernels of kernels_kkt_vec.hip.h and the instances
+// of the templates of kernels_tree_level.hip.h, kernels_kkt_big and kernels_kkt_top (and copy_doubles below).
 #include "kkt_launch.h"
 #include "kernels_gemm.hip.h"
 #include "kernels_kkt_big.hip.h"
+#include "kernels_kkt_top.hip.h"
+#include "kernels_kkt_vec.hip.h"    // its only includer: the plain kernels live in this unit
+#include "kernels_tree_level.hip.h"  // its only includer
 
 extern "C" {
 

@@ -1,6 +1,8 @@
 // Argument structs shared by the LMI kernel files and their host launchers (plain data, no
 // device code: safe to include from several translation units).
 #pragma once
+#include <hip/hip_runtime.h>
+
 #include <cstdint>
 
 namespace cxk {

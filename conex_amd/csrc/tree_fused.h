@@ -23,7 +23,7 @@ constexpr int kFusedExtraMax = 64;       // ... at most (longer lists: the level
 constexpr int kFusedMaxSlots = 4096;     // published values one entry / one row pulls, at most (taken kFastSlots at a time)
 
 // Words of a record (position = dependency order: a supernode only waits for lower positions):
-//   [0, 32)   SnRec (kernels_kkt.hip.h); its spare word 23: pub_beg
+//   [0, 32)   SnRec (kkt_records.h); its spare word 23: pub_beg
 //   [32, 56)  AsmRec: the Schur block of the supernode's own constraint and the position of every
 //             panel row in it.  A supernode of the replicated top of a sharded context (its panel
 //             comes from the exchange buffer): 32,33 xs_base, 34 xv_base -- where its slab entries
@@ -82,7 +82,7 @@ struct FusedTreeArgs {
   // ---- sharded contexts (kFusedShardUp / kFusedShardTop).  Positions [0, count_up) are
   // this rank's own subtrees, [count_up, count) the replicated top of the tree.  The exchange buffer
   // x = [T slab entries (n_xs) | AW_T | AQc_T | fwd_T (n_xv each) | <w,c> <c,Qc> fail pad] is what ONE
-  // sum all-reduce carries between the two launches (layout of exchange_pack, kernels_kkt.hip.h).
+  // sum all-reduce carries between the two launches (layout of exchange_pack, kernels_kkt_vec.hip.h).
   int count_up;
   double* x;
   long long n_xs;

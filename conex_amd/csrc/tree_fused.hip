@@ -6,7 +6,7 @@
 // (constraint_manager.h:107-124), BlockCholeskyInPlace (block_triangular_operations.cc:184-219),
 // ApplyBlockInverseInPlace / ...OfTransposeInPlace (:114-182), right-hand side cone_program.cc:409-411.
 //
-// Why one launch.  The level-by-level sweeps (kernels_kkt.hip.h) pay, per level of the tree, a
+// Why one launch.  The level-by-level sweeps (kernels_tree_level.hip.h) pay, per level of the tree, a
 // kernel boundary (~1.5 us), a record round trip and a data round trip before ~2 us of elimination
 // -- 46 us of dependency latency at BASELINE config 4 (5 levels up, 4 down) in which the chip is
 // nearly idle.  Here every supernode's wavefront is resident from the start: it fetches its
@@ -39,8 +39,7 @@
 
 #include <type_traits>
 
-#define CXK_DEVICE_FUNCTIONS_ONLY
-#include "kernels_kkt.hip.h"
+#include "tree_supernode.hip.h"
 #include "kernels_kkt_top.hip.h"  // ElimWide: the elimination over four mirrored DPP rows (33 .. 64 columns)
 #include "tree_fused.h"
 
@@ -96,7 +95,7 @@ __device__ __forceinline__ void ReportTimeout(const FusedTreeArgs& A) {
   }
 }
 
-// acc += w[lane J of the own 16-lane DPP row] * v (the multiply-add of DppColumns, kernels_kkt.hip.h; operands
+// acc += w[lane J of the own 16-lane DPP row] * v (the multiply-add of DppColumns, dense_elim.hip.h; operands
 // through DppOperandFence first)
 template <int J>
 __device__ __forceinline__ void FmacRowBcast(double& acc, double w, double v) {
@@ -1145,7 +1144,7 @@ __device__ __forceinline__ double WaitValue(const FusedTreeArgs& A, const double
   return v;
 }
 
-// exchange_pack (kernels_kkt.hip.h) riding in the up launch, one lane per buffer entry: the partial
+// exchange_pack (kernels_kkt_vec.hip.h) riding in the up launch, one lane per buffer entry: the partial
 // assembled value of a top entry -- own-rank sources in the gather's order, what assemble_gather
 // would have left in the slab -- minus the Schur updates this rank's subtrees publish into it (summed
 // in slot order, then subtracted); per top variable the partial AW / AQc and the sum of the

@@ -248,7 +248,7 @@ def test_a_singular_block_on_the_sharded_ldlt_path_is_settled_alike():
     """Equality constraints (the LQR program of test_sharded_equality_constraints_take_the_ldlt_path): one
     rank's part of the assembled matrix is zeroed, so its subtrees' pivots are all zero.  The block LDLT
     has no failing factorization: it clamps such pivots to +-1e-9 and reports success, as the reference's
-    RLDLT does (kernels_kkt.hip.h, tree_sweep_block_ldlt).  So what is checked is that every rank reports
+    RLDLT does (kernels_tree_level.hip.h, tree_sweep_block_ldlt).  So what is checked is that every rank reports
     the same outcome of the singular factorization, and that the next factorization of the real matrix
     solves like a float64 dense solve of the oracle's assembled matrix."""
     from test_oracle_kat import build_lqr_problem
