@@ -14,6 +14,7 @@
 #include "kernels_lmi_large.hip.h"
 #include "kernels_quad.hip.h"
 #include "kernels_soc_stream.hip.h"
+#include "kernels_linear_tiled.hip.h"
 
 namespace cxk_host {
 
@@ -89,6 +90,14 @@ SocStreamGroup MakeSocStream(Group& g) {
   d.ms = g.st_vec.p + 2 * per;
   d.dets = g.st_det.p;
   d.Gf = g.ws_gf.p;
+  return d;
+}
+LinTiledGroup MakeLinTiled(Group& g) {
+  LinTiledGroup d;
+  d.v = MakeVec(g);
+  d.WA = g.ws_main.p;
+  d.Gf = g.ws_gf.p;
+  d.part = g.lt_part.p;
   return d;
 }
 StaticGroup MakeStatic(Group& g) {
@@ -488,6 +497,40 @@ hipError_t LaunchSocStreamSchur(Group& g, const Arena& ar, hipStream_t st) {
   return hipGetLastError();
 }
 
+// The Schur complement of a group of linear blocks on the tiled route: scalars, apply, Gram (the batched GEMM as
+// LaunchSocStreamSchur sets it up, alpha = 1), mirror.  Stream order is the only dependency.
+hipError_t LaunchLinearTiledSchur(Group& g, const Arena& ar, hipStream_t st) {
+  const LinTiledGroup d = MakeLinTiled(g);
+  const int cnt = d.v.count, len = d.v.len, m = d.v.m;
+  linear_tiled_scalars<<<cnt, kLinTiledBlock, 0, st>>>(d, ar);
+  if (m == 0) return hipGetLastError();
+  linear_tiled_apply<<<(unsigned)((size_t)cnt * m), kLinTiledBlock, 0, st>>>(d, ar);
+  const int64_t mm = (int64_t)m * m;
+  constexpr int kMaxBatch = 65535;  // gridDim.z
+  for (int b0 = 0; b0 < cnt; b0 += kMaxBatch) {
+    const int nb = std::min(kMaxBatch, cnt - b0);
+    GemmArgs a{};
+    a.M = a.N = m;
+    a.K = len;
+    a.A = a.B = d.WA + (size_t)b0 * len * m;
+    a.lda = a.ldb = len;
+    a.sA1 = a.sB1 = (int64_t)len * m;
+    a.C = d.Gf + (size_t)b0 * mm;
+    a.ldc = m;
+    a.sC1 = mm;
+    a.inner = 1;
+    a.alpha = 1.0;
+    a.beta = 0.0;
+    a.lower_only = 1;
+    a.splits = g.splits;
+    a.sCs = (int64_t)std::min(cnt, kMaxBatch) * mm;
+    const hipError_t e = LaunchGemmSplitK(a, true, false, nb, g.ws_part.p, st);
+    if (e != hipSuccess) return e;
+  }
+  linear_tiled_mirror<<<GridFor((size_t)cnt * mm, kLinTiledBlock), kLinTiledBlock, 0, st>>>(d, ar);
+  return hipGetLastError();
+}
+
 // A hipEvent pair for this launch of a clock slot's kernels, when it is one of the sampled ones.
 bool ClockSample(cxk_context* ctx, int slot, hipEvent_t* e0, hipEvent_t* e1) {
   *e0 = *e1 = nullptr;
@@ -540,7 +583,15 @@ int LaunchSchur(cxk_context* ctx) {
         break;
       }
       case CXK_LINEAR:
-        linear_schur<<<count, 256, 0, ctx->stream>>>(MakeVec(g), ar);
+        if (g.tiled) {
+          hipEvent_t e0 = nullptr, e1 = nullptr;
+          const bool sample = ClockSample(ctx, CXK_CLOCK_ASSEMBLY, &e0, &e1);
+          if (sample) CXK_TRY(hipEventRecord(e0, ctx->stream));
+          CXK_TRY(LaunchLinearTiledSchur(g, ar, ctx->stream));
+          if (sample) CXK_TRY(hipEventRecord(e1, ctx->stream));
+        } else {
+          linear_schur<<<count, 256, 0, ctx->stream>>>(MakeVec(g), ar);
+        }
         break;
       case CXK_SOC:
       if (g.streamed) {
@@ -584,10 +635,30 @@ int GroupConstraints(cxk_context* ctx, const FinalizeSwitches& sw) {
   ctx->groups.clear();
   // second-order cones beyond LDS: refused, or held in HBM (cxk_set_streamed_cones, else CXK_STREAMED_CONES)
   const bool stream_on = ctx->streamed_cones >= 0 ? ctx->streamed_cones != 0 : sw.streamed_cones;
+  // linear blocks: the LDS route's one workgroup per block, or the tiled route (cxk_set_tiled_linear, else
+  // CXK_TILED_LINEAR, else by size)
+  const int tiled_mode = ctx->tiled_linear >= 0 ? ctx->tiled_linear : sw.tiled_linear;
   for (int i = 0; i < K; i++) {
     ConstraintRec& c = ctx->cons[i];
     c.streamed = false;
+    c.tiled = false;
     if (!ctx->owned[i]) continue;
+    if (c.type == CXK_LINEAR) {
+      c.tiled = tiled_mode >= 0 ? tiled_mode != 0
+                                : c.m > kLinearLdsMaxVars || (double)c.n * c.m * c.m >= (double)sw.tiled_linear_min_work;
+      if (c.tiled) {
+        // what remains is the int indexing of the kernels and of the GEMM
+        CXK_DEMAND((int64_t)c.n * std::max(c.m, 1) <= INT_MAX - 1024,
+                   "a tiled linear block whose rows x variables entries exceed the int range is not supported");
+        CXK_DEMAND((int64_t)c.m * c.m <= INT_MAX,
+                   "a tiled linear block whose variables x variables Schur block exceeds the int range is not supported");
+      } else {
+        // linear_line_search keeps two vectors of m doubles in 64 KB of dynamic LDS
+        CXK_DEMAND(c.m <= kLinearLdsMaxVars,
+                   "a linear block over more than 4096 variables does not fit the LDS route's kernels: it needs the tiled "
+                   "route (cxk_set_tiled_linear / CXK_TILED_LINEAR, which was set to 0)");
+      }
+    }
     if (c.type == CXK_LMI) {
       // sparse evaluation when it pays (CXK_SPARSE_LMI=0 / 1 forces never / always: tests)
       double nnz = 0;
@@ -631,7 +702,8 @@ int GroupConstraints(cxk_context* ctx, const FinalizeSwitches& sw) {
                  "a quadratic cone whose step kernels need more than the 163 328 B of LDS (variables + four vectors of "
                  "dimension + 1) is not supported");
     auto key = std::make_tuple(c.type, c.n, c.m, c.herm_d + (c.sparse ? 16 : 0) + (c.type == CXK_LMI && !c.symmetric ? 32 : 0) +
-                                                     (c.type == CXK_QUAD && !c.Q.empty() ? 64 : 0) + (c.streamed ? 128 : 0));
+                                                     (c.type == CXK_QUAD && !c.Q.empty() ? 64 : 0) + (c.streamed ? 128 : 0) +
+                                                     (c.tiled ? 256 : 0));
     auto it = gmap.find(key);
     if (it == gmap.end()) {
       it = gmap.emplace(key, (int)ctx->groups.size()).first;
@@ -644,6 +716,7 @@ int GroupConstraints(cxk_context* ctx, const FinalizeSwitches& sw) {
       ctx->groups.back().literal = c.type == CXK_LMI && !c.symmetric;
       ctx->groups.back().has_q = c.type == CXK_QUAD && !c.Q.empty();
       ctx->groups.back().streamed = c.streamed;
+      ctx->groups.back().tiled = c.tiled;
     }
     c.group = it->second;
     c.member = (int)ctx->groups[it->second].ids.size();
@@ -805,6 +878,17 @@ int UploadGroup(cxk_context* ctx, Group& g, const FinalizeSwitches& sw) {
     CXK_TRY(g.ws_gf.alloc(cnt * m * m));
     CXK_TRY(g.ws_part.alloc(g.splits > 1 ? (size_t)g.splits * std::min<size_t>(cnt, 65535) * m * m : 0));
   }
+  if (g.tiled) {
+    const size_t len = (size_t)g.n, m = (size_t)g.m, tiles = (len + kLinTiledRowTile - 1) / kLinTiledRowTile;
+    CXK_DEMAND(cnt * std::max(m, tiles) <= (size_t)INT_MAX,
+               "a group of tiled linear blocks with more than 2^31 columns or row tiles is not supported");
+    g.splits = SocStreamSplits((int)len, g.m, (long long)cnt);
+    if (sw.gram_splits > 0) g.splits = sw.gram_splits;  // (comparison runs)
+    CXK_TRY(g.ws_main.alloc(cnt * len * m));
+    CXK_TRY(g.ws_gf.alloc(cnt * m * m));
+    CXK_TRY(g.ws_part.alloc(g.splits > 1 ? (size_t)g.splits * std::min<size_t>(cnt, 65535) * m * m : 0));
+    CXK_TRY(g.lt_part.alloc(cnt * tiles * 4));
+  }
   if (g.schur_gemm) {
     const size_t nn = (size_t)g.n * g.n, m1 = (size_t)g.m + 1;
     // split-K of the contraction: enough workgroups to fill the chip, at most one K step each
@@ -851,7 +935,14 @@ int LaunchLinearLineSearch(cxk_context* ctx, double dinf_upper_bound, double c_s
   for (Group& g : ctx->groups) {
     const int cnt = (int)g.ids.size();
     if (cnt == 0 || g.type != CXK_LINEAR) continue;
-    linear_line_search<<<cnt, 256, sizeof(double) * 2 * g.m, ctx->stream>>>(MakeVec(g), a);
+    if (g.tiled) {
+      const LinTiledGroup d = MakeLinTiled(g);
+      const int tiles = (g.n + kLinTiledRowTile - 1) / kLinTiledRowTile;
+      linear_tiled_line_search<<<(unsigned)((size_t)cnt * tiles), kLinTiledBlock, 0, ctx->stream>>>(d, a, tiles);
+      linear_tiled_line_finish<<<cnt, kLinTiledBlock, 0, ctx->stream>>>(d, a, tiles);
+    } else {
+      linear_line_search<<<cnt, 256, sizeof(double) * 2 * g.m, ctx->stream>>>(MakeVec(g), a);
+    }
   }
   CXK_TRY(hipGetLastError());
   return CXK_SUCCESS;
@@ -1152,6 +1243,13 @@ int LaunchPrepareGroups(cxk_context* ctx, int pmode, const StepArgs& sa, const S
           lmi_prepare_generic<MODE, 0><<<cnt, 256, LmiPrepareLds(g.n, g.m), ctx->stream>>>(MakeLmi(g), sa);
           break;
       }
+    }
+    else if (g.type == CXK_LINEAR && g.tiled) {
+      const LinTiledGroup d = MakeLinTiled(g);
+      const int tiles = (g.n + kLinTiledRowTile - 1) / kLinTiledRowTile;
+      linear_tiled_slack<MODE><<<(unsigned)((size_t)cnt * tiles), kLinTiledBlock, 0, ctx->stream>>>(d, sa, tiles);
+      if (MODE == 1 || !sa.affine)  // (the affine update has no reduction)
+        linear_tiled_finish<MODE><<<cnt, kLinTiledBlock, 0, ctx->stream>>>(d, sa, tiles);
     }
     else if (g.type == CXK_LINEAR)
       linear_prepare<MODE><<<cnt, 256, sizeof(double) * g.m, ctx->stream>>>(MakeVec(g), sa);

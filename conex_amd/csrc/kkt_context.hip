@@ -101,6 +101,8 @@ static FinalizeSwitches ReadFinalizeSwitches() {
   if ((v = getenv("CXK_GRAM_SPLITS"))) sw.gram_splits = std::max(1, atoi(v));
   if ((v = getenv("CXK_STREAMED_CONES"))) sw.streamed_cones = atoi(v) != 0;
   if ((v = getenv("CXK_SOC_STREAM_STAGES"))) sw.soc_stream_stages = atoi(v);
+  if ((v = getenv("CXK_TILED_LINEAR")) && v[0] != '\0') sw.tiled_linear = atoi(v) != 0;
+  if ((v = getenv("CXK_TILED_LINEAR_MIN_WORK")) && v[0] != '\0') sw.tiled_linear_min_work = std::max(0ll, atoll(v));
   return sw;
 }
 
@@ -464,6 +466,20 @@ int cxk_count_streamed_cones(const cxk_context* ctx) {
   if (!ctx || !ctx->finalized) return -1;
   int k = 0;
   for (size_t i = 0; i < ctx->cons.size(); i++) k += ctx->owned[i] && ctx->cons[i].streamed;
+  return k;
+}
+
+int cxk_set_tiled_linear(cxk_context* ctx, int mode) {
+  if (!ctx) return CXK_FAILURE;
+  CXK_DEMAND(!ctx->finalized, "cxk_set_tiled_linear: the context is finalized (the choice is made by cxk_finalize)");
+  CXK_DEMAND(mode >= -1 && mode <= 1, "cxk_set_tiled_linear: the mode is -1 (automatic), 0 (never) or 1 (every linear block)");
+  ctx->tiled_linear = mode;
+  return CXK_SUCCESS;
+}
+int cxk_count_tiled_linear(const cxk_context* ctx) {
+  if (!ctx || !ctx->finalized) return -1;
+  int k = 0;
+  for (size_t i = 0; i < ctx->cons.size(); i++) k += ctx->owned[i] && ctx->cons[i].tiled;
   return k;
 }
 

@@ -44,6 +44,7 @@ struct ConstraintRec {
   // every A_i and C equals its transpose.  The fast kernels use tr(W A_i W A_j) = tr(P_i P_j),
   // P = A W, which needs that; anything else takes the literal kernels (dense_lmi_constraint.cc:72-88)
   bool symmetric = true;
+  bool tiled = false;  // linear block on the tiled route (kernels_linear_tiled.hip.h)
 };
 
 template <typename T>
@@ -119,6 +120,10 @@ struct Group {
   DevBuf<double> st_vec;   // s, Q(s) c, the slack: three vectors per cone
   DevBuf<double> st_det;   // det(s) per cone
   int st_stages = 0;       // CXK_SOC_STREAM_STAGES: 1 / 2 = the assembly stops after the vectors / the apply stage (timing runs)
+  // linear blocks on the tiled route (cxk_set_tiled_linear): the kernels of kernels_linear_tiled.hip.h; diag(w) A in
+  // ws_main, the Gram product's output in ws_gf, its split partials in ws_part, four doubles per row tile in lt_part
+  bool tiled = false;
+  DevBuf<double> lt_part;
 };
 
 
@@ -151,6 +156,7 @@ struct cxk_context {
   int chain_segments = -1;  // cxk_set_chain_segments: -1 automatic / environment, 0 off, P segments
   int segments = 0;         // segments in use (0: the reference's order)
   int streamed_cones = -1;  // cxk_set_streamed_cones: -1 the environment's CXK_STREAMED_CONES (else off), 0 off, 1 on
+  int tiled_linear = -1;    // cxk_set_tiled_linear: -1 the environment's CXK_TILED_LINEAR (else by size), 0 never, 1 every block
   std::vector<Group> groups;
   std::vector<int64_t> g_off, r_off;
   std::vector<unsigned char> owned;      // constraint i assembled/updated by this rank

@@ -54,6 +54,16 @@ CXK_LOCAL inline hipError_t RaiseDynamicLds(std::initializer_list<const void*> k
   return hipSuccess;
 }
 
+// The widest linear block the LDS route can run: linear_line_search is launched with 16 m bytes of dynamic LDS
+// and has the default limit of 64 KB (linear_prepare's 8 m bytes reach it at 8192).
+constexpr int kLinearLdsMaxVars = 4096;
+// Automatic mode sends a linear block of rows x m to the tiled route from rows m^2 >= this on.  Measured
+// (tools/linear_tiled_speed.py against the build before the tiled route): twice the smallest
+// rows m^2 among the measured shapes from which assembly, PrepareStep and the eigenvalue query are each faster on
+// the tiled route at that shape and at every larger one, 2000 x 64 (at 256 x 32 the assembly is five times faster
+// but the two-launch PrepareStep and query cost 2 us more); twice, because the numbers are one box's on one day.
+constexpr long long kTiledLinearMinWork = 2ll * 2000 * 64 * 64;  // 16 384 000
+
 // The environment switches of cxk_finalize, read once per call (FinalizeImpl).
 struct FinalizeSwitches {
   bool quirks_off = false;      // CXK_REFERENCE_QUIRKS=0: the two corrections instead of the reference as written
@@ -66,6 +76,8 @@ struct FinalizeSwitches {
   int gram_splits = 0;          // CXK_GRAM_SPLITS: K splits of the GEMM assembly (0: chosen by shape)
   bool streamed_cones = false;  // CXK_STREAMED_CONES=1: second-order cones beyond LDS run from HBM (cxk_set_streamed_cones)
   int soc_stream_stages = 0;    // CXK_SOC_STREAM_STAGES=1 / 2: their assembly stops after that stage (timing runs: wrong results)
+  int tiled_linear = -1;        // CXK_TILED_LINEAR=0 / 1: linear blocks never / always on the tiled route (cxk_set_tiled_linear)
+  long long tiled_linear_min_work = kTiledLinearMinWork;  // CXK_TILED_LINEAR_MIN_WORK (comparison runs)
 };
 
 // ---- kkt_context.hip

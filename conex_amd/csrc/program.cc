@@ -78,6 +78,7 @@ struct Program {
   int device = 0;
   int reference_identity = -1;  // -1: environment (CXK_REFERENCE_QUIRKS); see CONEX_HIP_SetReferenceIdentity
   int streamed_cones = 1;       // second-order cones beyond LDS run from HBM; see CONEX_HIP_SetStreamedCones
+  int tiled_linear = -1;        // linear blocks on the tiled kernels: -1 by size; see CONEX_HIP_SetTiledLinear
   // multi-GPU (one process per GPU, every rank builds the same program): see CONEX_HIP_SetCommunicator
   int shard_rank = 0, shard_world = 1;
   int debug_timeout_at = -1, debug_timeout_site = 0;  // CONEX_HIP_DebugFusedTimeoutAt (test hook)
@@ -148,6 +149,7 @@ int BuildContext(Program* p) {
   // the reference takes a second-order cone of any size (CONEX_NewLorentzConeConstraint makes every cone as wide
   // as the program): none is refused for its size here either
   cxk_set_streamed_cones(p->ctx, p->streamed_cones);
+  if (p->tiled_linear >= 0) cxk_set_tiled_linear(p->ctx, p->tiled_linear);
   if (p->shard_world > 1) {
     if (cxk_set_shard(p->ctx, p->shard_rank, p->shard_world)) return 1;
     if (p->allreduce_fn) {
@@ -1303,6 +1305,16 @@ int CONEX_HIP_SetStreamedCones(void* x, int on) {
   Program* p = static_cast<Program*>(x);
   if (!p) return CONEX_FAILURE;
   p->streamed_cones = on != 0;
+  p->dirty = true;
+  return CONEX_SUCCESS;
+}
+
+/* not part of conex.h: which linear-inequality blocks run on the tiled kernels (conex_kkt_hip.h,
+ * cxk_set_tiled_linear): -1 (the default) by size, 0 none, 1 every block */
+int CONEX_HIP_SetTiledLinear(void* x, int mode) {
+  Program* p = static_cast<Program*>(x);
+  if (!p || mode < -1 || mode > 1) return CONEX_FAILURE;
+  p->tiled_linear = mode;
   p->dirty = true;
   return CONEX_SUCCESS;
 }

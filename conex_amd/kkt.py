@@ -129,6 +129,8 @@ _SIGNATURES = {
     "cxk_chain_segments": (C.c_int, [C.c_void_p]),
     "cxk_set_streamed_cones": (C.c_int, [C.c_void_p, C.c_int]),
     "cxk_count_streamed_cones": (C.c_int, [C.c_void_p]),
+    "cxk_set_tiled_linear": (C.c_int, [C.c_void_p, C.c_int]),
+    "cxk_count_tiled_linear": (C.c_int, [C.c_void_p]),
     "cxk_fused_tree_timed_out": (C.c_int, [C.c_void_p]),
     "cxk_debug_force_fused_timeout": (C.c_int, [C.c_void_p]),
     "cxk_debug_fused_timeout_at": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
@@ -754,6 +756,15 @@ class KktContext:
     def count_streamed_cones(self):
         """Constraints this context owns that run on the streamed second-order cone kernels."""
         return self.L.cxk_count_streamed_cones(self.h)
+
+    def set_tiled_linear(self, mode=1):
+        """Linear blocks on the tiled kernels: 1 every block, 0 none (a block over more than 4096 variables is then
+        refused at initialize), -1 by size (before initialize; default: CXK_TILED_LINEAR in the environment, else -1)."""
+        self._check(self.L.cxk_set_tiled_linear(self.h, int(mode)), "cxk_set_tiled_linear")
+
+    def count_tiled_linear(self):
+        """Constraints this context owns that run on the tiled linear kernels."""
+        return self.L.cxk_count_tiled_linear(self.h)
 
     def fused_tree_timed_out(self):
         return bool(self.L.cxk_fused_tree_timed_out(self.h))

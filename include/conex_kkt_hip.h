@@ -137,6 +137,22 @@ int cxk_set_reference_identity(cxk_context* ctx, int on);
 int cxk_set_streamed_cones(cxk_context* ctx, int on);
 int cxk_count_streamed_cones(const cxk_context* ctx);
 
+/* Large linear-inequality blocks.  The LDS route (linear_schur, linear_prepare, linear_line_search) gives a
+ * block one workgroup; the tiled route (kernels_linear_tiled.hip.h) spreads it over the chip: columns and row
+ * tiles of 256 rows on their own workgroups, G = (diag(w) A)^T (diag(w) A) on the batched fp64 MFMA GEMM.
+ * Before cxk_finalize, mode = 1: every linear block takes the tiled route; 0: none does, and a block over more
+ * than 4096 variables -- which the LDS route's line search cannot launch -- is refused at cxk_finalize;
+ * -1 (the default without a call: the environment's CXK_TILED_LINEAR = 0 | 1, else this): a block takes the
+ * tiled route when it has more than 4096 variables or rows x variables^2 reaches the measured threshold
+ * (kTiledLinearMinWork; CXK_TILED_LINEAR_MIN_WORK moves it for comparison runs).  Blocks on the LDS route keep
+ * their kernels and their bits.  Every output, getter and setter of a tiled block is that of any linear block.
+ * Refused on the tiled route at cxk_finalize, by name: rows x variables or variables^2 beyond the int range; a
+ * group of equal blocks with more than 2^31 columns or row tiles.
+ * cxk_count_tiled_linear: constraints this context owns that run on the tiled route (-1 before cxk_finalize;
+ * 0 on a host-only context, which chooses no kernels). */
+int cxk_set_tiled_linear(cxk_context* ctx, int mode);
+int cxk_count_tiled_linear(const cxk_context* ctx);
+
 /* Initialize(): symbolic analysis (SupernodalKKTSolver ctor kkt_solver.cc:104-116),
  * Bind (kkt_solver.h:26-33), workspace carve + SetIdentity (cone_program.cc:78-112),
  * upload of constant data, construction of device index tables and level schedule.
