@@ -1201,6 +1201,13 @@ int cxk_fused_assembly(const cxk_context* ctx) { return ctx && ctx->fused_asm ? 
 /* 1 when assembly, factorization and solve of a KKT solve run as one launch (tree_fused.hip) */
 int cxk_fused_tree(const cxk_context* ctx) { return ctx && ctx->fused_tree ? 1 : 0; }
 
+int cxk_fused_tree_frames(const cxk_context* ctx, int* frame_a, int* frame_b) {
+  if (!ctx || !frame_a || !frame_b) return CXK_FAILURE;
+  *frame_a = ctx->fused_tree ? ctx->fused_sa : 0;
+  *frame_b = ctx->fused_tree ? ctx->fused_sb : 0;
+  return CXK_SUCCESS;
+}
+
 int cxk_fused_tree_timed_out(cxk_context* ctx) {
   if (!ctx || !ctx->timeout_unreported) return 0;
   ctx->timeout_unreported = false;

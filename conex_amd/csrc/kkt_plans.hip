@@ -164,6 +164,7 @@ struct PlanSwitches {
   bool no_fused_wide = getenv("CXK_NO_FUSED_WIDE") != nullptr;
   bool fused_split = getenv("CXK_FUSED_SPLIT") != nullptr;
   bool fused_level_order = getenv("CXK_FUSED_LEVEL_ORDER") != nullptr;
+  bool fused_padded_frames = getenv("CXK_FUSED_PADDED_FRAMES") != nullptr;
   bool no_fused_sweep = getenv("CXK_NO_FUSED_SWEEP") != nullptr;
   bool no_top_dense = getenv("CXK_NO_TOP_DENSE") != nullptr;
 };
@@ -1012,6 +1013,40 @@ struct FusedTables {
   std::vector<long long> xsrc, rsrc;
 };
 
+// The frames of RegisterShape are padded for most trees (config 4: 15 + 5 in <16, 8>, its root's 20 columns in
+// <24, 0>), and every padding column is a multiply-add per pivot, every padding pivot a step of the root's back
+// substitution.  Per frame of the pair: the tightest compiled frame (kFusedFrames) that holds every supernode the
+// launch sends there -- <NA, SA> takes what fits it, <NB, SB> the rest -- with the same rows per lane (the same NSMAX
+// wherever a supernode has separator rows: the image locations tg_reg / xreg count from it).  The pair is taken
+// only when an instance exists for it; padding contributes exact zeros and unit pivots, so the results are the
+// same bits in either pair (CXK_FUSED_PADDED_FRAMES=1 keeps the padded one).
+void TightFrames(const cxk_context* ctx, int* sa, int* sb) {
+  const int pa = *sa, pb = *sb;
+  int mn[2] = {0, 0}, ms[2] = {0, 0};
+  for (int e : ctx->level_sn) {
+    const int n = ctx->t_ns[e], s = ctx->t_nsep[e];
+    const int g = (pa == pb || (n <= (pa >> 8) && s <= (pa & 255))) ? 0 : 1;
+    mn[g] = std::max(mn[g], n);
+    ms[g] = std::max(ms[g], s);
+  }
+  int tight[2] = {pa, pb};
+  for (int g = 0; g < 2; g++) {
+    const int padded = g == 0 ? pa : pb;
+    for (int f : kFusedFrames)
+      if (mn[g] <= (f >> 8) && ms[g] <= (f & 255) && (f >> 8) <= (padded >> 8) && (f & 255) <= (padded & 255) &&
+          (ms[g] == 0 || (f >> 8) == (padded >> 8))) {
+        tight[g] = f;
+        break;
+      }
+  }
+  if (pa == pb) tight[1] = tight[0];
+  // (a supernode of the second frame must not fit the first: it did not fit the padded one, which holds the tight one)
+  if (tight[0] <= tight[1] && FusedTreeCompiled(tight[0], tight[1])) {
+    *sa = tight[0];
+    *sb = tight[1];
+  }
+}
+
 // The pair of register shapes the launch runs on (*sa <= *sb); returns whether the program is ONE
 // dense supernode of 33 .. 64 columns (BASELINE config 2: 50): the wide instances of the same
 // launch (tree_fused.hip, ElimWide)
@@ -1056,6 +1091,7 @@ bool FusedTreeShapes(const cxk_context* ctx, const PlanSwitches& sw, const Updat
   if (v.ok) {
     *sa = shapes[0];
     *sb = shapes.back();
+    if (!sw.fused_padded_frames && ctx->world <= 1) TightFrames(ctx, sa, sb);  // (sharded contexts keep the padded pair)
   }
   return false;
 }

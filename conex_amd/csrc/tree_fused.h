@@ -109,8 +109,11 @@ struct FusedTreeArgs {
 
 // The lane that takes the first right-hand side as a ROW of the panel in tree_fused's elimination (the next
 // ones follow it), or -1: shapes whose column updates reach a free lane -- <16, 8>: separator rows end at lane
-// 23, the updates cover DPP row 1; <24, 0>: rows end at lane 23, the updates cover DPP rows 0 and 1.
-constexpr int FusedRhsLane(int nsmax, int smax) { return (nsmax == 16 && smax == 8) || (nsmax == 24 && smax == 0) ? 24 : -1; }
+// 23, the updates cover DPP row 1; <24, 0>: rows end at lane 23, the updates cover DPP rows 0 and 1; their exact-fit
+// forms <16, 5> and <20, 0> end at lanes 20 and 19.
+constexpr int FusedRhsLane(int nsmax, int smax) {
+  return (nsmax == 16 && (smax == 8 || smax == 5)) || ((nsmax == 24 || nsmax == 20) && smax == 0) ? 24 : -1;
+}
 
 // What a launch does.  A tree whose supernodes are all resident at once takes kFusedFull (assembly,
 // factorization with the first right-hand side, back substitution) and kFusedSolve (forward + back
@@ -132,6 +135,8 @@ enum FusedTreeMode { kFusedFull = 0, kFusedSolve = 1, kFusedUp = 2, kFusedForwar
 // Register shapes (NSMAX << 8 | SMAX) of the tree's supernodes: at most two (shape_b == shape_a for
 // one).  False when no instance is compiled for the pair.
 bool FusedTreeCompiled(int shape_a, int shape_b);
+// The frames (NSMAX << 8 | SMAX) instances exist for, tightest first within one NSMAX: what BuildPlans picks from.
+constexpr int kFusedFrames[] = {8 << 8 | 8, 16 << 8 | 5, 16 << 8 | 8, 20 << 8 | 0, 24 << 8 | 0, 24 << 8 | 8, 32 << 8 | 16};
 // Workgroups per CU the hardware can hold of the instance (0 on error); sharded: of kFusedShardTop.
 int FusedTreeOccupancy(int shape_a, int shape_b, bool sharded = false);
 // ev_start / ev_stop (both or neither): a hipEvent pair carried by the dispatch itself (its begin / end time stamps)

@@ -729,14 +729,17 @@ __device__ __forceinline__ void FusedSupernode(const FusedTreeArgs& A, const int
   }
   {
     const double dinv = 1.0 / dg;
+    // (the root runs this sweep on the tree's critical path: each lane == k is compared at its step -- through
+    // OpaqueLane, or the masks are those of the load phase, kept in SGPRs that spill, two v_readlane per step)
+    const int lzb = OpaqueLane(lane);
 #pragma unroll
     for (int k = NSMAX - 1; k >= 0; k--) {
-      if (lane == k) ub *= dinv;
+      if (lzb == k) ub *= dinv;
       ub = fma(-col[k], ReadLane(ub, k), ub);  // col[k] is zero for lanes >= k
       if constexpr (NRHS > 1) {
 #pragma unroll
         for (int q = 0; q < NRHS - 1; q++) {
-          if (lane == k) ubx[q] *= dinv;
+          if (lzb == k) ubx[q] *= dinv;
           ubx[q] = fma(-col[k], ReadLane(ubx[q], k), ubx[q]);
         }
       }
@@ -744,7 +747,7 @@ __device__ __forceinline__ void FusedSupernode(const FusedTreeArgs& A, const int
         if (cnt > 0) {
 #pragma unroll
           for (int qq = 0; qq < QN; qq++) {
-            if (lane == k) Mb[qq] *= dinv;
+            if (lzb == k) Mb[qq] *= dinv;
             Mb[qq] = fma(-col[k], ReadLane(Mb[qq], k), Mb[qq]);
           }
         }
@@ -1106,6 +1109,11 @@ __device__ __forceinline__ void FusedScalars(const FusedTreeArgs& A) {
   }
 }
 
+// Which of a launch's two frames a supernode runs in: <NA, SA> when it fits, <NB, SB> otherwise (BuildPlans orders
+// the pair: no supernode it sends to <NB, SB> fits <NA, SA>; for the frames of RegisterShape this is its choice).
+template <int NA, int SA>
+__device__ __forceinline__ bool FitsFrame(int ns, int s) { return ns <= NA && s <= SA; }
+
 // MODE 0: the whole sweep (assembly + factor + solve); 1: its upward half only (two launches: trees
 // too large to be resident at once); 2: the whole sweep with three right-hand sides (kFusedTriple)
 template <int NA, int SA, int NB, int SB, int MODE>
@@ -1121,7 +1129,7 @@ __global__ void __launch_bounds__(64, 2) tree_fused(FusedTreeArgs A) {
   constexpr int NRHS = MODE == 2 ? 3 : 1;
   if (NA == NB && SA == SB) {
     FusedSupernode<NA, SA, MODE == 1, false, NRHS>(A, w, lds);
-  } else if (RegisterShape(ns, s) == (NA << 8 | SA)) {
+  } else if (FitsFrame<NA, SA>(ns, s)) {
     FusedSupernode<NA, SA, MODE == 1, false, NRHS>(A, w, lds);
   } else {
     FusedSupernode<NB, SB, MODE == 1, false, NRHS>(A, w, lds);
@@ -1236,7 +1244,7 @@ __global__ void __launch_bounds__(64) tree_fused_shard_up(FusedTreeArgs A) {
     const int ns = __builtin_amdgcn_readlane(w, 1), s = __builtin_amdgcn_readlane(w, 2);
     if (NA == NB && SA == SB) {
       FusedSupernode<NA, SA, true>(A, w, lds);
-    } else if (RegisterShape(ns, s) == (NA << 8 | SA)) {
+    } else if (FitsFrame<NA, SA>(ns, s)) {
       FusedSupernode<NA, SA, true>(A, w, lds);
     } else {
       FusedSupernode<NB, SB, true>(A, w, lds);
@@ -1279,7 +1287,7 @@ __global__ void __launch_bounds__(64) tree_fused_shard_top(FusedTreeArgs A) {
   const int pos = b < ntop ? A.count_up + b : A.count - 1 - b;
   const int w = A.rec[(size_t)pos * kFusedRecWords + (threadIdx.x & 63)];
   const int ns = __builtin_amdgcn_readlane(w, 1), s = __builtin_amdgcn_readlane(w, 2);
-  const bool isA = (NA == NB && SA == SB) || RegisterShape(ns, s) == (NA << 8 | SA);
+  const bool isA = (NA == NB && SA == SB) || FitsFrame<NA, SA>(ns, s);
   if (b < ntop) {
     if (isA)
       FusedSupernode<NA, SA, false, true>(A, w, lds);
@@ -1302,7 +1310,7 @@ __global__ void __launch_bounds__(64) tree_fused_solve(FusedTreeArgs A) {
   const int ns = __builtin_amdgcn_readlane(w, 1), s = __builtin_amdgcn_readlane(w, 2);
   if (NA == NB && SA == SB) {
     FusedSolveSupernode<NA, SA, PHASE>(A, w);
-  } else if (RegisterShape(ns, s) == (NA << 8 | SA)) {
+  } else if (FitsFrame<NA, SA>(ns, s)) {
     FusedSolveSupernode<NA, SA, PHASE>(A, w);
   } else {
     FusedSolveSupernode<NB, SB, PHASE>(A, w);
@@ -1318,7 +1326,7 @@ struct FusedKernels {
   int image;         // doubles of LDS of the factor sweeps
 };
 
-template <int NA, int SA, int NB, int SB>
+template <int NA, int SA, int NB, int SB, bool SHARDED = true>
 FusedKernels KernelsOf() {
   FusedKernels f;
   f.k[kFusedFull] = reinterpret_cast<const void*>(&tree_fused<NA, SA, NB, SB, 0>);
@@ -1330,7 +1338,7 @@ FusedKernels KernelsOf() {
   f.k[kFusedShardTop] = nullptr;
   f.k[kFusedTriple] = nullptr;
   if constexpr (NA <= 32 && NB <= 32) f.k[kFusedTriple] = reinterpret_cast<const void*>(&tree_fused<NA, SA, NB, SB, 2>);
-  if constexpr (NA <= 32 && NB <= 32) {  // (the wide single-supernode instances are single-GPU)
+  if constexpr (SHARDED && NA <= 32 && NB <= 32) {  // (the wide single-supernode instances are single-GPU)
     f.k[kFusedShardUp] = reinterpret_cast<const void*>(&tree_fused_shard_up<NA, SA, NB, SB>);
     f.k[kFusedShardTop] = reinterpret_cast<const void*>(&tree_fused_shard_top<NA, SA, NB, SB>);
   }
@@ -1354,6 +1362,12 @@ bool ForPair(int sa, int sb, FusedKernels* out) {
   CXK_FUSED_PAIR(8, 8, 24, 8)
   CXK_FUSED_PAIR(8, 8, 32, 16)
   CXK_FUSED_PAIR(16, 8, 24, 0)
+  // (the exact fit of 15 + 5 under a root of 20: BuildPlans, TightFrames; sharded contexts keep the padded pair, so
+  // the two sharded kernels are not instantiated for it)
+  if (sa == (16 << 8 | 5) && sb == (20 << 8 | 0)) {
+    if (out) *out = KernelsOf<16, 5, 20, 0, false>();
+    return true;
+  }
   CXK_FUSED_PAIR(16, 8, 24, 8)
   CXK_FUSED_PAIR(16, 8, 32, 16)
   CXK_FUSED_PAIR(24, 0, 24, 8)

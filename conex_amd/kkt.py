@@ -701,6 +701,14 @@ class KktContext:
         """True when a KKT solve runs as one launch over the whole elimination tree (cxk_fused_tree)."""
         return bool(self.L.cxk_fused_tree(self.h))
 
+    def fused_tree_frames(self):
+        """((NSMAX, SMAX), (NSMAX, SMAX)): the pair of register frames of the whole-tree launch (cxk_fused_tree_frames)."""
+        fn = self.L.cxk_fused_tree_frames
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        a, b = C.c_int(0), C.c_int(0)
+        self._check(fn(self.h, C.byref(a), C.byref(b)), "cxk_fused_tree_frames")
+        return (a.value >> 8, a.value & 255), (b.value >> 8, b.value & 255)
+
     def count_lmi_kernel(self, which):
         """Constraints whose Schur block comes from kernel `which` (cxk_count_lmi_kernel): 0 literal,
         1 DPP + MFMA rows, 2 persistent MFMA, 3 GEMM pipeline, 4 sparse."""

@@ -459,6 +459,10 @@ int cxk_fused_assembly(const cxk_context* ctx);
 /* 1 when a KKT solve (assembly gather + factorization + solve) runs as ONE launch over the whole
  * elimination tree (tree_fused.hip); CXK_NO_FUSED_TREE=1 in the environment turns it off */
 int cxk_fused_tree(const cxk_context* ctx);
+/* The pair of register frames (NSMAX << 8 | SMAX each, *frame_a <= *frame_b) the whole-tree launch runs its supernodes
+ * in; zeros when cxk_fused_tree is 0.  cxk_finalize picks the tightest compiled pair that holds every supernode;
+ * CXK_FUSED_PADDED_FRAMES=1 in the environment keeps the frames of the level kernels (speed only: same bits). */
+int cxk_fused_tree_frames(const cxk_context* ctx, int* frame_a, int* frame_b);
 /* The whole-tree launch keeps every supernode's wavefront resident and lets it wait, inside the
  * kernel, for its descendants' values: deadlock-free while the launch has the device to itself
  * (grid <= resident slots, workgroups dispatched in index order), every wait bounded.  On a device
