@@ -15,6 +15,7 @@
 #include "kernels_quad.hip.h"
 #include "kernels_soc_stream.hip.h"
 #include "kernels_linear_tiled.hip.h"
+#include "kernels_quad_stream.hip.h"
 
 namespace cxk_host {
 
@@ -91,6 +92,42 @@ SocStreamGroup MakeSocStream(Group& g) {
   d.dets = g.st_det.p;
   d.Gf = g.ws_gf.p;
   return d;
+}
+QuadStreamGroup MakeQuadStream(Group& g) {
+  QuadStreamGroup d;
+  const size_t cnt = g.ids.size(), n = (size_t)g.n, m = (size_t)g.m;
+  d.n = g.n;
+  d.m = g.m;
+  d.count = static_cast<int>(cnt);
+  d.splits = g.splits;
+  d.A = g.A.p;
+  d.c = g.C.p;
+  d.Q = g.has_q ? g.qQ.p : nullptr;
+  d.Agram = g.qGram.p;
+  d.W = g.W.p;
+  d.D = g.T1.p;
+  d.S = g.qS.p;
+  d.ids = g.dids.p;
+  d.part = g.ws_part.p;
+  double* p = g.st_vec.p;  // (the layout UploadGroup sizes: QuadStreamVecDoubles)
+  d.qc1 = p;
+  d.qw = (p += cnt * n);
+  d.dv = (p += cnt * n);
+  d.qd = (p += cnt * n);
+  d.ms = (p += cnt * n);
+  d.v = (p += cnt * (n + 1));
+  d.u = (p += cnt * m);
+  d.scal = (p += cnt * m);
+  d.cqc = (p += cnt * 8);
+  return d;
+}
+size_t QuadStreamVecDoubles(size_t cnt, size_t n, size_t m) { return cnt * (4 * n + (n + 1) + 2 * m + 8 + 1); }
+// soc_stream_slack serves the streamed quadratic cone as it is (same layout, same formula): what it reads of the group.
+SocStreamGroup QuadStreamSlackView(Group& g, const QuadStreamGroup& d) {
+  SocStreamGroup s{};
+  s.v = MakeVec(g);
+  s.ms = d.ms;
+  return s;
 }
 LinTiledGroup MakeLinTiled(Group& g) {
   LinTiledGroup d;
@@ -531,6 +568,88 @@ hipError_t LaunchLinearTiledSchur(Group& g, const Arena& ar, hipStream_t st) {
   return hipGetLastError();
 }
 
+// One pass over Q of a group of streamed quadratic cones: out_r = Q x_r for the R vectors of `x` (partials per
+// column split; QuadStreamQx adds them).  Nothing to do where Q is the identity.
+template <int R>
+hipError_t LaunchQuadStreamQmv(const QuadStreamGroup& d, const QuadStreamVecs& x, hipStream_t st) {
+  if (!d.Q) return hipSuccess;
+  const int tiles = (d.n + kQuadStreamRowTile - 1) / kQuadStreamRowTile;
+  quad_stream_qmv<R><<<(unsigned)((size_t)d.count * tiles * d.splits), kQuadStreamBlock, 0, st>>>(d, x, tiles);
+  return hipGetLastError();
+}
+QuadStreamVecs QuadStreamOne(const double* p, size_t stride) {
+  QuadStreamVecs x;
+  x.p[0] = x.p[1] = p;
+  x.stride[0] = x.stride[1] = stride;
+  return x;
+}
+
+// The Schur complement of a group of streamed quadratic cones: Q w1, the scalars, the columns, the block.
+hipError_t LaunchQuadStreamSchur(Group& g, const Arena& ar, hipStream_t st) {
+  const QuadStreamGroup d = MakeQuadStream(g);
+  const int cnt = d.count, m = d.m;
+  hipError_t e = LaunchQuadStreamQmv<1>(d, QuadStreamOne(d.W + 1, (size_t)d.n + 1), st);
+  if (e != hipSuccess) return e;
+  quad_stream_schur_vectors<<<cnt, kQuadStreamBlock, 0, st>>>(d);
+  if (m > 0) quad_stream_schur_columns<<<(unsigned)((size_t)cnt * m), kQuadStreamBlock, 0, st>>>(d);
+  const int blocks = (int)std::max<size_t>(1, ((size_t)m * m + kQuadStreamBlock - 1) / kQuadStreamBlock);
+  quad_stream_schur_finish<<<(unsigned)((size_t)cnt * blocks), kQuadStreamBlock, 0, st>>>(d, ar, blocks);
+  return hipGetLastError();
+}
+
+// The constants of a group of streamed quadratic cones, once at cxk_finalize, on the device: Qc1 = Q c1 and
+// c1' Q c1 by the pass kernel, A_gram = A1' (Q A1) as two batched GEMMs (A1 = A + 1 with leading dimension
+// n + 1; T = Q A1 in a buffer that lives for this call only).
+int QuadStreamConstants(cxk_context* ctx, Group& g) {
+  const QuadStreamGroup d = MakeQuadStream(g);
+  const int cnt = d.count, n = d.n, m = d.m, len = n + 1;
+  CXK_TRY(LaunchQuadStreamQmv<1>(d, QuadStreamOne(d.c + 1, (size_t)len), ctx->stream));
+  quad_stream_constants<<<cnt, kQuadStreamBlock, 0, ctx->stream>>>(d);
+  CXK_TRY(hipGetLastError());
+  DevBuf<double> T;
+  if (g.has_q && m > 0) CXK_TRY(T.alloc((size_t)cnt * n * m));
+  constexpr int kMaxBatch = 65535;  // gridDim.z
+  for (int b0 = 0; b0 < cnt && m > 0; b0 += kMaxBatch) {
+    const int nb = std::min(kMaxBatch, cnt - b0);
+    const double* A1 = g.A.p + (size_t)b0 * len * m + 1;
+    GemmArgs a{};
+    a.inner = 1;
+    a.alpha = 1.0;
+    a.beta = 0.0;
+    a.splits = 1;
+    if (g.has_q) {  // T = Q A1
+      a.M = n;
+      a.N = m;
+      a.K = n;
+      a.A = g.qQ.p + (size_t)b0 * n * n;
+      a.lda = n;
+      a.sA1 = (int64_t)n * n;
+      a.B = A1;
+      a.ldb = len;
+      a.sB1 = (int64_t)len * m;
+      a.C = T.p + (size_t)b0 * n * m;
+      a.ldc = n;
+      a.sC1 = (int64_t)n * m;
+      CXK_TRY(LaunchGemm(a, false, false, nb, ctx->stream));
+    }
+    // A_gram = A1' T (A1' A1 where Q is the identity)
+    a.M = a.N = m;
+    a.K = n;
+    a.A = A1;
+    a.lda = len;
+    a.sA1 = (int64_t)len * m;
+    a.B = g.has_q ? T.p + (size_t)b0 * n * m : A1;
+    a.ldb = g.has_q ? n : len;
+    a.sB1 = g.has_q ? (int64_t)n * m : (int64_t)len * m;
+    a.C = g.qGram.p + (size_t)b0 * m * m;
+    a.ldc = m;
+    a.sC1 = (int64_t)m * m;
+    CXK_TRY(LaunchGemm(a, true, false, nb, ctx->stream));
+  }
+  CXK_TRY(hipStreamSynchronize(ctx->stream));  // (T is released on return)
+  return CXK_SUCCESS;
+}
+
 // A hipEvent pair for this launch of a clock slot's kernels, when it is one of the sampled ones.
 bool ClockSample(cxk_context* ctx, int slot, hipEvent_t* e0, hipEvent_t* e1) {
   *e0 = *e1 = nullptr;
@@ -617,8 +736,17 @@ int LaunchSchur(cxk_context* ctx) {
         static_schur<<<count, 64, 0, ctx->stream>>>(MakeStatic(g), ar);
         break;
       case CXK_QUAD:
-        quad_schur<<<count, 64, QuadSchurLds(g.n, g.m), ctx->stream>>>(MakeQuad(g), ar);
+      {  // (both routes carry the assembly clock when timing is on: tools/quad_stream_speed.py compares them)
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        const bool sample = ClockSample(ctx, CXK_CLOCK_ASSEMBLY, &e0, &e1);
+        if (sample) CXK_TRY(hipEventRecord(e0, ctx->stream));
+        if (g.qstream)
+          CXK_TRY(LaunchQuadStreamSchur(g, ar, ctx->stream));
+        else
+          quad_schur<<<count, 64, QuadSchurLds(g.n, g.m), ctx->stream>>>(MakeQuad(g), ar);
+        if (sample) CXK_TRY(hipEventRecord(e1, ctx->stream));
         break;
+      }
       case CXK_OCT:
         oct_schur<<<count, 64, 0, ctx->stream>>>(MakeOct(g), ar);
         break;
@@ -638,10 +766,14 @@ int GroupConstraints(cxk_context* ctx, const FinalizeSwitches& sw) {
   // linear blocks: the LDS route's one workgroup per block, or the tiled route (cxk_set_tiled_linear, else
   // CXK_TILED_LINEAR, else by size)
   const int tiled_mode = ctx->tiled_linear >= 0 ? ctx->tiled_linear : sw.tiled_linear;
+  // quadratic cones: the LDS route's one workgroup per cone, or held in HBM (cxk_set_streamed_quadratic, else
+  // CXK_STREAMED_QUADRATIC, else none)
+  const int qstream_mode = ctx->streamed_quadratic != -2 ? ctx->streamed_quadratic : sw.streamed_quadratic;
   for (int i = 0; i < K; i++) {
     ConstraintRec& c = ctx->cons[i];
     c.streamed = false;
     c.tiled = false;
+    c.qstream = false;
     if (!ctx->owned[i]) continue;
     if (c.type == CXK_LINEAR) {
       c.tiled = tiled_mode >= 0 ? tiled_mode != 0
@@ -696,14 +828,27 @@ int GroupConstraints(cxk_context* ctx, const FinalizeSwitches& sw) {
                  "a second-order cone whose step kernels need more than the 163 328 B of LDS (four vectors of dimension + 1) is "
                  "not supported");
     }
-    if (c.type == CXK_QUAD)
+    if (c.type == CXK_QUAD) {
+      const bool fits = QuadPrepareLds(c.n, c.m) <= kLdsLimit && QuadSchurLds(c.n, c.m) <= kLdsLimit && QuadTakeLds(c.n) <= kLdsLimit;
+      const double work = (c.Q.empty() ? 0.0 : (double)c.n * c.n) + ((double)c.n + 1) * c.m;  // doubles streamed per pass
+      c.qstream = qstream_mode >= 0 ? qstream_mode != 0 : !fits || work >= (double)sw.streamed_quadratic_min_work;
+    }
+    if (c.type == CXK_QUAD && c.qstream) {
+      // held in HBM (kernels_quad_stream.hip.h): what remains is the int indexing of the kernels and of the GEMM
+      CXK_DEMAND((int64_t)(c.n + 1) * std::max(c.m, 1) <= INT_MAX - 1024,
+                 "a streamed quadratic cone whose (dimension + 1) x variables entries exceed the int range is not supported");
+      CXK_DEMAND((int64_t)c.m * c.m <= INT_MAX,
+                 "a streamed quadratic cone whose variables x variables Schur block exceeds the int range is not supported");
+      CXK_DEMAND(c.Q.empty() || (int64_t)c.n * c.n <= INT_MAX,
+                 "a streamed quadratic cone whose inner-product matrix has more than 2^31 entries is not supported");
+    } else if (c.type == CXK_QUAD)
       // quad_prepare keeps y and four vectors of the cone in LDS; quad_schur and quad_take_step need less
       CXK_DEMAND(QuadPrepareLds(c.n, c.m) <= kLdsLimit && QuadSchurLds(c.n, c.m) <= kLdsLimit && QuadTakeLds(c.n) <= kLdsLimit,
                  "a quadratic cone whose step kernels need more than the 163 328 B of LDS (variables + four vectors of "
                  "dimension + 1) is not supported");
     auto key = std::make_tuple(c.type, c.n, c.m, c.herm_d + (c.sparse ? 16 : 0) + (c.type == CXK_LMI && !c.symmetric ? 32 : 0) +
                                                      (c.type == CXK_QUAD && !c.Q.empty() ? 64 : 0) + (c.streamed ? 128 : 0) +
-                                                     (c.tiled ? 256 : 0));
+                                                     (c.tiled ? 256 : 0) + (c.qstream ? 512 : 0));
     auto it = gmap.find(key);
     if (it == gmap.end()) {
       it = gmap.emplace(key, (int)ctx->groups.size()).first;
@@ -717,6 +862,7 @@ int GroupConstraints(cxk_context* ctx, const FinalizeSwitches& sw) {
       ctx->groups.back().has_q = c.type == CXK_QUAD && !c.Q.empty();
       ctx->groups.back().streamed = c.streamed;
       ctx->groups.back().tiled = c.tiled;
+      ctx->groups.back().qstream = c.qstream;
     }
     c.group = it->second;
     c.member = (int)ctx->groups[it->second].ids.size();
@@ -828,7 +974,24 @@ int UploadGroup(cxk_context* ctx, Group& g, const FinalizeSwitches& sw) {
     }
     CXK_TRY(g.Apk.upload(hp));
   }
-  if (g.type == CXK_QUAD) {
+  if (g.type == CXK_QUAD && g.qstream) {
+    // held in HBM: Q as it is, the constants (Q c1, c1' Q c1, A_gram) on the device (QuadStreamConstants below)
+    const size_t n = (size_t)g.n, m = (size_t)g.m, tiles = (n + kQuadStreamRowTile - 1) / kQuadStreamRowTile;
+    g.splits = g.has_q ? QuadStreamSplits(g.n, (long long)cnt) : 1;
+    if (g.has_q && sw.gram_splits > 0) g.splits = sw.gram_splits;  // (comparison runs)
+    CXK_DEMAND(cnt * std::max<size_t>(std::max<size_t>(m, (m * m + kQuadStreamBlock - 1) / kQuadStreamBlock),
+                                      std::max<size_t>(tiles * (size_t)g.splits, (n + 1 + kSocStreamRowTile - 1) / kSocStreamRowTile)) <=
+                   (size_t)INT_MAX,
+               "a group of streamed quadratic cones with more than 2^31 columns, row tiles or blocks is not supported");
+    std::vector<double> hQ(g.has_q ? n * n * cnt : 0);
+    if (g.has_q)
+      for (size_t k = 0; k < cnt; k++) std::copy(ctx->cons[g.ids[k]].Q.begin(), ctx->cons[g.ids[k]].Q.end(), hQ.begin() + k * n * n);
+    CXK_TRY(g.qQ.upload(hQ));
+    CXK_TRY(g.qGram.alloc(m * m * cnt));
+    CXK_TRY(g.qS.alloc(w_sz * cnt));
+    CXK_TRY(g.st_vec.alloc(QuadStreamVecDoubles(cnt, n, m)));
+    CXK_TRY(g.ws_part.alloc(g.has_q ? cnt * (size_t)g.splits * 2 * n : 0));
+  } else if (g.type == CXK_QUAD) {
     // A_gram = A1' (Q A1), made once (QuadraticConstraintBase::Initialize, quadratic_cone_constraint.cc:216-219)
     const int n = g.n, m = g.m, len = n + 1;
     std::vector<double> hQ(g.has_q ? (size_t)n * n * cnt : 0), hG((size_t)m * m * cnt, 0.0), qa((size_t)n);
@@ -859,6 +1022,7 @@ int UploadGroup(cxk_context* ctx, Group& g, const FinalizeSwitches& sw) {
   CXK_TRY(g.T1.alloc(w_sz * cnt));
   CXK_TRY(g.T2.alloc(g.type == CXK_LINEAR ? w_sz * cnt : 0));
   CXK_TRY(g.dids.upload(g.ids));
+  if (g.type == CXK_QUAD && g.qstream && QuadStreamConstants(ctx, g)) return CXK_FAILURE;
   if (g.type == CXK_LMI && g.sparse && (g.large || !g.sp_small)) {
     const size_t nn = (size_t)g.n * g.n;
     CXK_TRY(g.ws_main.alloc(cnt * 8 * nn));  // step temporaries; C W and W C W during assembly
@@ -1261,6 +1425,19 @@ int LaunchPrepareGroups(cxk_context* ctx, int pmode, const StepArgs& sa, const S
     }
     else if (g.type == CXK_SOC)
       soc_prepare<MODE><<<cnt, 64, SocPrepareLds(g.n, g.m), ctx->stream>>>(MakeVec(g), sa);
+    else if (g.type == CXK_QUAD && g.qstream) {
+      const QuadStreamGroup d = MakeQuadStream(g);
+      const int tiles = (g.n + 1 + kSocStreamRowTile - 1) / kSocStreamRowTile;
+      soc_stream_slack<<<(unsigned)((size_t)cnt * tiles), kSocStreamBlock, 0, ctx->stream>>>(QuadStreamSlackView(g, d), sa, tiles);
+      QuadStreamVecs x;  // Q [w1, ms1] in one pass
+      x.p[0] = d.W + 1;
+      x.p[1] = d.ms + 1;
+      x.stride[0] = x.stride[1] = (size_t)g.n + 1;
+      CXK_TRY(LaunchQuadStreamQmv<2>(d, x, ctx->stream));
+      quad_stream_prepare_mid<MODE><<<cnt, kQuadStreamBlock, 0, ctx->stream>>>(d, sa);
+      CXK_TRY(LaunchQuadStreamQmv<1>(d, QuadStreamOne(d.dv, (size_t)g.n), ctx->stream));
+      quad_stream_prepare_finish<MODE><<<cnt, kQuadStreamBlock, 0, ctx->stream>>>(d, sa);
+    }
     else if (g.type == CXK_QUAD)
       quad_prepare<MODE><<<cnt, 64, QuadPrepareLds(g.n, g.m), ctx->stream>>>(MakeQuad(g), sa);
     else if (g.type == CXK_OCT)
@@ -1382,6 +1559,8 @@ int LaunchTakeStep(cxk_context* ctx, double e_weight, double step_size, const do
       soc_stream_take_step<<<cnt, kSocStreamBlock, 0, ctx->stream>>>(MakeSocStream(g), sa);
     else if (g.type == CXK_SOC)
       soc_take_step<<<cnt, 64, SocTakeLds(g.n), ctx->stream>>>(MakeVec(g), sa);
+    else if (g.type == CXK_QUAD && g.qstream)
+      quad_stream_take_step<<<cnt, kQuadStreamBlock, 0, ctx->stream>>>(MakeQuadStream(g), sa);
     else if (g.type == CXK_QUAD)
       quad_take_step<<<cnt, 64, QuadTakeLds(g.n), ctx->stream>>>(MakeQuad(g), sa);
     else if (g.type == CXK_OCT)

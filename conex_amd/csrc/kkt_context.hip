@@ -102,6 +102,8 @@ static FinalizeSwitches ReadFinalizeSwitches() {
   if ((v = getenv("CXK_STREAMED_CONES"))) sw.streamed_cones = atoi(v) != 0;
   if ((v = getenv("CXK_SOC_STREAM_STAGES"))) sw.soc_stream_stages = atoi(v);
   if ((v = getenv("CXK_TILED_LINEAR")) && v[0] != '\0') sw.tiled_linear = atoi(v) != 0;
+  if ((v = getenv("CXK_STREAMED_QUADRATIC")) && v[0] != '\0') sw.streamed_quadratic = atoi(v) != 0;
+  if ((v = getenv("CXK_STREAMED_QUADRATIC_MIN_WORK")) && v[0] != '\0') sw.streamed_quadratic_min_work = std::max(0ll, atoll(v));
   if ((v = getenv("CXK_TILED_LINEAR_MIN_WORK")) && v[0] != '\0') sw.tiled_linear_min_work = std::max(0ll, atoll(v));
   return sw;
 }
@@ -480,6 +482,20 @@ int cxk_count_tiled_linear(const cxk_context* ctx) {
   if (!ctx || !ctx->finalized) return -1;
   int k = 0;
   for (size_t i = 0; i < ctx->cons.size(); i++) k += ctx->owned[i] && ctx->cons[i].tiled;
+  return k;
+}
+
+int cxk_set_streamed_quadratic(cxk_context* ctx, int mode) {
+  if (!ctx) return CXK_FAILURE;
+  CXK_DEMAND(!ctx->finalized, "cxk_set_streamed_quadratic: the context is finalized (the choice is made by cxk_finalize)");
+  CXK_DEMAND(mode >= -1 && mode <= 1, "cxk_set_streamed_quadratic: the mode is -1 (automatic), 0 (never) or 1 (every quadratic cone)");
+  ctx->streamed_quadratic = mode;
+  return CXK_SUCCESS;
+}
+int cxk_count_streamed_quadratic(const cxk_context* ctx) {
+  if (!ctx || !ctx->finalized) return -1;
+  int k = 0;
+  for (size_t i = 0; i < ctx->cons.size(); i++) k += ctx->owned[i] && ctx->cons[i].qstream;
   return k;
 }
 

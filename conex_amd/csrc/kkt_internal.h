@@ -45,6 +45,7 @@ struct ConstraintRec {
   // P = A W, which needs that; anything else takes the literal kernels (dense_lmi_constraint.cc:72-88)
   bool symmetric = true;
   bool tiled = false;  // linear block on the tiled route (kernels_linear_tiled.hip.h)
+  bool qstream = false;  // quadratic cone held in HBM (kernels_quad_stream.hip.h); `streamed` stays the second-order cone's
 };
 
 template <typename T>
@@ -124,6 +125,10 @@ struct Group {
   // ws_main, the Gram product's output in ws_gf, its split partials in ws_part, four doubles per row tile in lt_part
   bool tiled = false;
   DevBuf<double> lt_part;
+  // quadratic cones held in HBM (cxk_set_streamed_quadratic): the kernels of kernels_quad_stream.hip.h; the split
+  // partials of the products with Q in ws_part (`splits` column splits), every vector and scalar of the work space
+  // in st_vec (MakeQuadStream lays it out)
+  bool qstream = false;
 };
 
 
@@ -156,6 +161,8 @@ struct cxk_context {
   int chain_segments = -1;  // cxk_set_chain_segments: -1 automatic / environment, 0 off, P segments
   int segments = 0;         // segments in use (0: the reference's order)
   int streamed_cones = -1;  // cxk_set_streamed_cones: -1 the environment's CXK_STREAMED_CONES (else off), 0 off, 1 on
+  // cxk_set_streamed_quadratic: -2 the environment's CXK_STREAMED_QUADRATIC (else never), -1 by size, 0 never, 1 every cone
+  int streamed_quadratic = -2;
   int tiled_linear = -1;    // cxk_set_tiled_linear: -1 the environment's CXK_TILED_LINEAR (else by size), 0 never, 1 every block
   std::vector<Group> groups;
   std::vector<int64_t> g_off, r_off;

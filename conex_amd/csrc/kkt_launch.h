@@ -64,6 +64,13 @@ constexpr int kLinearLdsMaxVars = 4096;
 // but the two-launch PrepareStep and query cost 2 us more); twice, because the numbers are one box's on one day.
 constexpr long long kTiledLinearMinWork = 2ll * 2000 * 64 * 64;  // 16 384 000
 
+// Automatic mode (cxk_set_streamed_quadratic(ctx, -1)) sends a quadratic cone to the streamed route from this many
+// doubles streamed per pass, (Q ? n n : 0) + (n + 1) m, on.  Measured (tools/quad_stream_speed.py):
+// the smallest shape of the sweep, n = 32 with Q over m = 8 (32 * 32 + 33 * 8), where assembly + PrepareStep +
+// TakeStep already take 48 us on the streamed route against 333 us on the LDS route; every larger swept shape gains
+// more.  Nothing smaller was measured, so nothing smaller moves (the cones of a handful of doubles stay where they are).
+constexpr long long kQuadStreamMinWork = 32 * 32 + 33 * 8;  // 1288
+
 // The environment switches of cxk_finalize, read once per call (FinalizeImpl).
 struct FinalizeSwitches {
   bool quirks_off = false;      // CXK_REFERENCE_QUIRKS=0: the two corrections instead of the reference as written
@@ -78,6 +85,8 @@ struct FinalizeSwitches {
   int soc_stream_stages = 0;    // CXK_SOC_STREAM_STAGES=1 / 2: their assembly stops after that stage (timing runs: wrong results)
   int tiled_linear = -1;        // CXK_TILED_LINEAR=0 / 1: linear blocks never / always on the tiled route (cxk_set_tiled_linear)
   long long tiled_linear_min_work = kTiledLinearMinWork;  // CXK_TILED_LINEAR_MIN_WORK (comparison runs)
+  int streamed_quadratic = 0;   // CXK_STREAMED_QUADRATIC=0 / 1: quadratic cones never / always held in HBM (cxk_set_streamed_quadratic)
+  long long streamed_quadratic_min_work = kQuadStreamMinWork;  // CXK_STREAMED_QUADRATIC_MIN_WORK (comparison runs)
 };
 
 // ---- kkt_context.hip

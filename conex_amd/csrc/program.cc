@@ -79,6 +79,7 @@ struct Program {
   int reference_identity = -1;  // -1: environment (CXK_REFERENCE_QUIRKS); see CONEX_HIP_SetReferenceIdentity
   int streamed_cones = 1;       // second-order cones beyond LDS run from HBM; see CONEX_HIP_SetStreamedCones
   int tiled_linear = -1;        // linear blocks on the tiled kernels: -1 by size; see CONEX_HIP_SetTiledLinear
+  int streamed_quadratic = -1;  // quadratic cones held in HBM: -1 beyond LDS or by size; see CONEX_HIP_SetStreamedQuadratic
   // multi-GPU (one process per GPU, every rank builds the same program): see CONEX_HIP_SetCommunicator
   int shard_rank = 0, shard_world = 1;
   int debug_timeout_at = -1, debug_timeout_site = 0;  // CONEX_HIP_DebugFusedTimeoutAt (test hook)
@@ -150,6 +151,8 @@ int BuildContext(Program* p) {
   // as the program): none is refused for its size here either
   cxk_set_streamed_cones(p->ctx, p->streamed_cones);
   if (p->tiled_linear >= 0) cxk_set_tiled_linear(p->ctx, p->tiled_linear);
+  // (likewise no quadratic cone is refused for its size: automatic, where the cxk_* interface defaults to never)
+  cxk_set_streamed_quadratic(p->ctx, p->streamed_quadratic);
   if (p->shard_world > 1) {
     if (cxk_set_shard(p->ctx, p->shard_rank, p->shard_world)) return 1;
     if (p->allreduce_fn) {
@@ -1315,6 +1318,17 @@ int CONEX_HIP_SetTiledLinear(void* x, int mode) {
   Program* p = static_cast<Program*>(x);
   if (!p || mode < -1 || mode > 1) return CONEX_FAILURE;
   p->tiled_linear = mode;
+  p->dirty = true;
+  return CONEX_SUCCESS;
+}
+
+/* not part of conex.h: which quadratic cones are held in HBM and run on the streamed kernels (conex_kkt_hip.h,
+ * cxk_set_streamed_quadratic): -1 (the default) those beyond LDS and those large enough to be faster there, 0 none
+ * (a cone beyond LDS is then refused when the program is initialized), 1 every cone */
+int CONEX_HIP_SetStreamedQuadratic(void* x, int mode) {
+  Program* p = static_cast<Program*>(x);
+  if (!p || mode < -1 || mode > 1) return CONEX_FAILURE;
+  p->streamed_quadratic = mode;
   p->dirty = true;
   return CONEX_SUCCESS;
 }

@@ -129,6 +129,8 @@ _SIGNATURES = {
     "cxk_chain_segments": (C.c_int, [C.c_void_p]),
     "cxk_set_streamed_cones": (C.c_int, [C.c_void_p, C.c_int]),
     "cxk_count_streamed_cones": (C.c_int, [C.c_void_p]),
+    "cxk_set_streamed_quadratic": (C.c_int, [C.c_void_p, C.c_int]),
+    "cxk_count_streamed_quadratic": (C.c_int, [C.c_void_p]),
     "cxk_set_tiled_linear": (C.c_int, [C.c_void_p, C.c_int]),
     "cxk_count_tiled_linear": (C.c_int, [C.c_void_p]),
     "cxk_fused_tree_timed_out": (C.c_int, [C.c_void_p]),
@@ -764,6 +766,16 @@ class KktContext:
     def count_streamed_cones(self):
         """Constraints this context owns that run on the streamed second-order cone kernels."""
         return self.L.cxk_count_streamed_cones(self.h)
+
+    def set_streamed_quadratic(self, mode=1):
+        """Quadratic cones held in HBM on the streamed kernels: 1 every cone, 0 none (a cone beyond LDS is then refused
+        at initialize), -1 those beyond LDS and those large enough to be faster there (before initialize; default:
+        CXK_STREAMED_QUADRATIC in the environment, else 0)."""
+        self._check(self.L.cxk_set_streamed_quadratic(self.h, int(mode)), "cxk_set_streamed_quadratic")
+
+    def count_streamed_quadratic(self):
+        """Constraints this context owns that run on the streamed quadratic cone kernels."""
+        return self.L.cxk_count_streamed_quadratic(self.h)
 
     def set_tiled_linear(self, mode=1):
         """Linear blocks on the tiled kernels: 1 every block, 0 none (a block over more than 4096 variables is then

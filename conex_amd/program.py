@@ -186,6 +186,32 @@ class Conex:
         self.c.append(c.copy())
         self.num_constraints += 1
 
+    def AddQuadraticConstraint(self, Q, A, c, variables=None):
+        """c - A y in {(x0, x1): x0 >= sqrt(x1' Q x1)}: the reference's QuadraticConstraint(Q, A, c), which it reaches
+        through its C++ API only (an extra next to its Python surface, like CONEX_HIP_AddQuadraticConstraint itself).
+        Q is n x n or None (the identity), A (n + 1) x len(variables) (x all variables when None), c has n + 1
+        entries.  Returns the constraint id."""
+        A = np.asarray(A, dtype=np.float64)
+        c = _f64(np.asarray(c, dtype=np.float64).ravel())
+        if A.ndim != 2 or A.shape[0] < 2 or len(c) != A.shape[0]:
+            raise ConexError("Invalid quadratic constraint.")
+        n = A.shape[0] - 1
+        Af = capi.colmajor(A)
+        Qf = None
+        if Q is not None:
+            Q = np.asarray(Q, dtype=np.float64)
+            if Q.shape != (n, n):
+                raise ConexError("Invalid quadratic constraint.")
+            Qf = capi.colmajor(Q)
+        v = None if variables is None else np.ascontiguousarray(np.asarray(variables).ravel(), dtype=np.int64)
+        cid = self._L.CONEX_HIP_AddQuadraticConstraint(
+            self.a, None if Qf is None else capi.dp(Qf), n, capi.dp(Af), n + 1, A.shape[1], capi.dp(c), n + 1,
+            None if v is None else v.ctypes.data_as(C.POINTER(C.c_long)), 0 if v is None else len(v))
+        if cid < 0:
+            raise ConexError("Failed to add constraint.")
+        self.num_constraints += 1
+        return cid
+
     # ---- entry-by-entry builders
     def _new(self, fn, *args, what="constraint"):
         cid = C.c_int()

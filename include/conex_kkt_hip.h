@@ -153,6 +153,27 @@ int cxk_count_streamed_cones(const cxk_context* ctx);
 int cxk_set_tiled_linear(cxk_context* ctx, int mode);
 int cxk_count_tiled_linear(const cxk_context* ctx);
 
+/* Quadratic cones { x0 >= sqrt(x1' Q x1) } of real size.  The LDS route (quad_schur, quad_prepare, quad_take_step)
+ * gives a cone one workgroup and runs its maps, the products with Q among them, on one thread; a cone whose
+ * variables + 4 (dimension + 1) doubles exceed LDS is refused at cxk_finalize.  The streamed route
+ * (kernels_quad_stream.hip.h) keeps the cone and Q in HBM: the products with Q on a grid of row tiles and column
+ * splits (up to two vectors per pass over Q; one pass per assembly, two per PrepareStep or eigenvalue query, none
+ * per TakeStep), the O(n) maps on one 256-thread workgroup per cone, A1' Q A1 on the batched fp64 MFMA GEMM at
+ * cxk_finalize.  No atomics, fixed summation orders: two runs give the same bits (not the LDS route's bits).
+ * Before cxk_finalize, mode = 1: every quadratic cone takes the streamed route; 0 (the default without a call: the
+ * environment's CXK_STREAMED_QUADRATIC = 0 | 1, else 0): none does, and the refusal above stands, whatever
+ * cxk_set_streamed_cones says; -1: a cone takes it when it fails one of the LDS route's three demands or when the
+ * doubles streamed per pass, (Q ? n n : 0) + (n + 1) m, reach the measured threshold (kQuadStreamMinWork;
+ * CXK_STREAMED_QUADRATIC_MIN_WORK moves it for comparison runs).  Cones on the LDS route keep their kernels and
+ * their bits.  Every output, getter and setter of a streamed cone is that of any quadratic cone.
+ * Refused on the streamed route at cxk_finalize, by name: (dimension + 1) x variables, variables^2 or the entries
+ * of Q beyond the int range; a group of equal cones with more than 2^31 columns, row tiles or blocks.
+ * cxk_count_streamed_quadratic: constraints this context owns that run on the streamed route (-1 before
+ * cxk_finalize; 0 on a host-only context, which chooses no kernels); cxk_count_streamed_cones keeps counting
+ * second-order cones only. */
+int cxk_set_streamed_quadratic(cxk_context* ctx, int mode);
+int cxk_count_streamed_quadratic(const cxk_context* ctx);
+
 /* Initialize(): symbolic analysis (SupernodalKKTSolver ctor kkt_solver.cc:104-116),
  * Bind (kkt_solver.h:26-33), workspace carve + SetIdentity (cone_program.cc:78-112),
  * upload of constant data, construction of device index tables and level schedule.
