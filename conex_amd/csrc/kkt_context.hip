@@ -161,7 +161,9 @@ static int AllocateSystemBuffers(cxk_context* ctx) {
   const int K = (int)ctx->cons.size();
   const int64_t go = ctx->g_off.empty() ? 0 : ctx->g_off[K - 1] + (int64_t)ctx->cons[K - 1].m * ctx->cons[K - 1].m;
   const int64_t ro = ctx->r_off.empty() ? 0 : ctx->r_off[K - 1] + ctx->cons[K - 1].m;
-  CXK_TRY(ctx->G.alloc((size_t)go));
+  // (two more words behind the last block: the +0.0 and the 1.0 the whole-tree launch's load images point entries
+  // at that do not exist, PlanFusedTree)
+  CXK_TRY(ctx->G.alloc((size_t)go + 2));
   CXK_TRY(ctx->AWc.alloc((size_t)ro));
   CXK_TRY(ctx->AQcc.alloc((size_t)ro));
   CXK_TRY(ctx->sc.alloc((size_t)2 * K, true));  // entries of constraints owned by other ranks stay 0 (summed by the gather)

@@ -276,6 +276,7 @@ struct cxk_context {
   DevBuf<int> fx_rec, fx_xreg;
   DevBuf<long long> fx_xsrc, fx_rsrc;
   DevBuf<int> fx_pub;
+  DevBuf<unsigned> fx_img;  // load images (tree_fused.h, FusedImgLayout); empty for the wide frames
   DevBuf<double> fx_hand, fx_ysig;
   std::vector<double> fx_hand_init;
   long long fx_updb_base = 0;

@@ -1010,6 +1010,8 @@ int PlanFusedAssembly(cxk_context* ctx, const PlanSwitches& sw, const AsmGather&
 // entries / variables with further sources, and where each supernode publishes
 struct FusedTables {
   std::vector<int> recs, xreg, pub;
+  std::vector<unsigned> img;  // load images, img_stride dwords per position (0: the launch has none)
+  int img_stride = 0;
   std::vector<long long> xsrc, rsrc;
 };
 
@@ -1237,14 +1239,101 @@ void FusedTreePublished(const cxk_context* ctx, const UpdateSlots& u, const std:
   }
 }
 
+// The load image of every position below the cut (tree_fused.h, FusedImgLayout): what FusedSupernode's load phase
+// would derive from the record -- where each lane finds each entry of its panel, which entries do not exist, where
+// its row of the right-hand side and of the factor sits, where the published values go and where they are picked up
+// behind the elimination -- is structure, fixed with the plans.  Entries that do not exist point at the +0.0 behind
+// the last block of G, a padding pivot's diagonal at the 1.0 behind that (AllocateSystemBuffers leaves room, the
+// caller writes the two words).  Offsets are 32-bit: a context whose G, AWc or hand-off slots lie beyond that keeps
+// the level kernels.
+void FusedTreeLoadImages(const cxk_context* ctx, int sa, int sb, int cnt_up, size_t n_upd, size_t n_updb, Verdict& v,
+                         FusedTables* ft) {
+  const int na = sa >> 8, ssa = sa & 255, nb = sb >> 8, ssb = sb & 255;
+  if (na > 32 || nb > 32) return;  // (the wide frames keep the computed load phase)
+  const FusedImgLayout ly = FusedImgLayoutOf(na, ssa, nb, ssb);
+  const int K = (int)ctx->cons.size();
+  const int64_t g_end = ctx->g_off[K - 1] + (int64_t)ctx->cons[K - 1].m * ctx->cons[K - 1].m;
+  const int64_t go = (int64_t)ctx->G.n - 2;  // the two constants
+  const int64_t ro = ctx->r_off[K - 1] + ctx->cons[K - 1].m;
+  if (!v.check(go >= g_end && 8 * (go + 2) <= (int64_t)UINT32_MAX && ro < (int64_t)INT32_MAX &&
+                   ctx->md.N < INT32_MAX - 64 && n_upd + 3 * n_updb + 8 < (size_t)INT32_MAX,
+               "offsets beyond the 32 bits of the load image"))
+    return;
+  const unsigned zero_at = (unsigned)(8 * go), one_at = (unsigned)(8 * (go + 1));
+  const int cnt_all = (int)ctx->level_sn.size();
+  ft->img_stride = ly.stride;
+  ft->img.assign((size_t)cnt_all * ly.stride, 0u);
+  for (int pos = 0; pos < cnt_up && v.ok; pos++) {
+    const int* w = ft->recs.data() + (size_t)pos * kFusedRecWords;
+    unsigned* im = ft->img.data() + (size_t)pos * ly.stride;
+    SnRec sr;
+    AsmRec ar;
+    memcpy(&sr, w, sizeof(SnRec));
+    memcpy(&ar, w + 32, sizeof(AsmRec));
+    const int ns = sr.ns, s = sr.nsep;
+    const bool in_a = sa == sb || (ns <= na && s <= ssa);  // (FitsFrame, tree_fused.hip)
+    const int nsm = in_a ? na : nb, smx = in_a ? ssa : ssb;
+    if (!v.check(ns >= 1 && ns <= nsm && s <= smx && ns <= 0xffff, "a supernode beyond its frame")) break;
+    const unsigned rel = (unsigned)(sr.offd_off - sr.diag_off);
+    auto entry = [&](int pa, int pb) {
+      const int hi = std::max(pa, pb), lo = std::min(pa, pb);
+      return (unsigned)(8 * (ar.g_off + hi + (int64_t)lo * ar.m));
+    };
+    for (int row = 0; row < ly.rows; row++) {
+      unsigned* o = im + (size_t)row * ly.nc;
+      unsigned* l = im + ly.l_at + 4 * row;
+      for (int j = 0; j < ly.nc; j++) o[j] = zero_at;
+      l[0] = (unsigned)(ar.r_off + ar.pos[0]);
+      l[1] = (unsigned)sr.start;
+      l[2] = 0u;
+      l[3] = 1u;  // st = 1, lim = 0
+      const int c = row - nsm;
+      if (row < ns) {
+        for (int j = 0; j <= row; j++) o[j] = entry(ar.pos[row], ar.pos[j]);
+        l[0] = (unsigned)(ar.r_off + ar.pos[row]);
+        l[1] = (unsigned)(sr.start + row);
+        l[2] = (unsigned)row;
+        l[3] = (unsigned)ns | (unsigned)(row + 1) << 16;
+      } else if (c >= 0 && c < s) {
+        if (ar.pos[ns + c] != 255)  // (255: structural fill, the row starts as zeros)
+          for (int j = 0; j < ns; j++) o[j] = entry(ar.pos[ns + c], ar.pos[j]);
+        l[2] = rel + (unsigned)(c * ns);
+        l[3] = 1u | (unsigned)ns << 16;
+      } else if (row < nsm) {
+        o[row] = one_at;  // a padding pivot
+      }
+    }
+    // published values, numbered as for three right-hand sides
+    const int npairs = s * (s + 1) / 2, nv3 = npairs + 3 * s;
+    const int rl = FusedRhsLane(nsm, smx);
+    if (!v.check(nv3 <= ly.ul, "more published values than the load image holds")) break;
+    for (int t = 0; t < nv3; t++) {
+      const int tq = t >= npairs + s ? (t - npairs) / s : 0;
+      const int tk = t - tq * s;  // the value of right-hand side 0 it sits behind
+      int k = 0, rem = t < npairs ? t : 0;
+      while (k < s && rem >= s - k) {
+        rem -= s - k;
+        k++;
+      }
+      const int kk = t < npairs ? k : tk - npairs, cc = t < npairs ? k + rem : smx + tq;
+      const unsigned as_col = (unsigned)(nsm + kk) | (unsigned)cc << 8;
+      const unsigned as_row = (rl >= 0 && t >= npairs) ? ((unsigned)(rl + tq) | (unsigned)kk << 8) : as_col;
+      im[ly.u_at + 2 * t] = (unsigned)(ft->pub[(size_t)w[23] + tk] + tq * (int)n_updb);
+      im[ly.u_at + 2 * t + 1] = as_row | as_col << 16 | (tq > 0 ? 1u << 31 : 0u);
+    }
+  }
+}
+
 // Which workgroup takes which supernode.  Every wavefront of the launch is resident (no order is needed
 // for progress) and the dispatcher deals workgroups round-robin over the 8 XCDs (workgroup b on XCD
 // b mod 8: tools/xcc_placement_bench.hip -- a speed assumption only).  A hand-off between wavefronts of
 // one XCD is 0.1 - 0.3 us shorter than one across the fabric (MI355X_MICROARCH.md, handoff-1to1), and
 // the launch is nine hand-offs deep: the supernodes are dealt in depth-first order of the tree, an
 // eighth of them per XCD, so that a supernode mostly sits with its children; within an XCD the level
-// order stays (leaves first: they have the most to load).
-void DealOverXcds(const cxk_context* ctx, const std::vector<int>& pos_of, std::vector<int>* recs) {
+// order stays (leaves first: they have the most to load).  (Within a level, the supernodes with the longest
+// chain of ancestors first -- C4: the 415 leaves at depth four -- measured nothing: DESIGN 4.3.1.)
+void DealOverXcds(const cxk_context* ctx, const std::vector<int>& pos_of, FusedTables* ft) {
+  std::vector<int>* recs = &ft->recs;
   const Layout& L = ctx->lay;
   const int cnt_all = (int)ctx->level_sn.size();
   std::vector<std::vector<int>> kids(cnt_all);
@@ -1279,6 +1368,13 @@ void DealOverXcds(const cxk_context* ctx, const std::vector<int>& pos_of, std::v
   for (int b = 0; b < cnt_all; b++)
     memcpy(dealt.data() + (size_t)b * kFusedRecWords, recs->data() + (size_t)perm[b] * kFusedRecWords, sizeof(int) * kFusedRecWords);
   recs->swap(dealt);
+  // (a workgroup's load image sits at its index, like its record)
+  if (ft->img_stride > 0) {
+    std::vector<unsigned> img(ft->img.size());
+    for (int b = 0; b < cnt_all; b++)
+      memcpy(img.data() + (size_t)b * ft->img_stride, ft->img.data() + (size_t)perm[b] * ft->img_stride, sizeof(unsigned) * ft->img_stride);
+    ft->img.swap(img);
+  }
 }
 
 int PlanFusedTree(cxk_context* ctx, const PlanSwitches& sw, const AsmGather& ag, const ResidGather& rg,
@@ -1309,6 +1405,7 @@ int PlanFusedTree(cxk_context* ctx, const PlanSwitches& sw, const AsmGather& ag,
   std::vector<int> pos_of(ctx->md.K, -1);  // supernode -> position in level order
   for (int pos = 0; pos < cnt_all; pos++) pos_of[ctx->level_sn[pos]] = pos;
   if (v.ok) FusedTreePublished(ctx, u, pos_of, us, ubs, v, &ft);
+  if (v.ok) FusedTreeLoadImages(ctx, sa, sb, cnt_up, us, ubs, v, &ft);
   bool split = false;
   if (v.ok) {
     // residency: every workgroup (one wavefront each, one more for the scalars) at once, with a
@@ -1367,7 +1464,12 @@ int PlanFusedTree(cxk_context* ctx, const PlanSwitches& sw, const AsmGather& ag,
         for (size_t q = 1; q < 3; q++) ctx->fx_hand_init[d + q * ubs] = ctx->fx_hand_init[hs + d + q * ubs] = sent;
     }
   }
-  if (!split && !sharded && !sw.fused_level_order) DealOverXcds(ctx, pos_of, &ft.recs);
+  if (!split && !sharded && !sw.fused_level_order) DealOverXcds(ctx, pos_of, &ft);
+  if (ft.img_stride > 0) {
+    const double consts[2] = {0.0, 1.0};  // (what the images' entries that do not exist point at)
+    CXK_TRY(hipMemcpy(ctx->G.p + ctx->G.n - 2, consts, sizeof(consts), hipMemcpyHostToDevice));
+  }
+  CXK_TRY(ctx->fx_img.upload(ft.img));
   CXK_TRY(ctx->fx_rec.upload(ft.recs));
   CXK_TRY(ctx->fx_xreg.upload(ft.xreg));
   CXK_TRY(ctx->fx_xsrc.upload(ft.xsrc));

@@ -36,6 +36,38 @@ constexpr int kFusedMaxSlots = 4096;     // published values one entry / one row
 struct GatherRec;
 struct ResidRec;
 
+// The load image of a supernode (two-row frames, NSMAX <= 32, in the launches that load from the Schur blocks:
+// kFusedFull, kFusedTriple, kFusedUp, kFusedShardUp): what the load phase needs of the program's STRUCTURE, written
+// once by BuildPlans, one image per workgroup at img + blockIdx x stride -- requested in the same trip as the record,
+// before the record says which of the pair's two frames the supernode runs in, so its layout follows from the pair:
+//   [0, rows x nc)   per lane (lanes >= rows - 1 share the last row, which holds nothing) and column j < nc of the
+//                    frame: the BYTE offset from G of panel entry (lane, j) -- an entry that does not exist (beyond
+//                    the row's columns, a padding row or column, structural fill) points at the +0.0 behind the last
+//                    block of G, a padding pivot's diagonal at the 1.0 behind that: no masks, no selects
+//   [l_at, + 4 rows) per lane: index of its row into AWc / AQcc, index into b, o0, st | lim << 16 (where its row of
+//                    the factor goes in the slab: entry j < lim at o0 + j st)
+//   [u_at, + 2 ul)   per published value t (always numbered as for three right-hand sides: the s (s + 1) / 2 Schur
+//                    updates, then s forward values per right-hand side): its hand-off slot, and where it sits in
+//                    the scratch image behind the elimination as row | col << 8 (index (SMAX + NRHS) row + col) --
+//                    bits 0 .. 15 with the right-hand sides as rows of the panel, 16 .. 30 as columns -- and bit 31:
+//                    a value of right-hand side 1 or 2 (its slot is in the triple launches' own sets)
+struct FusedImgLayout {
+  int nc, rows, ul, l_at, u_at, stride;  // (dwords; every section starts on 16 bytes)
+};
+constexpr int FusedPublished3(int smax) { return smax * (smax + 1) / 2 + 3 * smax; }
+constexpr FusedImgLayout FusedImgLayoutOf(int na, int sa, int nb, int sb) {
+  FusedImgLayout l{};
+  l.nc = na > nb ? na : nb;
+  l.rows = (na + sa > nb + sb ? na + sa : nb + sb) + 1;
+  l.rows = l.rows > 64 ? 64 : l.rows;
+  const int nv = FusedPublished3(sa) > FusedPublished3(sb) ? FusedPublished3(sa) : FusedPublished3(sb);
+  l.ul = nv > 2 ? (nv + 1) / 2 * 2 : 2;
+  l.l_at = l.rows * l.nc;
+  l.u_at = l.l_at + 4 * l.rows;
+  l.stride = l.u_at + 2 * l.ul;
+  return l;
+}
+
 struct FusedTreeArgs {
   const int* rec;
   int count;  // supernodes = workgroups (one more workgroup sums the two scalars)
@@ -44,6 +76,7 @@ struct FusedTreeArgs {
   double* slab;
   double* y;
   const int* pub;      // pub[pub_beg + t]: hand-off slot of a supernode's published value number t
+  const unsigned* img;  // load images, FusedImgLayoutOf(the pair's frames).stride dwords per workgroup
   const int* tg_reg;
   const int* xreg;
   const long long* xsrc;
@@ -77,7 +110,10 @@ struct FusedTreeArgs {
   // A wavefront whose values cannot be there yet SLEEPS before it starts to poll (it shares a SIMD with
   // wavefronts that are eliminating, which are bound by instruction issue): word 63 of its record is its
   // level, a level of the tree takes at least up_sleep units of 64 cycles.  (Measured on C4, same box:
-  // 30.3 -> 29.8 us at 20 .. 40 units, back to 30.1 at 60, 31.7 at 100; the same on the way down: nothing.)
+  // 30.3 -> 29.8 us at 20 .. 40 units, back to 30.1 at 60, 31.7 at 100; the same on the way down: nothing.
+  // Re-measured with the load image, which has level 1 ready a microsecond earlier: level 1 polling at once,
+  // (level - 1) x 30, costs the C4 step 1.1 us -- a poll that reaches a slot before its producer's store misses
+  // L2 and holds the store up -- so level 1 keeps its 30 units and its median of zero polls: DESIGN 4.3.1.)
   int up_sleep;
   // ---- sharded contexts (kFusedShardUp / kFusedShardTop).  Positions [0, count_up) are
   // this rank's own subtrees, [count_up, count) the replicated top of the tree.  The exchange buffer

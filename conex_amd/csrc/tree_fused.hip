@@ -10,8 +10,8 @@
 // kernel boundary (~1.5 us), a record round trip and a data round trip before ~2 us of elimination
 // -- 46 us of dependency latency at BASELINE config 4 (5 levels up, 4 down) in which the chip is
 // nearly idle.  Here every supernode's wavefront is resident from the start: it fetches its
-// record, its panel (straight from the Schur blocks: own block by position, further sources from
-// a dense list), its publish destinations and pull locations while its descendants still work,
+// record, its panel (straight from the Schur blocks: own block through its plan-time load image,
+// tree_fused.h FusedImgLayout, or by position where there is none; further sources from a dense list), its publish destinations and pull locations while its descendants still work,
 // and then only WAITS for their values.
 //
 // Hand-off without flags or fences.  A published value is its own "ready" flag: every slot a
@@ -95,6 +95,56 @@ __device__ __forceinline__ void ReportTimeout(const FusedTreeArgs& A) {
   }
 }
 
+// A lane's part of its supernode's load image (tree_fused.h), fetched by the kernel beside the record: NC offsets of
+// panel entries, the row's four words, PRW rounds of publish entries.  FusedNoImg: the launches and frames that keep
+// the load phase computed from the record (the replicated top of a sharded context, the wide frames).
+template <int NC, int PRW>
+struct FusedImg {
+  unsigned off[NC];
+  unsigned aw, bi, o0, sl;
+  int pd[PRW];
+  unsigned pk[PRW];
+};
+struct FusedNoImg {};
+
+constexpr int FusedRounds(int smax, int nrhs) { return (smax * (smax + 1) / 2 + nrhs * smax + 63) / 64; }
+template <int NA, int SA, int NB, int SB, int NRHS>
+struct FusedImgOf {
+  static constexpr FusedImgLayout kLy = FusedImgLayoutOf(NA, SA, NB, SB);
+  static constexpr int kRa = FusedRounds(SA, NRHS), kRb = FusedRounds(SB, NRHS);
+  static constexpr int kRounds = kRa > kRb ? (kRa > 1 ? kRa : 1) : (kRb > 1 ? kRb : 1);
+  using type = FusedImg<kLy.nc, kRounds>;
+  static_assert(kLy.nc % 4 == 0 && NA + SA < kLy.rows && NB + SB < kLy.rows, "rows of four-word groups, one spare row");
+  static __device__ __forceinline__ type Load(const FusedTreeArgs& A, int pos) {
+    type I;
+    const int lane = threadIdx.x & 63;
+    const unsigned* im = A.img + (size_t)pos * kLy.stride;
+    const int row = lane < kLy.rows - 1 ? lane : kLy.rows - 1;
+    const uint4* po = reinterpret_cast<const uint4*>(im + row * kLy.nc);
+#pragma unroll
+    for (int q = 0; q < kLy.nc / 4; q++) {
+      const uint4 v = po[q];
+      I.off[4 * q] = v.x;
+      I.off[4 * q + 1] = v.y;
+      I.off[4 * q + 2] = v.z;
+      I.off[4 * q + 3] = v.w;
+    }
+    const uint4 l = *reinterpret_cast<const uint4*>(im + kLy.l_at + 4 * row);
+    I.aw = l.x;
+    I.bi = l.y;
+    I.o0 = l.z;
+    I.sl = l.w;
+#pragma unroll
+    for (int r = 0; r < kRounds; r++) {
+      const int t = lane + 64 * r;
+      const uint2 u = *reinterpret_cast<const uint2*>(im + kLy.u_at + 2 * (t < kLy.ul ? t : 0));
+      I.pd[r] = (int)u.x;
+      I.pk[r] = u.y;
+    }
+    return I;
+  }
+};
+
 // acc += w[lane J of the own 16-lane DPP row] * v (the multiply-add of DppColumns, dense_elim.hip.h; operands
 // through DppOperandFence first)
 template <int J>
@@ -116,9 +166,12 @@ __device__ __forceinline__ void FmacRowBcast(double& acc, double w, double v) {
 // solutions: the interior-point iteration needs no second sweep over the tree.  Right-hand side 0 uses the
 // hand-off slots of every other launch (set = run parity); 1 and 2 have slots of their own behind them
 // (fwd_stride / N apart), whose two sets alternate with the TRIPLE launches only (A.tgen).
-template <int NSMAX, int SMAX, bool UP_ONLY = false, bool FROM_X = false, int NRHS = 1>
-__device__ __forceinline__ void FusedSupernode(const FusedTreeArgs& A, const int w, double* __restrict__ my) {
+template <int NSMAX, int SMAX, bool UP_ONLY = false, bool FROM_X = false, int NRHS = 1, class IMG = FusedNoImg>
+__device__ __forceinline__ void FusedSupernode(const FusedTreeArgs& A, const int w, double* __restrict__ my, const IMG& I = IMG{}) {
   static_assert(NSMAX + SMAX <= 64, "one lane per panel row");
+  // the load phase reads the plan-time image, or computes everything from the record
+  constexpr bool IMAGED = !std::is_same<IMG, FusedNoImg>::value;
+  static_assert(IMAGED == (!FROM_X && NSMAX <= 32), "two-row frames that load from the Schur blocks: the image");
   static_assert(NRHS == 1 || (NRHS == 3 && !UP_ONLY && !FROM_X && NSMAX <= 32), "three right-hand sides: the one-launch sweep of a single GPU");
   // (three right-hand sides: pull lists four slots at a time -- the registers of eight are spoken for)
   constexpr int RB = NSMAX + SMAX, MMAX = NRHS > 1 ? 4 : kFastSlots, MFMAX = MMAX, XMAX = kFusedExtraSlots;
@@ -148,9 +201,17 @@ __device__ __forceinline__ void FusedSupernode(const FusedTreeArgs& A, const int
   const bool is_sep = sc >= 0 && sc < s;
   double* base = A.slab + R.diag_off;
   const unsigned rel = (unsigned)(R.offd_off - R.diag_off);
-  const unsigned o0 = is_row ? (unsigned)lane : (is_sep ? rel + (unsigned)(sc * ns) : 0u);
-  const unsigned st = is_row ? (unsigned)ns : 1u;
-  const int lim = is_row ? lane + 1 : (is_sep ? ns : 0);  // valid j < lim
+  unsigned o0, st;
+  int lim;  // valid j < lim
+  if constexpr (IMAGED) {
+    o0 = I.o0;
+    st = I.sl & 0xffffu;
+    lim = (int)(I.sl >> 16);
+  } else {
+    o0 = is_row ? (unsigned)lane : (is_sep ? rel + (unsigned)(sc * ns) : 0u);
+    st = is_row ? (unsigned)ns : 1u;
+    lim = is_row ? lane + 1 : (is_sep ? ns : 0);
+  }
   const int gen = A.gen;
   double* handG = A.hand + (int64_t)gen * A.hand_stride;        // this run's set of hand-off slots
   double* handO = A.hand + (int64_t)(gen ^ 1) * A.hand_stride;  // the other one: re-armed at the end
@@ -164,7 +225,36 @@ __device__ __forceinline__ void FusedSupernode(const FusedTreeArgs& A, const int
   const int pub_beg = __builtin_amdgcn_readlane(w, 23);
   const int npairs = s * (s + 1) / 2, nv = npairs + NRHS * s;
 
-  // ---- load phase, first trip: everything whose address follows from the record
+  // ---- load phase, first trip: everything whose address follows from the record (or, IMAGED, from the image
+  // that came with it)
+  double a[NSMAX + SMAX + NCOL];
+  double rv[NRHS];  // this lane's entry of every right-hand side, until the elimination
+  double fwx = 0.0;  // FROM_X: what this rank's ... every rank's subtrees subtract from the right-hand side
+  double awv, aqv;
+  double rb;
+  // where this supernode's values go: lane t of round r publishes value number t + 64 r (the
+  // s (s + 1) / 2 Schur updates in the reference's S_S enumeration, then the s forward values)
+  int pd[PR > 0 ? PR : 1], prd[PR > 0 ? PR : 1];
+  bool pdt[PR > 0 ? PR : 1];  // value of right-hand side 1 or 2: its slot is in the TRIPLE launches' own sets
+  pd[0] = prd[0] = 0;
+  pdt[0] = false;
+  if constexpr (IMAGED) {
+    // every entry has an address of its own in G -- those that do not exist the +0.0 or the 1.0 behind the last
+    // block -- so a column is one load from a scalar base and the 0.0 + below, nothing else
+    const char* gb = reinterpret_cast<const char*>(A.G);
+#pragma unroll
+    for (int j = 0; j < NSMAX; j++) a[j] = *reinterpret_cast<const double*>(gb + I.off[j]);
+    awv = A.AWc[I.aw];
+    aqv = A.AQcc[I.aw];
+    rb = A.b[I.bi];
+#pragma unroll
+    for (int r = 0; r < PR; r++) {
+      const unsigned pk = ROWRHS ? I.pk[r] : I.pk[r] >> 16;
+      pd[r] = I.pd[r];
+      prd[r] = (SMAX + NRHS) * (int)(pk & 255u) + (int)((pk >> 8) & 127u);
+      pdt[r] = (int)I.pk[r] < 0;
+    }
+  } else {
   const double* Gk = A.G + (FROM_X ? 0 : Join64(f(0), f(1)));
   const int64_t roff = FROM_X ? 0 : Join64(f(2), f(3));
   const int M = f(4);
@@ -174,9 +264,6 @@ __device__ __forceinline__ void FusedSupernode(const FusedTreeArgs& A, const int
   const int mypr = (__builtin_amdgcn_ds_bpermute(4 * (32 + 6 + (q >> 2)), w) >> (8 * (q & 3))) & 255;
   const int myp = mypr == 255 ? 0 : mypr;
   const int has_fill = FROM_X ? 0 : f(5);
-  double a[NSMAX + SMAX + NCOL];
-  double rv[NRHS];  // this lane's entry of every right-hand side, until the elimination
-  double fwx = 0.0;  // FROM_X: what this rank's ... every rank's subtrees subtract from the right-hand side
   if constexpr (FROM_X) {
     // entry (row, j) of the diagonal block sits at xs_base + j ns - j (j - 1) / 2 + (row - j) (lower
     // triangle, column by column), entry (j, c) of the off block behind the triangle at c ns + j
@@ -213,7 +300,6 @@ __device__ __forceinline__ void FusedSupernode(const FusedTreeArgs& A, const int
     }
   }
   const int pr = is_row ? myp : (f(6) & 255);
-  double awv, aqv;
   if constexpr (FROM_X) {
     const int64_t xv = A.n_xs + f(2) + (is_row ? lane : 0);
     awv = A.x[xv];
@@ -223,13 +309,7 @@ __device__ __forceinline__ void FusedSupernode(const FusedTreeArgs& A, const int
     awv = A.AWc[roff + pr];
     aqv = A.AQcc[roff + pr];
   }
-  double rb = A.b[R.start + (is_row ? lane : 0)];
-  // where this supernode's values go: lane t of round r publishes value number t + 64 r (the
-  // s (s + 1) / 2 Schur updates in the reference's S_S enumeration, then the s forward values)
-  int pd[PR > 0 ? PR : 1], prd[PR > 0 ? PR : 1];
-  bool pdt[PR > 0 ? PR : 1];  // value of right-hand side 1 or 2: its slot is in the TRIPLE launches' own sets
-  pd[0] = prd[0] = 0;
-  pdt[0] = false;
+  rb = A.b[R.start + (is_row ? lane : 0)];
 #pragma unroll
   for (int r = 0; r < PR; r++) {
     const int t = lane + 64 * r;
@@ -252,6 +332,7 @@ __device__ __forceinline__ void FusedSupernode(const FusedTreeArgs& A, const int
     else
       prd[r] = (SMAX + NRHS) * (NSMAX + (t < nv ? kk : 0)) + (t < nv ? cc : 0);
   }
+  }  // load phase computed from the record
   const int ntg = R.tg_end - R.tg_beg;
   int ploc0 = 0, ploc1 = 0;
   if (ntg > 0) {
@@ -346,14 +427,16 @@ __device__ __forceinline__ void FusedSupernode(const FusedTreeArgs& A, const int
       rb = A.k * (rb * A.bs + aqv * A.cs) - 2 * awv;
   }
   if constexpr (FROM_X) rb -= fwx;  // (exchange_unpack: y = .. - the forward values of all ranks' subtrees)
+  if constexpr (!IMAGED) {
 #pragma unroll
-  for (int j = 0; j < NSMAX; j++) a[j] = (j < lim) ? a[j] : 0.0;
-  // padding pivots: unit diagonal (set here, ahead of the wait for the descendants -- no pulled entry is a padding
-  // one, the LDS image below carries them along -- instead of behind it, where every instruction is on the
-  // tree's critical path)
+    for (int j = 0; j < NSMAX; j++) a[j] = (j < lim) ? a[j] : 0.0;
+    // padding pivots: unit diagonal (set here, ahead of the wait for the descendants -- no pulled entry is a padding
+    // one, the LDS image below carries them along -- instead of behind it, where every instruction is on the
+    // tree's critical path; IMAGED: the entries beyond lim came as +0.0, the unit diagonals as 1.0)
 #pragma unroll
-  for (int j = 0; j < NSMAX; j++)
-    if (j >= ns && lane == j) a[j] = 1.0;
+    for (int j = 0; j < NSMAX; j++)
+      if (j >= ns && lane == j) a[j] = 1.0;
+  }
 #pragma unroll
   for (int c = 0; c < SMAX; c++) a[NSMAX + c] = 0.0;
   rv[0] = is_row ? (NRHS == 1 ? rb : rb * A.bs) : 0.0;
@@ -1125,14 +1208,23 @@ __global__ void __launch_bounds__(64, 2) tree_fused(FusedTreeArgs A) {
     return;
   }
   const int w = A.rec[(size_t)pos * kFusedRecWords + (threadIdx.x & 63)];
-  const int ns = __builtin_amdgcn_readlane(w, 1), s = __builtin_amdgcn_readlane(w, 2);
   constexpr int NRHS = MODE == 2 ? 3 : 1;
-  if (NA == NB && SA == SB) {
-    FusedSupernode<NA, SA, MODE == 1, false, NRHS>(A, w, lds);
-  } else if (FitsFrame<NA, SA>(ns, s)) {
-    FusedSupernode<NA, SA, MODE == 1, false, NRHS>(A, w, lds);
+  if constexpr (NA <= 32 && NB <= 32) {
+    // (the image is asked for in the same trip as the record, before the record says which frame it is for)
+    using Img = FusedImgOf<NA, SA, NB, SB, NRHS>;
+    const typename Img::type I = Img::Load(A, pos);
+    const int ns = __builtin_amdgcn_readlane(w, 1), s = __builtin_amdgcn_readlane(w, 2);
+    if (NA == NB && SA == SB) {
+      FusedSupernode<NA, SA, MODE == 1, false, NRHS>(A, w, lds, I);
+    } else if (FitsFrame<NA, SA>(ns, s)) {
+      FusedSupernode<NA, SA, MODE == 1, false, NRHS>(A, w, lds, I);
+    } else {
+      FusedSupernode<NB, SB, MODE == 1, false, NRHS>(A, w, lds, I);
+    }
   } else {
-    FusedSupernode<NB, SB, MODE == 1, false, NRHS>(A, w, lds);
+    // (the wide frames: one supernode of 33 .. 64 columns, load phase computed from the record)
+    static_assert(NA == NB && SA == SB, "the wide instances are single-frame");
+    FusedSupernode<NA, SA, MODE == 1, false, NRHS>(A, w, lds);
   }
 }
 
@@ -1241,13 +1333,15 @@ __global__ void __launch_bounds__(64) tree_fused_shard_up(FusedTreeArgs A) {
   const int pos = blockIdx.x;
   if (pos < A.count_up) {
     const int w = A.rec[(size_t)pos * kFusedRecWords + (threadIdx.x & 63)];
+    using Img = FusedImgOf<NA, SA, NB, SB, 1>;
+    const typename Img::type I = Img::Load(A, pos);
     const int ns = __builtin_amdgcn_readlane(w, 1), s = __builtin_amdgcn_readlane(w, 2);
     if (NA == NB && SA == SB) {
-      FusedSupernode<NA, SA, true>(A, w, lds);
+      FusedSupernode<NA, SA, true>(A, w, lds, I);
     } else if (FitsFrame<NA, SA>(ns, s)) {
-      FusedSupernode<NA, SA, true>(A, w, lds);
+      FusedSupernode<NA, SA, true>(A, w, lds, I);
     } else {
-      FusedSupernode<NB, SB, true>(A, w, lds);
+      FusedSupernode<NB, SB, true>(A, w, lds, I);
     }
     // Behind this wavefront's failure report, if any (an atomic too: the wait orders the two).  64
     // counters on lines of their own, position modulo 64: one counter would serialise its adders at
