@@ -694,7 +694,11 @@ int LaunchSchur(cxk_context* ctx) {
             lg.A = g.Apad.p;
             lg.a_stride = (long long)(g.m + 1) * np * np;
           }
-          CXK_TRY(LaunchLmiSchurMfma(lg, ar, ctx->cus, ctx->stream, e0, e1));
+          // every other launch of the group last to first: a launch then starts on the operands the previous one
+          // ended with, which shortens its fill (the results are the same bits either way)
+          const int rev = ctx->lmi_order_forward ? 0 : (int)(g.schur_launches & 1);
+          g.schur_launches++;
+          CXK_TRY(LaunchLmiSchurMfma(lg, ar, ctx->cus, rev, ctx->stream, e0, e1));
         } else {
           lmi_schur_generic<<<count, 256, LmiGenericLds(g.n), ctx->stream>>>(MakeLmi(g), ar);
         }

@@ -241,6 +241,7 @@ int cxk_create(int num_vars, int device, void* stream, cxk_context** out) {
   ctx->prepare_lds = getenv("CXK_PREPARE_LDS") != nullptr;
   ctx->no_step_tail = getenv("CXK_NO_STEP_TAIL") != nullptr || ctx->prepare_lds;
   ctx->no_triple = getenv("CXK_NO_TRIPLE") != nullptr;
+  if (const char* v = getenv("CXK_LMI_ORDER")) ctx->lmi_order_forward = !strcmp(v, "forward");
   ctx->no_y_deferral = getenv("CXK_NO_Y_DEFERRAL") != nullptr;
   ctx->no_device_mu = getenv("CXK_NO_DEVICE_MU") != nullptr;
   if (device >= 0) {

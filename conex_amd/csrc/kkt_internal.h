@@ -98,6 +98,9 @@ struct Group {
   DevBuf<double> qQ, qGram, qS;   // CXK_QUAD: Q, A1' Q A1, the state kept between PrepareStep and TakeStep
   int herm_d = 0;
   bool mfma = false;     // lmi_schur_mfma (lmi_fused_mfma.hip)
+  // lmi_schur_mfma launches of this group so far: an odd one walks each workgroup's constraints backwards, so
+  // that it starts on the operands its predecessor ended with (cxk_context::lmi_order_forward turns that off)
+  unsigned schur_launches = 0;
   bool literal = false;  // non-symmetric data: literal kernels only
   // orders beyond the LDS-resident kernels: HBM-resident matrices + MFMA GEMM pipeline
   bool large = false;
@@ -292,6 +295,7 @@ struct cxk_context {
   bool no_y_deferral = false;  // CXK_NO_Y_DEFERRAL=1 at cxk_create: the direction in a launch of its own (newton_from_three)
   DevBuf<unsigned long long> y_done;  // count of the direction's workgroups, all launches so far
   unsigned long long y_done_target = 0;
+  bool lmi_order_forward = false;  // CXK_LMI_ORDER=forward at cxk_create: every lmi_schur_mfma launch in the same (forward) order
   bool no_triple = false;  // CXK_NO_TRIPLE=1 at cxk_create: the mu selection's solve and the Newton direction as two sweeps
   unsigned fused_gen = 0;
   double* fx_flag = nullptr;  // pinned host word the kernel sets when a wait ran out

@@ -28,9 +28,11 @@ LmiMfmaInstance LmiMfmaChoose(int n, int m, int herm_d);
 
 // ConstructSchurComplementSystem(DenseLMIConstraint*) for every member of the group
 // (dense_lmi_constraint.cc:72-103); `cus` = multiprocessors of the device the stream runs on.
+// rev: 0 = every workgroup takes its constraints first to last, 1 = last to first (same constraints, same
+// results, bit for bit: the caller alternates, so that a launch starts on what its predecessor ended with).
 // ev_start / ev_stop (both or neither): HIP events attached to the dispatch (hipExtLaunchKernel), whose
 // elapsed time is the kernel's own duration.
-hipError_t LaunchLmiSchurMfma(const LmiGroup& g, const Arena& ar, int cus, hipStream_t stream,
+hipError_t LaunchLmiSchurMfma(const LmiGroup& g, const Arena& ar, int cus, int rev, hipStream_t stream,
                               hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
 
 }  // namespace cxk

@@ -74,9 +74,24 @@ __device__ long long g_mfma_stamp[2 * 16 * 64];
     if ((blockIdx.x == 0 || blockIdx.x == 200) && (threadIdx.x & 63) == 0 && (slot) < 64)          \
       g_mfma_stamp[((blockIdx.x ? 1 : 0) * 16 + (threadIdx.x >> 6)) * 64 + (slot)] = __builtin_amdgcn_s_memtime(); \
   } while (0)
+// ... and where the dispatcher put those two workgroups in each of the last 64 launches (XCC_ID), with the
+// order each launch ran in: the alternating order gains only if workgroup b keeps its XCD from launch to launch
+__device__ int g_mfma_xcc[2 * 64];
+__device__ int g_mfma_launches[2];
+#define MXCC(rev)                                                                                   \
+  do {                                                                                              \
+    if ((blockIdx.x == 0 || blockIdx.x == 200) && threadIdx.x == 0) {                               \
+      const int b_ = blockIdx.x ? 1 : 0, n_ = g_mfma_launches[b_];                                  \
+      g_mfma_xcc[b_ * 64 + (n_ & 63)] = (__builtin_amdgcn_s_getreg((31 << 11) | 20) & 15) | ((rev) ? 16 : 0); \
+      g_mfma_launches[b_] = n_ + 1;                                                                 \
+    }                                                                                               \
+  } while (0)
 #else
 #define MSTAMP(slot) \
   do {               \
+  } while (0)
+#define MXCC(rev) \
+  do {            \
   } while (0)
 #endif
 
@@ -447,7 +462,11 @@ template <int N, bool H>
 // (Tried on top of it: one buffer of partial tiles as well, which halves a workgroup's LDS, and TWO
 // workgroups per CU -- 26.9 us instead of 22.2 at C4: symmetric workgroups fill and drain together,
 // so neither hides the other's waits, and the first loads double.)
-__global__ void __launch_bounds__(MfmaCfg<N>::THREADS) lmi_schur_mfma(LmiGroup g, Arena ar, int single) {
+// rev != 0: the workgroup walks its constraints last to first (LaunchLmiSchurMfma: every other launch of a
+// group), so that a launch starts on the operands its predecessor finished with: measured, the fill is 2 k cycles
+// shorter in launches of either direction (profiles/r07; whether the XCD's L2 is what serves them is not
+// established).  The set of constraints, what is computed for each and where it goes are the same in both orders.
+__global__ void __launch_bounds__(MfmaCfg<N>::THREADS) lmi_schur_mfma(LmiGroup g, Arena ar, int single, int rev) {
   using Cfg = MfmaCfg<N, H>;
   constexpr int NK = Cfg::NK, LD = Cfg::LD, MS = Cfg::MS, TPW = Cfg::TPW, RPM = Cfg::RPM;
   extern __shared__ double lds[];
@@ -470,6 +489,9 @@ __global__ void __launch_bounds__(MfmaCfg<N>::THREADS) lmi_schur_mfma(LmiGroup g
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int first = blockIdx.x, stride = gridDim.x;
   const int cnt = (g.count - first + stride - 1) / stride;  // constraints of this workgroup (>= 1)
+  // member of iteration it: first + it * stride forwards, first + (cnt - 1 - it) * stride backwards
+  const int mem0 = rev ? first + (cnt - 1) * stride : first, mstep = rev ? -stride : stride;
+  MXCC(rev);
 
   if (wave < Cfg::PROD) {
     // ------------------------------------------------------------------ producers
@@ -479,7 +501,7 @@ __global__ void __launch_bounds__(MfmaCfg<N>::THREADS) lmi_schur_mfma(LmiGroup g
     MakeGeom<N, H>(gm, wave, lane, rows, nt1);
     MSTAMP(0);
     {
-      const ConstraintPtrs c0 = Member(g, first, g.n * g.n);
+      const ConstraintPtrs c0 = Member(g, mem0, g.n * g.n);
       // Issue order matters: waits count loads in flight in issue order, and the loop below
       // reloads the slots in the order 0, 1, ...; the scheduling barriers keep the compiler from
       // permuting these independent loads (it emitted them last-slot-first, which made every
@@ -498,7 +520,7 @@ __global__ void __launch_bounds__(MfmaCfg<N>::THREADS) lmi_schur_mfma(LmiGroup g
       // count of loads in flight is the same on every path and each wait can be exact.
       MSTAMP(1 + 4 * it);
       const int itn = it + 1 < cnt ? it + 1 : it;
-      const ConstraintPtrs nx = Member(g, first + itn * stride, g.n * g.n);
+      const ConstraintPtrs nx = Member(g, mem0 + itn * mstep, g.n * g.n);
       w = wn;
       // the next constraint's W operands: a whole iteration ahead where the registers allow it
       // (N <= 20), behind this iteration's tiles otherwise (the order-24 instances spill with both
@@ -614,9 +636,10 @@ __global__ void __launch_bounds__(MfmaCfg<N>::THREADS) lmi_schur_mfma(LmiGroup g
     ca = two ? il * MS : ra;
   }
   // Iteration 0 has nothing to consume: look up where this workgroup's constraints write (two
-  // dependent loads each) and park the answers in LDS, off every later critical path.
+  // dependent loads each) and park the answers in LDS, off every later critical path.  (Slot ct belongs to
+  // ITERATION ct, whichever member that is in this launch's order.)
   if (ct < kDestSlots && ct < cnt) {
-    const int id = g.ids[first + ct * stride];
+    const int id = g.ids[mem0 + ct * mstep];
     dest[3 * ct] = id;
     dest[3 * ct + 1] = ar.g_off[id];
     dest[3 * ct + 2] = ar.r_off[id];
@@ -733,7 +756,7 @@ bool SingleT(int m) {
 }
 
 template <int N, bool H>
-hipError_t LaunchT(const LmiGroup& g, const Arena& ar, int cus, hipStream_t stream, hipEvent_t ev_start,
+hipError_t LaunchT(const LmiGroup& g, const Arena& ar, int cus, int rev, hipStream_t stream, hipEvent_t ev_start,
                    hipEvent_t ev_stop) {
   static PerDeviceOnce once;
   const hipError_t ec = once.run([] {
@@ -750,9 +773,9 @@ hipError_t LaunchT(const LmiGroup& g, const Arena& ar, int cus, hipStream_t stre
     // the events ride on the dispatch itself (its own begin / end time stamps, what rocprofv3
     // reports): no marker packets around the kernel, no ~5.7 us bubble behind a bracketed launch
     hipExtLaunchKernelGGL((lmi_schur_mfma<N, H>), dim3(grid), dim3(MfmaCfg<N>::THREADS), (uint32_t)lds, stream, ev_start,
-                          ev_stop, 0, g, ar, single);
+                          ev_stop, 0, g, ar, single, rev);
   else
-    lmi_schur_mfma<N, H><<<grid, MfmaCfg<N>::THREADS, lds, stream>>>(g, ar, single);
+    lmi_schur_mfma<N, H><<<grid, MfmaCfg<N>::THREADS, lds, stream>>>(g, ar, single, rev);
   return hipGetLastError();
 }
 
@@ -794,17 +817,17 @@ LmiMfmaInstance LmiMfmaChoose(int n, int m, int herm_d) {
 }
 
 // g.A / g.a_stride: [A_1 .. A_m | C] per member at the PADDED order; g.n, g.W: the order itself.
-hipError_t LaunchLmiSchurMfma(const LmiGroup& g, const Arena& ar, int cus, hipStream_t stream, hipEvent_t ev_start,
+hipError_t LaunchLmiSchurMfma(const LmiGroup& g, const Arena& ar, int cus, int rev, hipStream_t stream, hipEvent_t ev_start,
                               hipEvent_t ev_stop) {
   if (g.count <= 0) return hipSuccess;
   const LmiMfmaInstance inst = LmiMfmaChoose(g.n, g.m, g.herm_d);
-  if (inst.folded) return LaunchT<24, true>(g, ar, cus, stream, ev_start, ev_stop);
+  if (inst.folded) return LaunchT<24, true>(g, ar, cus, rev, stream, ev_start, ev_stop);
   switch (inst.order) {
-    case 8: return LaunchT<8, false>(g, ar, cus, stream, ev_start, ev_stop);
-    case 12: return LaunchT<12, false>(g, ar, cus, stream, ev_start, ev_stop);
-    case 16: return LaunchT<16, false>(g, ar, cus, stream, ev_start, ev_stop);
-    case 20: return LaunchT<20, false>(g, ar, cus, stream, ev_start, ev_stop);
-    case 24: return LaunchT<24, false>(g, ar, cus, stream, ev_start, ev_stop);
+    case 8: return LaunchT<8, false>(g, ar, cus, rev, stream, ev_start, ev_stop);
+    case 12: return LaunchT<12, false>(g, ar, cus, rev, stream, ev_start, ev_stop);
+    case 16: return LaunchT<16, false>(g, ar, cus, rev, stream, ev_start, ev_stop);
+    case 20: return LaunchT<20, false>(g, ar, cus, rev, stream, ev_start, ev_stop);
+    case 24: return LaunchT<24, false>(g, ar, cus, rev, stream, ev_start, ev_stop);
   }
   return hipErrorNotSupported;
 }
@@ -814,5 +837,11 @@ hipError_t LaunchLmiSchurMfma(const LmiGroup& g, const Arena& ar, int cus, hipSt
 #ifdef CXK_MFMA_STAMPS
 extern "C" __attribute__((visibility("default"))) int cxk_debug_mfma_stamps(long long* out) {
   return hipMemcpyFromSymbol(out, HIP_SYMBOL(cxk::g_mfma_stamp), sizeof(long long) * 2 * 16 * 64) == hipSuccess ? 0 : 1;
+}
+// out[2 * 64]: XCC_ID (bits 3:0) and order (bit 4: reversed) of workgroups 0 and 200, launch n in slot n & 63;
+// launches[2]: how many launches each has recorded
+extern "C" __attribute__((visibility("default"))) int cxk_debug_mfma_xcc(int* out, int* launches) {
+  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(cxk::g_mfma_xcc), sizeof(int) * 2 * 64) != hipSuccess) return 1;
+  return hipMemcpyFromSymbol(launches, HIP_SYMBOL(cxk::g_mfma_launches), sizeof(int) * 2) == hipSuccess ? 0 : 1;
 }
 #endif
