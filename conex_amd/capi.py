@@ -72,6 +72,7 @@ def api():
         "CONEX_HIP_AddQuadraticCostEpigraph": (ci, [vp, c_double_p, ci, C.POINTER(C.c_long), C.c_long]),
         "CONEX_HIP_SetStreamedCones": (ci, [vp, ci]),
         "CONEX_HIP_SetTiledLinear": (ci, [vp, ci]),
+        "CONEX_HIP_SetSparseLinear": (ci, [vp, ci]),
         "CONEX_HIP_SetStreamedQuadratic": (ci, [vp, ci]),
         # the block solve of the cxk_* layer (include/conex_kkt_hip.h), as conex_amd.kkt declares it
         "cxk_solve_block": (ci, [vp, c_double_p, ci, ci]),

@@ -15,6 +15,7 @@
 #include "kernels_quad.hip.h"
 #include "kernels_soc_stream.hip.h"
 #include "kernels_linear_tiled.hip.h"
+#include "kernels_linear_sparse.hip.h"
 #include "kernels_quad_stream.hip.h"
 
 namespace cxk_host {
@@ -135,6 +136,18 @@ LinTiledGroup MakeLinTiled(Group& g) {
   d.WA = g.ws_main.p;
   d.Gf = g.ws_gf.p;
   d.part = g.lt_part.p;
+  return d;
+}
+LinSparseGroup MakeLinSparse(Group& g) {
+  LinSparseGroup d;
+  d.t = MakeLinTiled(g);  // (A is null, WA and Gf unused: the scalars and finish kernels read v and part only)
+  d.eptr = g.ls_eptr.p;
+  d.rowptr = g.ls_rowptr.p;
+  d.col = g.ls_col.p;
+  d.val = g.ls_val.p;
+  d.colptr = g.ls_colptr.p;
+  d.crow = g.ls_crow.p;
+  d.cval = g.ls_cval.p;
   return d;
 }
 StaticGroup MakeStatic(Group& g) {
@@ -568,6 +581,23 @@ hipError_t LaunchLinearTiledSchur(Group& g, const Arena& ar, hipStream_t st) {
   return hipGetLastError();
 }
 
+// The Schur complement of a group of linear blocks on the sparse route: the scalars (the tiled route's kernel), then
+// every column of every block from its nonzeros: one wavefront per column up to kLinSparseWaveCols variables, 256
+// threads per column and chunk of kLinSparseColChunk entries beyond.
+hipError_t LaunchLinearSparseSchur(Group& g, const Arena& ar, hipStream_t st) {
+  const LinSparseGroup d = MakeLinSparse(g);
+  const int cnt = d.t.v.count, m = d.t.v.m;
+  linear_tiled_scalars<<<cnt, kLinTiledBlock, 0, st>>>(d.t, ar);
+  if (m == 0) return hipGetLastError();
+  if (m <= kLinSparseWaveCols) {
+    linear_sparse_schur<kLinSparseWaveCols><<<(unsigned)((size_t)cnt * m), 64, 0, st>>>(d, ar, 1);
+  } else {
+    const int chunks = (m + kLinSparseColChunk - 1) / kLinSparseColChunk;
+    linear_sparse_schur<kLinSparseColChunk><<<(unsigned)((size_t)cnt * m * chunks), 256, 0, st>>>(d, ar, chunks);
+  }
+  return hipGetLastError();
+}
+
 // One pass over Q of a group of streamed quadratic cones: out_r = Q x_r for the R vectors of `x` (partials per
 // column split; QuadStreamQx adds them).  Nothing to do where Q is the identity.
 template <int R>
@@ -706,11 +736,11 @@ int LaunchSchur(cxk_context* ctx) {
         break;
       }
       case CXK_LINEAR:
-        if (g.tiled) {
+        if (g.tiled || g.lsparse) {
           hipEvent_t e0 = nullptr, e1 = nullptr;
           const bool sample = ClockSample(ctx, CXK_CLOCK_ASSEMBLY, &e0, &e1);
           if (sample) CXK_TRY(hipEventRecord(e0, ctx->stream));
-          CXK_TRY(LaunchLinearTiledSchur(g, ar, ctx->stream));
+          CXK_TRY(g.lsparse ? LaunchLinearSparseSchur(g, ar, ctx->stream) : LaunchLinearTiledSchur(g, ar, ctx->stream));
           if (sample) CXK_TRY(hipEventRecord(e1, ctx->stream));
         } else {
           linear_schur<<<count, 256, 0, ctx->stream>>>(MakeVec(g), ar);
@@ -760,6 +790,62 @@ int LaunchSchur(cxk_context* ctx) {
   return CXK_SUCCESS;
 }
 
+// The nonzeros (v != 0.0) of a dense-added linear block, by rows, columns ascending.
+static void LinearNonzeros(ConstraintRec* c) {
+  const size_t rows = (size_t)c->n;
+  c->sp_rowptr.assign(rows + 1, 0);
+  for (int j = 0; j < c->m; j++)
+    for (size_t r = 0; r < rows; r++) c->sp_rowptr[r + 1] += c->A[r + (size_t)j * rows] != 0.0;
+  for (size_t r = 0; r < rows; r++) c->sp_rowptr[r + 1] += c->sp_rowptr[r];
+  c->sp_col.resize((size_t)c->sp_rowptr[rows]);
+  c->sp_val.resize((size_t)c->sp_rowptr[rows]);
+  std::vector<int> next(c->sp_rowptr.begin(), c->sp_rowptr.end() - 1);
+  for (int j = 0; j < c->m; j++)
+    for (size_t r = 0; r < rows; r++) {
+      const double v = c->A[r + (size_t)j * rows];
+      if (v != 0.0) {
+        c->sp_col[(size_t)next[r]] = j;
+        c->sp_val[(size_t)next[r]++] = v;
+      }
+    }
+}
+
+// The device copy of a group of linear blocks on the sparse route: every member's nonzeros by rows and by columns.
+static int UploadSparseLinear(cxk_context* ctx, Group& g) {
+  const size_t cnt = g.ids.size(), rows = (size_t)g.n, m = (size_t)g.m;
+  size_t total = 0;
+  for (size_t k = 0; k < cnt; k++) total += ctx->cons[g.ids[k]].sp_col.size();
+  CXK_DEMAND(total <= (size_t)INT_MAX, "a group of sparse linear blocks with more than 2^31 nonzeros is not supported");
+  std::vector<int> eptr(cnt + 1, 0), rowptr(cnt * (rows + 1)), colptr(cnt * (m + 1), 0), col(total), crow(total);
+  std::vector<double> val(total), cval(total);
+  for (size_t k = 0; k < cnt; k++) {
+    const ConstraintRec& c = ctx->cons[g.ids[k]];
+    const size_t base = (size_t)eptr[k];
+    eptr[k + 1] = (int)(base + c.sp_col.size());
+    std::copy(c.sp_rowptr.begin(), c.sp_rowptr.end(), rowptr.begin() + k * (rows + 1));
+    std::copy(c.sp_col.begin(), c.sp_col.end(), col.begin() + base);
+    std::copy(c.sp_val.begin(), c.sp_val.end(), val.begin() + base);
+    int* cp = colptr.data() + k * (m + 1);
+    for (int v : c.sp_col) cp[v + 1]++;
+    for (size_t j = 0; j < m; j++) cp[j + 1] += cp[j];
+    std::vector<int> next(cp, cp + m);
+    for (size_t r = 0; r < rows; r++)  // (rows in order: every column's rows come out ascending)
+      for (int s = c.sp_rowptr[r]; s < c.sp_rowptr[r + 1]; s++) {
+        const size_t at = base + (size_t)next[(size_t)c.sp_col[(size_t)s]]++;
+        crow[at] = (int)r;
+        cval[at] = c.sp_val[(size_t)s];
+      }
+  }
+  CXK_TRY(g.ls_eptr.upload(eptr));
+  CXK_TRY(g.ls_rowptr.upload(rowptr));
+  CXK_TRY(g.ls_col.upload(col));
+  CXK_TRY(g.ls_val.upload(val));
+  CXK_TRY(g.ls_colptr.upload(colptr));
+  CXK_TRY(g.ls_crow.upload(crow));
+  CXK_TRY(g.ls_cval.upload(cval));
+  return CXK_SUCCESS;
+}
+
 // cxk_finalize, per-group stages.  Groups of identically shaped constraints (owned ones only carry data).
 int GroupConstraints(cxk_context* ctx, const FinalizeSwitches& sw) {
   const int K = (int)ctx->cons.size();
@@ -773,13 +859,45 @@ int GroupConstraints(cxk_context* ctx, const FinalizeSwitches& sw) {
   // quadratic cones: the LDS route's one workgroup per cone, or held in HBM (cxk_set_streamed_quadratic, else
   // CXK_STREAMED_QUADRATIC, else none)
   const int qstream_mode = ctx->streamed_quadratic != -2 ? ctx->streamed_quadratic : sw.streamed_quadratic;
+  // linear blocks evaluated from their nonzeros (cxk_set_sparse_linear, else CXK_SPARSE_LINEAR, else none); automatic
+  // mode yields to an explicit tiled mode, which asks for the dense kernels
+  const int lsparse_mode = ctx->sparse_linear != -2 ? ctx->sparse_linear : sw.sparse_linear;
   for (int i = 0; i < K; i++) {
     ConstraintRec& c = ctx->cons[i];
     c.streamed = false;
     c.tiled = false;
     c.qstream = false;
+    c.lsparse = false;
     if (!ctx->owned[i]) continue;
     if (c.type == CXK_LINEAR) {
+      CXK_DEMAND(!c.csr_only || lsparse_mode != 0,
+                 "a linear block added by cxk_add_linear_csr has no dense matrix and can only take the sparse route "
+                 "(cxk_set_sparse_linear / CXK_SPARSE_LINEAR, which is 0)");
+      bool countable = true;  // (the pointers are ints)
+      if (lsparse_mode != 0 && !c.csr_only && c.sp_rowptr.empty()) {
+        size_t nnz = 0;
+        for (double v : c.A) nnz += v != 0.0;
+        countable = nnz <= (size_t)INT_MAX;
+        CXK_DEMAND(countable || lsparse_mode != 1, "a sparse linear block with more than 2^31 nonzeros is not supported");
+        if (countable) LinearNonzeros(&c);
+      }
+      c.lsparse = c.csr_only || lsparse_mode == 1;
+      if (lsparse_mode == -1 && !c.csr_only && tiled_mode < 0 && countable) {
+        double sq = 0;
+        std::vector<int> per_col((size_t)c.m, 0);
+        for (int r = 0; r < c.n; r++) {
+          const double nz = c.sp_rowptr[(size_t)r + 1] - c.sp_rowptr[(size_t)r];
+          sq += nz * nz;
+        }
+        for (int v : c.sp_col) per_col[(size_t)v]++;
+        const int longest = c.m ? *std::max_element(per_col.begin(), per_col.end()) : 0;
+        c.lsparse = LinearSparsePays(c.n, c.m, sq, longest, sw.sparse_linear_min_ratio);
+      }
+    }
+    if (c.type == CXK_LINEAR && c.lsparse) {
+      CXK_DEMAND((int64_t)c.m * c.m <= INT_MAX,
+                 "a sparse linear block whose variables x variables Schur block exceeds the int range is not supported");
+    } else if (c.type == CXK_LINEAR) {
       c.tiled = tiled_mode >= 0 ? tiled_mode != 0
                                 : c.m > kLinearLdsMaxVars || (double)c.n * c.m * c.m >= (double)sw.tiled_linear_min_work;
       if (c.tiled) {
@@ -852,7 +970,7 @@ int GroupConstraints(cxk_context* ctx, const FinalizeSwitches& sw) {
                  "dimension + 1) is not supported");
     auto key = std::make_tuple(c.type, c.n, c.m, c.herm_d + (c.sparse ? 16 : 0) + (c.type == CXK_LMI && !c.symmetric ? 32 : 0) +
                                                      (c.type == CXK_QUAD && !c.Q.empty() ? 64 : 0) + (c.streamed ? 128 : 0) +
-                                                     (c.tiled ? 256 : 0) + (c.qstream ? 512 : 0));
+                                                     (c.tiled ? 256 : 0) + (c.qstream ? 512 : 0) + (c.lsparse ? 1024 : 0));
     auto it = gmap.find(key);
     if (it == gmap.end()) {
       it = gmap.emplace(key, (int)ctx->groups.size()).first;
@@ -867,6 +985,7 @@ int GroupConstraints(cxk_context* ctx, const FinalizeSwitches& sw) {
       ctx->groups.back().streamed = c.streamed;
       ctx->groups.back().tiled = c.tiled;
       ctx->groups.back().qstream = c.qstream;
+      ctx->groups.back().lsparse = c.lsparse;
     }
     c.group = it->second;
     c.member = (int)ctx->groups[it->second].ids.size();
@@ -919,6 +1038,10 @@ int UploadGroup(cxk_context* ctx, Group& g, const FinalizeSwitches& sw) {
   if (g.type == CXK_LMI && g.sparse) {
     if (UploadSparseLmi(ctx, g)) return CXK_FAILURE;
     a_sz = 0;  // no dense copy of A on the device
+  }
+  if (g.lsparse) {
+    if (UploadSparseLinear(ctx, g)) return CXK_FAILURE;
+    a_sz = 0;  // likewise
   }
   // lmi_schur_mfma reads [A_1 .. A_m | C] of a constraint as one contiguous array of stacked
   // rows: such groups keep a copy of C right behind the A_i (LmiGroup::a_stride)
@@ -1057,6 +1180,13 @@ int UploadGroup(cxk_context* ctx, Group& g, const FinalizeSwitches& sw) {
     CXK_TRY(g.ws_part.alloc(g.splits > 1 ? (size_t)g.splits * std::min<size_t>(cnt, 65535) * m * m : 0));
     CXK_TRY(g.lt_part.alloc(cnt * tiles * 4));
   }
+  if (g.lsparse) {
+    const size_t len = (size_t)g.n, m = (size_t)g.m, tiles = (len + kLinTiledRowTile - 1) / kLinTiledRowTile;
+    const size_t chunks = m <= (size_t)kLinSparseWaveCols ? 1 : (m + kLinSparseColChunk - 1) / kLinSparseColChunk;
+    CXK_DEMAND(cnt * std::max(m * chunks, tiles) <= (size_t)INT_MAX,
+               "a group of sparse linear blocks with more than 2^31 column chunks or row tiles is not supported");
+    CXK_TRY(g.lt_part.alloc(cnt * tiles * 4));
+  }
   if (g.schur_gemm) {
     const size_t nn = (size_t)g.n * g.n, m1 = (size_t)g.m + 1;
     // split-K of the contraction: enough workgroups to fill the chip, at most one K step each
@@ -1103,7 +1233,12 @@ int LaunchLinearLineSearch(cxk_context* ctx, double dinf_upper_bound, double c_s
   for (Group& g : ctx->groups) {
     const int cnt = (int)g.ids.size();
     if (cnt == 0 || g.type != CXK_LINEAR) continue;
-    if (g.tiled) {
+    if (g.lsparse) {
+      const LinSparseGroup d = MakeLinSparse(g);
+      const int tiles = (g.n + kLinTiledRowTile - 1) / kLinTiledRowTile;
+      linear_sparse_line_search<<<(unsigned)((size_t)cnt * tiles), kLinTiledBlock, 0, ctx->stream>>>(d, a, tiles);
+      linear_tiled_line_finish<<<cnt, kLinTiledBlock, 0, ctx->stream>>>(d.t, a, tiles);
+    } else if (g.tiled) {
       const LinTiledGroup d = MakeLinTiled(g);
       const int tiles = (g.n + kLinTiledRowTile - 1) / kLinTiledRowTile;
       linear_tiled_line_search<<<(unsigned)((size_t)cnt * tiles), kLinTiledBlock, 0, ctx->stream>>>(d, a, tiles);
@@ -1411,6 +1546,13 @@ int LaunchPrepareGroups(cxk_context* ctx, int pmode, const StepArgs& sa, const S
           lmi_prepare_generic<MODE, 0><<<cnt, 256, LmiPrepareLds(g.n, g.m), ctx->stream>>>(MakeLmi(g), sa);
           break;
       }
+    }
+    else if (g.type == CXK_LINEAR && g.lsparse) {
+      const LinSparseGroup d = MakeLinSparse(g);
+      const int tiles = (g.n + kLinTiledRowTile - 1) / kLinTiledRowTile;
+      linear_sparse_slack<MODE><<<(unsigned)((size_t)cnt * tiles), kLinTiledBlock, 0, ctx->stream>>>(d, sa, tiles);
+      if (MODE == 1 || !sa.affine)  // (the affine update has no reduction)
+        linear_tiled_finish<MODE><<<cnt, kLinTiledBlock, 0, ctx->stream>>>(d.t, sa, tiles);
     }
     else if (g.type == CXK_LINEAR && g.tiled) {
       const LinTiledGroup d = MakeLinTiled(g);

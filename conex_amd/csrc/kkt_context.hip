@@ -104,6 +104,8 @@ static FinalizeSwitches ReadFinalizeSwitches() {
   if ((v = getenv("CXK_TILED_LINEAR")) && v[0] != '\0') sw.tiled_linear = atoi(v) != 0;
   if ((v = getenv("CXK_STREAMED_QUADRATIC")) && v[0] != '\0') sw.streamed_quadratic = atoi(v) != 0;
   if ((v = getenv("CXK_STREAMED_QUADRATIC_MIN_WORK")) && v[0] != '\0') sw.streamed_quadratic_min_work = std::max(0ll, atoll(v));
+  if ((v = getenv("CXK_SPARSE_LINEAR")) && v[0] != '\0') sw.sparse_linear = atoi(v) != 0;
+  if ((v = getenv("CXK_SPARSE_LINEAR_MIN_RATIO")) && v[0] != '\0') sw.sparse_linear_min_ratio = std::max(0.0, atof(v));
   if ((v = getenv("CXK_TILED_LINEAR_MIN_WORK")) && v[0] != '\0') sw.tiled_linear_min_work = std::max(0ll, atoll(v));
   return sw;
 }
@@ -367,6 +369,46 @@ int cxk_add_linear(cxk_context* ctx, int rows, int m, const double* A, const dou
   return AddConstraint(ctx, std::move(r), vars);
 }
 
+int cxk_add_linear_csr(cxk_context* ctx, int rows, int m, const int* rowptr, const int* col, const double* val,
+                       const double* c, const int* vars) {
+  if (!ctx) return -1;
+  auto refuse = [ctx](const char* msg) {
+    ctx->err = msg;
+    return -1;
+  };
+  if (rows < 1 || m < 0) return refuse("cxk_add_linear_csr: rows is at least 1 and m at least 0");
+  if (!rowptr || !c) return refuse("cxk_add_linear_csr: rowptr or c is null");
+  if (rowptr[0] != 0) return refuse("cxk_add_linear_csr: rowptr[0] is not 0");
+  for (int r = 0; r < rows; r++)
+    if (rowptr[r + 1] < rowptr[r]) return refuse("cxk_add_linear_csr: rowptr decreases");
+  if (rowptr[rows] > 0 && (!col || !val)) return refuse("cxk_add_linear_csr: col or val is null");
+  ConstraintRec rec;
+  rec.type = CXK_LINEAR;
+  rec.n = rows;
+  rec.m = m;
+  rec.csr_only = true;
+  rec.C.assign(c, c + rows);
+  rec.sp_rowptr.assign((size_t)rows + 1, 0);
+  std::vector<std::pair<int, double>> row;
+  for (int r = 0; r < rows; r++) {
+    row.clear();
+    for (int s = rowptr[r]; s < rowptr[r + 1]; s++) {
+      if (col[s] < 0 || col[s] >= m) return refuse("cxk_add_linear_csr: a column is outside [0, m)");
+      row.emplace_back(col[s], val[s]);
+    }
+    std::sort(row.begin(), row.end(), [](const std::pair<int, double>& a, const std::pair<int, double>& b) { return a.first < b.first; });
+    for (size_t s = 1; s < row.size(); s++)
+      if (row[s].first == row[s - 1].first) return refuse("cxk_add_linear_csr: a row names a column twice");
+    for (const auto& e : row)
+      if (e.second != 0.0) {  // explicit zeros are dropped
+        rec.sp_col.push_back(e.first);
+        rec.sp_val.push_back(e.second);
+      }
+    rec.sp_rowptr[(size_t)r + 1] = (int)rec.sp_col.size();
+  }
+  return AddConstraint(ctx, std::move(rec), vars);
+}
+
 int cxk_add_soc(cxk_context* ctx, int n, int m, const double* A, const double* c, const int* vars) {
   if (!ctx || n < 1 || m < 0 || !A || !c) return -1;
   ConstraintRec r;
@@ -485,6 +527,20 @@ int cxk_count_tiled_linear(const cxk_context* ctx) {
   if (!ctx || !ctx->finalized) return -1;
   int k = 0;
   for (size_t i = 0; i < ctx->cons.size(); i++) k += ctx->owned[i] && ctx->cons[i].tiled;
+  return k;
+}
+
+int cxk_set_sparse_linear(cxk_context* ctx, int mode) {
+  if (!ctx) return CXK_FAILURE;
+  CXK_DEMAND(!ctx->finalized, "cxk_set_sparse_linear: the context is finalized (the choice is made by cxk_finalize)");
+  CXK_DEMAND(mode >= -1 && mode <= 1, "cxk_set_sparse_linear: the mode is -1 (automatic), 0 (never) or 1 (every linear block)");
+  ctx->sparse_linear = mode;
+  return CXK_SUCCESS;
+}
+int cxk_count_sparse_linear(const cxk_context* ctx) {
+  if (!ctx || !ctx->finalized) return -1;
+  int k = 0;
+  for (size_t i = 0; i < ctx->cons.size(); i++) k += ctx->owned[i] && ctx->cons[i].lsparse;
   return k;
 }
 

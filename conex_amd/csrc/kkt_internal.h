@@ -46,6 +46,12 @@ struct ConstraintRec {
   bool symmetric = true;
   bool tiled = false;  // linear block on the tiled route (kernels_linear_tiled.hip.h)
   bool qstream = false;  // quadratic cone held in HBM (kernels_quad_stream.hip.h); `streamed` stays the second-order cone's
+  // linear block: its nonzeros by rows, columns ascending (cxk_add_linear_csr gives them and leaves A empty: such a
+  // block can only take the sparse route; GroupConstraints reads them off the A of a dense-added block)
+  bool lsparse = false;   // linear block on the sparse route (kernels_linear_sparse.hip.h)
+  bool csr_only = false;  // added by cxk_add_linear_csr: no dense A
+  std::vector<int> sp_rowptr, sp_col;
+  std::vector<double> sp_val;
 };
 
 template <typename T>
@@ -132,6 +138,12 @@ struct Group {
   // partials of the products with Q in ws_part (`splits` column splits), every vector and scalar of the work space
   // in st_vec (MakeQuadStream lays it out)
   bool qstream = false;
+  // linear blocks on the sparse route (cxk_set_sparse_linear): the kernels of kernels_linear_sparse.hip.h; every
+  // member's nonzeros by rows (ls_col, ls_val) and by columns (ls_crow, ls_cval) from ls_eptr[member] on, the
+  // pointers of its rows and columns relative to that; four doubles per row tile in lt_part.  No dense A.
+  bool lsparse = false;
+  DevBuf<int> ls_eptr, ls_rowptr, ls_col, ls_colptr, ls_crow;
+  DevBuf<double> ls_val, ls_cval;
 };
 
 
@@ -167,6 +179,8 @@ struct cxk_context {
   // cxk_set_streamed_quadratic: -2 the environment's CXK_STREAMED_QUADRATIC (else never), -1 by size, 0 never, 1 every cone
   int streamed_quadratic = -2;
   int tiled_linear = -1;    // cxk_set_tiled_linear: -1 the environment's CXK_TILED_LINEAR (else by size), 0 never, 1 every block
+  // cxk_set_sparse_linear: -2 the environment's CXK_SPARSE_LINEAR (else never), -1 by pattern, 0 never, 1 every block
+  int sparse_linear = -2;
   std::vector<Group> groups;
   std::vector<int64_t> g_off, r_off;
   std::vector<unsigned char> owned;      // constraint i assembled/updated by this rank

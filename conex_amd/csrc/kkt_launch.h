@@ -64,6 +64,25 @@ constexpr int kLinearLdsMaxVars = 4096;
 // but the two-launch PrepareStep and query cost 2 us more); twice, because the numbers are one box's on one day.
 constexpr long long kTiledLinearMinWork = 2ll * 2000 * 64 * 64;  // 16 384 000
 
+// Automatic mode (cxk_set_sparse_linear(ctx, -1)) sends a linear block to the sparse route when
+// R sum_r nnz_r^2 <= rows m^2: the sparse assembly forms about sum_r nnz_r^2 products one fma at a time, the dense
+// routes rows m^2 on the matrix pipe.  Measured (tools/linear_sparse_speed.py against the build before the sparse
+// route on its own choice): R is twice the smallest rows m^2 / sum_r nnz_r^2 among the measured
+// shapes at which assembly, PrepareStep and the eigenvalue query are each faster on the sparse route, 3.9 at the
+// half-full 2000 x 64; twice, because the numbers are one box's on one day.  A fully dense block (ratio 1) never moves.
+// CXK_SPARSE_LINEAR_MIN_RATIO moves R for comparison runs.  Two more conditions, both from shapes that lost:
+//  - a column's rows are one wavefront's dependent chain, 0.33 us per row (100 000 x 50 with one full column: 32.6 ms
+//    against 0.38 ms): no column longer than kSparseLinearMaxColumn, twice the longest measured to win (about 1050);
+//  - a thousand 20 x 10 blocks with 3 nonzeros per row are 20 % slower at every stage than on the LDS route's one
+//    launch per stage: nothing below the rows m^2 of the smallest measured shape that won, 2000 x 64, moves.
+constexpr double kSparseLinearMinRatio = 7.8;
+constexpr int kSparseLinearMaxColumn = 2048;
+constexpr long long kSparseLinearMinWork = 2000ll * 64 * 64;  // 8 192 000
+inline bool LinearSparsePays(double rows, double m, double sum_nnz_sq, int longest_column, double ratio) {
+  return ratio * sum_nnz_sq <= rows * m * m && rows * m * m >= (double)kSparseLinearMinWork &&
+         longest_column <= kSparseLinearMaxColumn;
+}
+
 // Automatic mode (cxk_set_streamed_quadratic(ctx, -1)) sends a quadratic cone to the streamed route from this many
 // doubles streamed per pass, (Q ? n n : 0) + (n + 1) m, on.  Measured (tools/quad_stream_speed.py):
 // the smallest shape of the sweep, n = 32 with Q over m = 8 (32 * 32 + 33 * 8), where assembly + PrepareStep +
@@ -87,6 +106,8 @@ struct FinalizeSwitches {
   long long tiled_linear_min_work = kTiledLinearMinWork;  // CXK_TILED_LINEAR_MIN_WORK (comparison runs)
   int streamed_quadratic = 0;   // CXK_STREAMED_QUADRATIC=0 / 1: quadratic cones never / always held in HBM (cxk_set_streamed_quadratic)
   long long streamed_quadratic_min_work = kQuadStreamMinWork;  // CXK_STREAMED_QUADRATIC_MIN_WORK (comparison runs)
+  int sparse_linear = 0;        // CXK_SPARSE_LINEAR=0 / 1: linear blocks never / always on the sparse route (cxk_set_sparse_linear)
+  double sparse_linear_min_ratio = kSparseLinearMinRatio;  // CXK_SPARSE_LINEAR_MIN_RATIO (comparison runs)
 };
 
 // ---- kkt_context.hip

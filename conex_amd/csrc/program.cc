@@ -79,6 +79,7 @@ struct Program {
   int reference_identity = -1;  // -1: environment (CXK_REFERENCE_QUIRKS); see CONEX_HIP_SetReferenceIdentity
   int streamed_cones = 1;       // second-order cones beyond LDS run from HBM; see CONEX_HIP_SetStreamedCones
   int tiled_linear = -1;        // linear blocks on the tiled kernels: -1 by size; see CONEX_HIP_SetTiledLinear
+  int sparse_linear = -1;       // linear blocks from their nonzeros: -1 by pattern; see CONEX_HIP_SetSparseLinear
   int streamed_quadratic = -1;  // quadratic cones held in HBM: -1 beyond LDS or by size; see CONEX_HIP_SetStreamedQuadratic
   // multi-GPU (one process per GPU, every rank builds the same program): see CONEX_HIP_SetCommunicator
   int shard_rank = 0, shard_world = 1;
@@ -151,6 +152,8 @@ int BuildContext(Program* p) {
   // as the program): none is refused for its size here either
   cxk_set_streamed_cones(p->ctx, p->streamed_cones);
   if (p->tiled_linear >= 0) cxk_set_tiled_linear(p->ctx, p->tiled_linear);
+  // (automatic, where the cxk_* interface defaults to never: bounds and polytopic rows are almost empty)
+  cxk_set_sparse_linear(p->ctx, p->sparse_linear);
   // (likewise no quadratic cone is refused for its size: automatic, where the cxk_* interface defaults to never)
   cxk_set_streamed_quadratic(p->ctx, p->streamed_quadratic);
   if (p->shard_world > 1) {
@@ -1318,6 +1321,17 @@ int CONEX_HIP_SetTiledLinear(void* x, int mode) {
   Program* p = static_cast<Program*>(x);
   if (!p || mode < -1 || mode > 1) return CONEX_FAILURE;
   p->tiled_linear = mode;
+  p->dirty = true;
+  return CONEX_SUCCESS;
+}
+
+/* not part of conex.h: which linear-inequality blocks are evaluated from their nonzeros (conex_kkt_hip.h,
+ * cxk_set_sparse_linear): -1 (the default) those whose pattern makes it pay, unless CONEX_HIP_SetTiledLinear made an
+ * explicit choice; 0 none; 1 every block */
+int CONEX_HIP_SetSparseLinear(void* x, int mode) {
+  Program* p = static_cast<Program*>(x);
+  if (!p || mode < -1 || mode > 1) return CONEX_FAILURE;
+  p->sparse_linear = mode;
   p->dirty = true;
   return CONEX_SUCCESS;
 }

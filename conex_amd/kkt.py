@@ -132,6 +132,9 @@ _SIGNATURES = {
     "cxk_set_streamed_quadratic": (C.c_int, [C.c_void_p, C.c_int]),
     "cxk_count_streamed_quadratic": (C.c_int, [C.c_void_p]),
     "cxk_set_tiled_linear": (C.c_int, [C.c_void_p, C.c_int]),
+    "cxk_set_sparse_linear": (C.c_int, [C.c_void_p, C.c_int]),
+    "cxk_count_sparse_linear": (C.c_int, [C.c_void_p]),
+    "cxk_add_linear_csr": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_int_p, c_int_p, c_double_p, c_double_p, c_int_p]),
     "cxk_count_tiled_linear": (C.c_int, [C.c_void_p]),
     "cxk_fused_tree_timed_out": (C.c_int, [C.c_void_p]),
     "cxk_debug_force_fused_timeout": (C.c_int, [C.c_void_p]),
@@ -239,6 +242,23 @@ class KktContext:
         cc = np.ascontiguousarray(np.asarray(c, dtype=np.float64).ravel())
         keep, vp = self._vars(vars_)
         r = self.L.cxk_add_linear(self.h, rows, m, _dp(a), _dp(cc), vp)
+        if r >= 0:
+            self.cons.append(("linear", rows, m))
+        return r
+
+    def add_linear_csr(self, rowptr, col, val, c, vars_=None):
+        """The constraint of add_linear by its nonzeros: row r holds col / val [rowptr[r]:rowptr[r + 1]], columns in any
+        order.  The number of variables is len(vars_), or the context's.  Such a block takes the sparse route only."""
+        rp = np.ascontiguousarray(rowptr, dtype=np.int32)
+        cl = np.ascontiguousarray(col, dtype=np.int32)
+        vl = np.ascontiguousarray(val, dtype=np.float64)
+        cc = np.ascontiguousarray(np.asarray(c, dtype=np.float64).ravel())
+        rows = len(cc)
+        if len(rp) != rows + 1 or len(cl) != len(vl) or (len(rp) and rp[-1] > len(cl)):
+            raise ValueError("add_linear_csr: rowptr has len(c) + 1 entries and points into col / val of equal length")
+        keep, vp = self._vars(vars_)
+        m = self.num_vars if vars_ is None else len(keep)
+        r = self.L.cxk_add_linear_csr(self.h, rows, m, _ip(rp), _ip(cl), _dp(vl), _dp(cc), vp)
         if r >= 0:
             self.cons.append(("linear", rows, m))
         return r
@@ -785,6 +805,15 @@ class KktContext:
     def count_tiled_linear(self):
         """Constraints this context owns that run on the tiled linear kernels."""
         return self.L.cxk_count_tiled_linear(self.h)
+
+    def set_sparse_linear(self, mode=1):
+        """Linear blocks evaluated from their nonzeros: 1 every block, 0 none, -1 those whose pattern makes it pay
+        (before initialize; default: CXK_SPARSE_LINEAR in the environment, else 0)."""
+        self._check(self.L.cxk_set_sparse_linear(self.h, int(mode)), "cxk_set_sparse_linear")
+
+    def count_sparse_linear(self):
+        """Constraints this context owns that run on the sparse linear kernels."""
+        return self.L.cxk_count_sparse_linear(self.h)
 
     def fused_tree_timed_out(self):
         return bool(self.L.cxk_fused_tree_timed_out(self.h))

@@ -153,6 +153,33 @@ int cxk_count_streamed_cones(const cxk_context* ctx);
 int cxk_set_tiled_linear(cxk_context* ctx, int mode);
 int cxk_count_tiled_linear(const cxk_context* ctx);
 
+/* Linear-inequality blocks evaluated from their nonzeros.  The LDS and the tiled route multiply a block as a dense
+ * rows x variables matrix; bounds lb <= y <= ub, or the polytopic rows of an LP, QP or MPC problem, are almost
+ * empty.  The sparse route (kernels_linear_sparse.hip.h) holds a block on the device by rows and by columns (CSR
+ * and CSC) and never uploads its dense matrix: the assembly costs about sum_r nnz_r^2 multiply-adds and one write of
+ * the variables x variables square, the slack passes nnz multiply-adds.  No atomics, fixed summation orders: two runs
+ * give the same bits, and the per-row slack, W after a step, norminfd, normsqrd and the eigenvalue query are the tiled
+ * route's bit for bit.  G comes out exactly symmetric.  Every output, getter and setter is that of any linear block.
+ * cxk_set_sparse_linear, before cxk_finalize: mode 1 every linear block takes the sparse route; 0 none does; -1 a
+ * block does when kSparseLinearMinRatio x sum_r nnz_r^2 <= rows x variables^2, rows x variables^2 is at least
+ * kSparseLinearMinWork and no column has more than kSparseLinearMaxColumn rows (kkt_launch.h: 7.8, 8 192 000, 2048,
+ * measured; CXK_SPARSE_LINEAR_MIN_RATIO moves the ratio for comparison runs) and neither cxk_set_tiled_linear
+ * nor CXK_TILED_LINEAR made an explicit choice, which is a request for the dense kernels.  Without a call: the
+ * environment's CXK_SPARSE_LINEAR = 0 | 1, else 0.  A sparse block may have more than 4096 variables whatever the
+ * tiled mode.  Refused on the sparse route at cxk_finalize, by name: variables^2 beyond the int range; a group of
+ * equal-shaped blocks with more than 2^31 nonzeros, column chunks or row tiles.
+ * cxk_count_sparse_linear: constraints this context owns on the sparse route (-1 before cxk_finalize; 0 on a
+ * host-only context); cxk_count_tiled_linear does not count them.
+ * cxk_add_linear_csr: the constraint of cxk_add_linear given by its nonzeros, rowptr[r] .. rowptr[r + 1] being row
+ * r's entries of col / val.  Columns within a row come in any order (the library sorts them); explicit zeros are
+ * dropped.  Returns -1 (cxk_last_error names the reason) for rowptr[0] != 0, a decreasing rowptr, a column outside
+ * [0, m), a column named twice in a row, null pointers.  Such a block can only take the sparse route: cxk_finalize
+ * refuses it by name when the mode in force is 0.  A block added by cxk_add_linear may take any of the three routes. */
+int cxk_set_sparse_linear(cxk_context* ctx, int mode);
+int cxk_count_sparse_linear(const cxk_context* ctx);
+int cxk_add_linear_csr(cxk_context* ctx, int rows, int m, const int* rowptr /* rows + 1 */, const int* col,
+                       const double* val, const double* c /* rows */, const int* vars);
+
 /* Quadratic cones { x0 >= sqrt(x1' Q x1) } of real size.  The LDS route (quad_schur, quad_prepare, quad_take_step)
  * gives a cone one workgroup and runs its maps, the products with Q among them, on one thread; a cone whose
  * variables + 4 (dimension + 1) doubles exceed LDS is refused at cxk_finalize.  The streamed route
