@@ -73,6 +73,8 @@ def api():
         "CONEX_HIP_SetStreamedCones": (ci, [vp, ci]),
         "CONEX_HIP_SetTiledLinear": (ci, [vp, ci]),
         "CONEX_HIP_SetSparseLinear": (ci, [vp, ci]),
+        "CONEX_HIP_SetSparseSoc": (ci, [vp, ci]),
+        "CONEX_HIP_CountSparseSoc": (ci, [vp]),
         "CONEX_HIP_SetStreamedQuadratic": (ci, [vp, ci]),
         # the block solve of the cxk_* layer (include/conex_kkt_hip.h), as conex_amd.kkt declares it
         "cxk_solve_block": (ci, [vp, c_double_p, ci, ci]),

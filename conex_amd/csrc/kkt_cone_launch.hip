@@ -16,6 +16,7 @@
 #include "kernels_soc_stream.hip.h"
 #include "kernels_linear_tiled.hip.h"
 #include "kernels_linear_sparse.hip.h"
+#include "kernels_soc_sparse.hip.h"
 #include "kernels_quad_stream.hip.h"
 
 namespace cxk_host {
@@ -150,6 +151,30 @@ LinSparseGroup MakeLinSparse(Group& g) {
   d.cval = g.ls_cval.p;
   return d;
 }
+SocSparseGroup MakeSocSparse(Group& g) {
+  SocSparseGroup d{};
+  const size_t cnt = g.ids.size(), len = (size_t)g.n + 1, m = (size_t)g.m;
+  d.st.v = MakeVec(g);  // (A is null; WA, wc, dets and Gf stay null: the step kernels read v, s and ms only)
+  double* p = g.st_vec.p;  // (the layouts UploadGroup sizes: SocSparseVecDoubles, SocSparseConstDoubles)
+  d.st.s = p;
+  d.st.ms = (p += cnt * len);
+  d.u = (p += cnt * len);
+  d.scal = (p += cnt * m);
+  p = g.ss_const.p;
+  d.H = p;
+  d.h = (p += cnt * m * m);
+  d.z = (p += cnt * m);
+  d.eptr = g.ls_eptr.p;
+  d.rowptr = g.ls_rowptr.p;
+  d.col = g.ls_col.p;
+  d.val = g.ls_val.p;
+  d.colptr = g.ls_colptr.p;
+  d.crow = g.ls_crow.p;
+  d.cval = g.ls_cval.p;
+  return d;
+}
+size_t SocSparseVecDoubles(size_t cnt, size_t len, size_t m) { return cnt * (2 * len + m + 2); }
+size_t SocSparseConstDoubles(size_t cnt, size_t m) { return cnt * (m * m + m + 1); }
 StaticGroup MakeStatic(Group& g) {
   StaticGroup d;
   d.m = g.m;
@@ -598,6 +623,57 @@ hipError_t LaunchLinearSparseSchur(Group& g, const Arena& ar, hipStream_t st) {
   return hipGetLastError();
 }
 
+// Launch shapes of a group of sparse second-order cones: chunks of a column of H, tiles of the combine kernel.
+static int SocSparseGramChunks(int m) { return m <= kSocSparseWaveCols ? 1 : (m + kSocSparseColChunk - 1) / kSocSparseColChunk; }
+static int SocSparseCombineTiles(int m) { return (int)(((size_t)m * m + kSocSparseCombineTile - 1) / kSocSparseCombineTile); }
+
+// The Schur complement of a group of second-order cones on the sparse route: det(w), w . c and the scalars, the
+// column dots u = A' w with AW and AQc, then G = 4 u u' + 2 det(w) H.  Stream order is the only dependency.
+hipError_t LaunchSocSparseSchur(Group& g, const Arena& ar, hipStream_t st) {
+  const SocSparseGroup d = MakeSocSparse(g);
+  const int cnt = d.st.v.count, m = d.st.v.m;
+  soc_sparse_vectors<<<cnt, kSocSparseBlock, 0, st>>>(d, ar);
+  if (m == 0) return hipGetLastError();
+  constexpr int per = kSocSparseBlock / 64;  // columns per workgroup
+  soc_sparse_dots<<<(unsigned)(((size_t)cnt * m + per - 1) / per), kSocSparseBlock, 0, st>>>(d, ar);
+  const int tiles = SocSparseCombineTiles(m);
+  soc_sparse_combine<<<(unsigned)((size_t)cnt * tiles), kSocSparseBlock, 0, st>>>(d, ar, tiles);
+  return hipGetLastError();
+}
+
+// The constants of a group of sparse second-order cones, once at cxk_finalize, on the device: z = c' J c, then
+// H = A' J A and h = A' J c column by column: one wavefront per column up to kSocSparseWaveCols variables, 256 threads
+// per column and chunk of kSocSparseColChunk entries beyond.
+// The launches carry a hipEvent pair: cxk_sparse_soc_setup_ms reports what this one-off step cost.
+int SocSparseConstants(cxk_context* ctx, Group& g) {
+  const SocSparseGroup d = MakeSocSparse(g);
+  const int cnt = d.st.v.count, m = d.st.v.m;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  CXK_TRY(hipEventCreate(&e0));
+  if (hipEventCreate(&e1) != hipSuccess) {
+    (void)hipEventDestroy(e0);
+    CXK_DEMAND(false, "hipEventCreate failed");
+  }
+  hipError_t err = hipEventRecord(e0, ctx->stream);
+  soc_sparse_cjc<<<cnt, kSocSparseBlock, 0, ctx->stream>>>(d);
+  if (m > 0 && m <= kSocSparseWaveCols) {
+    soc_sparse_gram<kSocSparseWaveCols><<<(unsigned)((size_t)cnt * m), 64, 0, ctx->stream>>>(d, 1);
+  } else if (m > 0) {
+    const int chunks = SocSparseGramChunks(m);
+    soc_sparse_gram<kSocSparseColChunk><<<(unsigned)((size_t)cnt * m * chunks), 256, 0, ctx->stream>>>(d, chunks);
+  }
+  if (err == hipSuccess) err = hipGetLastError();
+  if (err == hipSuccess) err = hipEventRecord(e1, ctx->stream);
+  if (err == hipSuccess) err = hipEventSynchronize(e1);
+  float ms = 0;
+  if (err == hipSuccess) err = hipEventElapsedTime(&ms, e0, e1);
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  CXK_TRY(err);
+  ctx->sparse_soc_setup_ms += ms;
+  return CXK_SUCCESS;
+}
+
 // One pass over Q of a group of streamed quadratic cones: out_r = Q x_r for the R vectors of `x` (partials per
 // column split; QuadStreamQx adds them).  Nothing to do where Q is the identity.
 template <int R>
@@ -747,11 +823,11 @@ int LaunchSchur(cxk_context* ctx) {
         }
         break;
       case CXK_SOC:
-      if (g.streamed) {
+      if (g.streamed || g.ssparse) {
         hipEvent_t e0 = nullptr, e1 = nullptr;
         const bool sample = ClockSample(ctx, CXK_CLOCK_ASSEMBLY, &e0, &e1);
         if (sample) CXK_TRY(hipEventRecord(e0, ctx->stream));
-        CXK_TRY(LaunchSocStreamSchur(g, ar, ctx->stream));
+        CXK_TRY(g.ssparse ? LaunchSocSparseSchur(g, ar, ctx->stream) : LaunchSocStreamSchur(g, ar, ctx->stream));
         if (sample) CXK_TRY(hipEventRecord(e1, ctx->stream));
       } else {
         // one wavefront per cone, up to four cones per workgroup; the cone's data staged in LDS when
@@ -790,9 +866,10 @@ int LaunchSchur(cxk_context* ctx) {
   return CXK_SUCCESS;
 }
 
-// The nonzeros (v != 0.0) of a dense-added linear block, by rows, columns ascending.
+// The nonzeros (v != 0.0) of a dense-added linear block (rows = n) or second-order cone (rows = n + 1), by rows,
+// columns ascending.
 static void LinearNonzeros(ConstraintRec* c) {
-  const size_t rows = (size_t)c->n;
+  const size_t rows = (size_t)c->n + (c->type == CXK_SOC ? 1 : 0);
   c->sp_rowptr.assign(rows + 1, 0);
   for (int j = 0; j < c->m; j++)
     for (size_t r = 0; r < rows; r++) c->sp_rowptr[r + 1] += c->A[r + (size_t)j * rows] != 0.0;
@@ -810,12 +887,15 @@ static void LinearNonzeros(ConstraintRec* c) {
     }
 }
 
-// The device copy of a group of linear blocks on the sparse route: every member's nonzeros by rows and by columns.
+// The device copy of a group of linear blocks (rows = n) or second-order cones (rows = n + 1) on the sparse route:
+// every member's nonzeros by rows and by columns.
 static int UploadSparseLinear(cxk_context* ctx, Group& g) {
-  const size_t cnt = g.ids.size(), rows = (size_t)g.n, m = (size_t)g.m;
+  const size_t cnt = g.ids.size(), rows = (size_t)g.n + (g.type == CXK_SOC ? 1 : 0), m = (size_t)g.m;
   size_t total = 0;
   for (size_t k = 0; k < cnt; k++) total += ctx->cons[g.ids[k]].sp_col.size();
-  CXK_DEMAND(total <= (size_t)INT_MAX, "a group of sparse linear blocks with more than 2^31 nonzeros is not supported");
+  CXK_DEMAND(total <= (size_t)INT_MAX, g.type == CXK_SOC
+                                           ? "a group of sparse second-order cones with more than 2^31 nonzeros is not supported"
+                                           : "a group of sparse linear blocks with more than 2^31 nonzeros is not supported");
   std::vector<int> eptr(cnt + 1, 0), rowptr(cnt * (rows + 1)), colptr(cnt * (m + 1), 0), col(total), crow(total);
   std::vector<double> val(total), cval(total);
   for (size_t k = 0; k < cnt; k++) {
@@ -862,12 +942,16 @@ int GroupConstraints(cxk_context* ctx, const FinalizeSwitches& sw) {
   // linear blocks evaluated from their nonzeros (cxk_set_sparse_linear, else CXK_SPARSE_LINEAR, else none); automatic
   // mode yields to an explicit tiled mode, which asks for the dense kernels
   const int lsparse_mode = ctx->sparse_linear != -2 ? ctx->sparse_linear : sw.sparse_linear;
+  // second-order cones evaluated from their nonzeros (cxk_set_sparse_soc, else CXK_SPARSE_SOC, else none)
+  const int ssparse_mode = ctx->sparse_soc != -2 ? ctx->sparse_soc : sw.sparse_soc;
+  ctx->sparse_soc_setup_ms = 0;
   for (int i = 0; i < K; i++) {
     ConstraintRec& c = ctx->cons[i];
     c.streamed = false;
     c.tiled = false;
     c.qstream = false;
     c.lsparse = false;
+    c.ssparse = false;
     if (!ctx->owned[i]) continue;
     if (c.type == CXK_LINEAR) {
       CXK_DEMAND(!c.csr_only || lsparse_mode != 0,
@@ -930,10 +1014,33 @@ int GroupConstraints(cxk_context* ctx, const FinalizeSwitches& sw) {
       }
     }
     if (c.type == CXK_SOC) {
+      CXK_DEMAND(!c.csr_only || ssparse_mode != 0,
+                 "a second-order cone added by cxk_add_soc_csr has no dense matrix and can only take the sparse route "
+                 "(cxk_set_sparse_soc / CXK_SPARSE_SOC, which is 0)");
+      // (a dense route indexes the (n + 1) x m entries with ints)
+      const bool dense_ok = (int64_t)(c.n + 1) * std::max(c.m, 1) <= INT_MAX - 1024;
+      bool countable = true;  // (the pointers are ints)
+      if (ssparse_mode != 0 && !c.csr_only && c.sp_rowptr.empty()) {
+        size_t nnz = 0;
+        for (double v : c.A) nnz += v != 0.0;
+        countable = nnz <= (size_t)INT_MAX;
+        CXK_DEMAND(countable || ssparse_mode != 1, "a sparse second-order cone with more than 2^31 nonzeros is not supported");
+        if (countable) LinearNonzeros(&c);
+      }
+      c.ssparse = c.csr_only || ssparse_mode == 1;
+      if (ssparse_mode == -1 && !c.csr_only && countable)
+        c.ssparse = !dense_ok || SocSparsePays((double)c.n + 1, c.m, (double)c.sp_col.size(), sw.sparse_soc_min_ratio);
+    }
+    if (c.type == CXK_SOC && !c.ssparse) {
       c.streamed = stream_on && !(SocSchurLds(c.n, c.m, false) <= kLdsLimit && SocTakeLds(c.n) <= kLdsLimit &&
                                   SocPrepareLds(c.n, c.m) <= kLdsLimit);
     }
-    if (c.type == CXK_SOC && c.streamed) {
+    if (c.type == CXK_SOC && c.ssparse) {
+      // held as nonzeros (kernels_soc_sparse.hip.h): no LDS room, no streamed switch; what remains is the int indexing
+      // of the m x m squares H and G
+      CXK_DEMAND((int64_t)c.m * c.m <= INT_MAX,
+                 "a sparse second-order cone whose variables x variables Schur block exceeds the int range is not supported");
+    } else if (c.type == CXK_SOC && c.streamed) {
       // held in HBM (kernels_soc_stream.hip.h): what remains is the int indexing of the kernels and of the GEMM
       CXK_DEMAND((int64_t)(c.n + 1) * std::max(c.m, 1) <= INT_MAX - 1024,
                  "a streamed second-order cone whose (dimension + 1) x variables entries exceed the int range is not supported");
@@ -970,7 +1077,7 @@ int GroupConstraints(cxk_context* ctx, const FinalizeSwitches& sw) {
                  "dimension + 1) is not supported");
     auto key = std::make_tuple(c.type, c.n, c.m, c.herm_d + (c.sparse ? 16 : 0) + (c.type == CXK_LMI && !c.symmetric ? 32 : 0) +
                                                      (c.type == CXK_QUAD && !c.Q.empty() ? 64 : 0) + (c.streamed ? 128 : 0) +
-                                                     (c.tiled ? 256 : 0) + (c.qstream ? 512 : 0) + (c.lsparse ? 1024 : 0));
+                                                     (c.tiled ? 256 : 0) + (c.qstream ? 512 : 0) + (c.lsparse ? 1024 : 0) + (c.ssparse ? 2048 : 0));
     auto it = gmap.find(key);
     if (it == gmap.end()) {
       it = gmap.emplace(key, (int)ctx->groups.size()).first;
@@ -986,6 +1093,7 @@ int GroupConstraints(cxk_context* ctx, const FinalizeSwitches& sw) {
       ctx->groups.back().tiled = c.tiled;
       ctx->groups.back().qstream = c.qstream;
       ctx->groups.back().lsparse = c.lsparse;
+      ctx->groups.back().ssparse = c.ssparse;
     }
     c.group = it->second;
     c.member = (int)ctx->groups[it->second].ids.size();
@@ -1039,7 +1147,7 @@ int UploadGroup(cxk_context* ctx, Group& g, const FinalizeSwitches& sw) {
     if (UploadSparseLmi(ctx, g)) return CXK_FAILURE;
     a_sz = 0;  // no dense copy of A on the device
   }
-  if (g.lsparse) {
+  if (g.lsparse || g.ssparse) {
     if (UploadSparseLinear(ctx, g)) return CXK_FAILURE;
     a_sz = 0;  // likewise
   }
@@ -1186,6 +1294,16 @@ int UploadGroup(cxk_context* ctx, Group& g, const FinalizeSwitches& sw) {
     CXK_DEMAND(cnt * std::max(m * chunks, tiles) <= (size_t)INT_MAX,
                "a group of sparse linear blocks with more than 2^31 column chunks or row tiles is not supported");
     CXK_TRY(g.lt_part.alloc(cnt * tiles * 4));
+  }
+  if (g.ssparse) {
+    const size_t len = (size_t)g.n + 1, m = (size_t)g.m, tiles = (len + kSocStreamRowTile - 1) / kSocStreamRowTile;
+    CXK_DEMAND(cnt * std::max(std::max(m * (size_t)SocSparseGramChunks(g.m), tiles), (size_t)SocSparseCombineTiles(g.m)) <=
+                   (size_t)INT_MAX,
+               "a group of sparse second-order cones with more than 2^31 column chunks, row tiles or tiles of the Schur "
+               "block is not supported");
+    CXK_TRY(g.st_vec.alloc(SocSparseVecDoubles(cnt, len, m)));
+    CXK_TRY(g.ss_const.alloc(SocSparseConstDoubles(cnt, m)));
+    if (SocSparseConstants(ctx, g)) return CXK_FAILURE;
   }
   if (g.schur_gemm) {
     const size_t nn = (size_t)g.n * g.n, m1 = (size_t)g.m + 1;
@@ -1563,6 +1681,12 @@ int LaunchPrepareGroups(cxk_context* ctx, int pmode, const StepArgs& sa, const S
     }
     else if (g.type == CXK_LINEAR)
       linear_prepare<MODE><<<cnt, 256, sizeof(double) * g.m, ctx->stream>>>(MakeVec(g), sa);
+    else if (g.type == CXK_SOC && g.ssparse) {
+      const SocSparseGroup d = MakeSocSparse(g);
+      const int tiles = (g.n + 1 + kSocStreamRowTile - 1) / kSocStreamRowTile;
+      soc_sparse_slack<<<(unsigned)((size_t)cnt * tiles), kSocStreamBlock, 0, ctx->stream>>>(d, sa, tiles);
+      soc_stream_prepare<MODE><<<cnt, kSocStreamBlock, 0, ctx->stream>>>(d.st, sa);
+    }
     else if (g.type == CXK_SOC && g.streamed) {
       const SocStreamGroup d = MakeSocStream(g);
       const int tiles = (g.n + 1 + kSocStreamRowTile - 1) / kSocStreamRowTile;
@@ -1701,6 +1825,8 @@ int LaunchTakeStep(cxk_context* ctx, double e_weight, double step_size, const do
     }
     else if (g.type == CXK_LINEAR)
       linear_take_step<<<GridFor((size_t)cnt * g.n, 256), 256, 0, ctx->stream>>>(MakeVec(g), sa);
+    else if (g.type == CXK_SOC && g.ssparse)
+      soc_stream_take_step<<<cnt, kSocStreamBlock, 0, ctx->stream>>>(MakeSocSparse(g).st, sa);
     else if (g.type == CXK_SOC && g.streamed)
       soc_stream_take_step<<<cnt, kSocStreamBlock, 0, ctx->stream>>>(MakeSocStream(g), sa);
     else if (g.type == CXK_SOC)

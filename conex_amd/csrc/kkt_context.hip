@@ -107,6 +107,8 @@ static FinalizeSwitches ReadFinalizeSwitches() {
   if ((v = getenv("CXK_SPARSE_LINEAR")) && v[0] != '\0') sw.sparse_linear = atoi(v) != 0;
   if ((v = getenv("CXK_SPARSE_LINEAR_MIN_RATIO")) && v[0] != '\0') sw.sparse_linear_min_ratio = std::max(0.0, atof(v));
   if ((v = getenv("CXK_TILED_LINEAR_MIN_WORK")) && v[0] != '\0') sw.tiled_linear_min_work = std::max(0ll, atoll(v));
+  if ((v = getenv("CXK_SPARSE_SOC")) && v[0] != '\0') sw.sparse_soc = atoi(v) != 0;
+  if ((v = getenv("CXK_SPARSE_SOC_MIN_RATIO")) && v[0] != '\0') sw.sparse_soc_min_ratio = std::max(0.0, atof(v));
   return sw;
 }
 
@@ -369,22 +371,24 @@ int cxk_add_linear(cxk_context* ctx, int rows, int m, const double* A, const dou
   return AddConstraint(ctx, std::move(r), vars);
 }
 
-int cxk_add_linear_csr(cxk_context* ctx, int rows, int m, const int* rowptr, const int* col, const double* val,
-                       const double* c, const int* vars) {
+// cxk_add_linear_csr / cxk_add_soc_csr: a constraint of `type` whose matrix of `rows` rows is given by its nonzeros;
+// `fn` names the caller in the refusals, `size` its size argument.
+static int AddCsrConstraint(cxk_context* ctx, const char* fn, const char* size, int type, int n, int rows, int m,
+                            const int* rowptr, const int* col, const double* val, const double* c, const int* vars) {
   if (!ctx) return -1;
-  auto refuse = [ctx](const char* msg) {
-    ctx->err = msg;
+  auto refuse = [ctx, fn](const std::string& msg) {
+    ctx->err = std::string(fn) + ": " + msg;
     return -1;
   };
-  if (rows < 1 || m < 0) return refuse("cxk_add_linear_csr: rows is at least 1 and m at least 0");
-  if (!rowptr || !c) return refuse("cxk_add_linear_csr: rowptr or c is null");
-  if (rowptr[0] != 0) return refuse("cxk_add_linear_csr: rowptr[0] is not 0");
+  if (n < 1 || rows < 1 || m < 0) return refuse(std::string(size) + " is at least 1 and m at least 0");
+  if (!rowptr || !c) return refuse("rowptr or c is null");
+  if (rowptr[0] != 0) return refuse("rowptr[0] is not 0");
   for (int r = 0; r < rows; r++)
-    if (rowptr[r + 1] < rowptr[r]) return refuse("cxk_add_linear_csr: rowptr decreases");
-  if (rowptr[rows] > 0 && (!col || !val)) return refuse("cxk_add_linear_csr: col or val is null");
+    if (rowptr[r + 1] < rowptr[r]) return refuse("rowptr decreases");
+  if (rowptr[rows] > 0 && (!col || !val)) return refuse("col or val is null");
   ConstraintRec rec;
-  rec.type = CXK_LINEAR;
-  rec.n = rows;
+  rec.type = type;
+  rec.n = n;
   rec.m = m;
   rec.csr_only = true;
   rec.C.assign(c, c + rows);
@@ -393,12 +397,12 @@ int cxk_add_linear_csr(cxk_context* ctx, int rows, int m, const int* rowptr, con
   for (int r = 0; r < rows; r++) {
     row.clear();
     for (int s = rowptr[r]; s < rowptr[r + 1]; s++) {
-      if (col[s] < 0 || col[s] >= m) return refuse("cxk_add_linear_csr: a column is outside [0, m)");
+      if (col[s] < 0 || col[s] >= m) return refuse("a column is outside [0, m)");
       row.emplace_back(col[s], val[s]);
     }
     std::sort(row.begin(), row.end(), [](const std::pair<int, double>& a, const std::pair<int, double>& b) { return a.first < b.first; });
     for (size_t s = 1; s < row.size(); s++)
-      if (row[s].first == row[s - 1].first) return refuse("cxk_add_linear_csr: a row names a column twice");
+      if (row[s].first == row[s - 1].first) return refuse("a row names a column twice");
     for (const auto& e : row)
       if (e.second != 0.0) {  // explicit zeros are dropped
         rec.sp_col.push_back(e.first);
@@ -407,6 +411,16 @@ int cxk_add_linear_csr(cxk_context* ctx, int rows, int m, const int* rowptr, con
     rec.sp_rowptr[(size_t)r + 1] = (int)rec.sp_col.size();
   }
   return AddConstraint(ctx, std::move(rec), vars);
+}
+
+int cxk_add_linear_csr(cxk_context* ctx, int rows, int m, const int* rowptr, const int* col, const double* val,
+                       const double* c, const int* vars) {
+  return AddCsrConstraint(ctx, "cxk_add_linear_csr", "rows", CXK_LINEAR, rows, rows, m, rowptr, col, val, c, vars);
+}
+
+int cxk_add_soc_csr(cxk_context* ctx, int n, int m, const int* rowptr, const int* col, const double* val, const double* c,
+                    const int* vars) {
+  return AddCsrConstraint(ctx, "cxk_add_soc_csr", "n", CXK_SOC, n, n < INT_MAX ? n + 1 : 0, m, rowptr, col, val, c, vars);
 }
 
 int cxk_add_soc(cxk_context* ctx, int n, int m, const double* A, const double* c, const int* vars) {
@@ -543,6 +557,22 @@ int cxk_count_sparse_linear(const cxk_context* ctx) {
   for (size_t i = 0; i < ctx->cons.size(); i++) k += ctx->owned[i] && ctx->cons[i].lsparse;
   return k;
 }
+
+int cxk_set_sparse_soc(cxk_context* ctx, int mode) {
+  if (!ctx) return CXK_FAILURE;
+  CXK_DEMAND(!ctx->finalized, "cxk_set_sparse_soc: the context is finalized (the choice is made by cxk_finalize)");
+  CXK_DEMAND(mode >= -1 && mode <= 1, "cxk_set_sparse_soc: the mode is -1 (automatic), 0 (never) or 1 (every second-order cone)");
+  ctx->sparse_soc = mode;
+  return CXK_SUCCESS;
+}
+int cxk_count_sparse_soc(const cxk_context* ctx) {
+  if (!ctx || !ctx->finalized) return -1;
+  int k = 0;
+  for (size_t i = 0; i < ctx->cons.size(); i++) k += ctx->owned[i] && ctx->cons[i].ssparse;
+  return k;
+}
+
+double cxk_sparse_soc_setup_ms(const cxk_context* ctx) { return ctx && ctx->finalized ? ctx->sparse_soc_setup_ms : 0.0; }
 
 int cxk_set_streamed_quadratic(cxk_context* ctx, int mode) {
   if (!ctx) return CXK_FAILURE;

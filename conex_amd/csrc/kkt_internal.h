@@ -49,7 +49,10 @@ struct ConstraintRec {
   // linear block: its nonzeros by rows, columns ascending (cxk_add_linear_csr gives them and leaves A empty: such a
   // block can only take the sparse route; GroupConstraints reads them off the A of a dense-added block)
   bool lsparse = false;   // linear block on the sparse route (kernels_linear_sparse.hip.h)
-  bool csr_only = false;  // added by cxk_add_linear_csr: no dense A
+  bool csr_only = false;  // added by cxk_add_linear_csr / cxk_add_soc_csr: no dense A
+  // second-order cone on the sparse route (kernels_soc_sparse.hip.h): the same sp_* vectors hold the nonzeros of its
+  // (n + 1) x m matrix, given by cxk_add_soc_csr (csr_only) or read off the A of a cone added by cxk_add_soc
+  bool ssparse = false;
   std::vector<int> sp_rowptr, sp_col;
   std::vector<double> sp_val;
 };
@@ -144,6 +147,12 @@ struct Group {
   bool lsparse = false;
   DevBuf<int> ls_eptr, ls_rowptr, ls_col, ls_colptr, ls_crow;
   DevBuf<double> ls_val, ls_cval;
+  // second-order cones on the sparse route (cxk_set_sparse_soc): the kernels of kernels_soc_sparse.hip.h; the nonzeros
+  // in the ls_* arrays as above (rows = n + 1); the constants H = A' J A, h = A' J c, z = c' J c of every member in
+  // ss_const (formed on the device at finalize), s, ms, u = A' w and (det w, w . c) in st_vec (MakeSocSparse lays
+  // both out).  No dense A, no WA, no GEMM output.
+  bool ssparse = false;
+  DevBuf<double> ss_const;
 };
 
 
@@ -181,6 +190,9 @@ struct cxk_context {
   int tiled_linear = -1;    // cxk_set_tiled_linear: -1 the environment's CXK_TILED_LINEAR (else by size), 0 never, 1 every block
   // cxk_set_sparse_linear: -2 the environment's CXK_SPARSE_LINEAR (else never), -1 by pattern, 0 never, 1 every block
   int sparse_linear = -2;
+  // cxk_set_sparse_soc: -2 the environment's CXK_SPARSE_SOC (else never), -1 by pattern, 0 never, 1 every second-order cone
+  int sparse_soc = -2;
+  double sparse_soc_setup_ms = 0;  // device time the last cxk_finalize spent on their constants (cxk_sparse_soc_setup_ms)
   std::vector<Group> groups;
   std::vector<int64_t> g_off, r_off;
   std::vector<unsigned char> owned;      // constraint i assembled/updated by this rank

@@ -83,6 +83,23 @@ inline bool LinearSparsePays(double rows, double m, double sum_nnz_sq, int longe
          longest_column <= kSparseLinearMaxColumn;
 }
 
+// Automatic mode (cxk_set_sparse_soc(ctx, -1)) sends a second-order cone of dimension len = n + 1 over m variables to
+// the sparse route when it can run nowhere else (added by cxk_add_soc_csr, or len m beyond the int range), or when
+// R nnz <= len m and len m^2 >= kSparseSocMinWork: the sparse assembly reads the nnz nonzeros and moves the m x m
+// square twice, the dense routes stream len m entries (and the streamed one multiplies len m^2).  Measured
+// (tools/soc_sparse_speed.py --sweep against the streamed route): each constant is twice the smallest
+// value among the swept shapes at which assembly + query + PrepareStep + TakeStep are faster on the sparse route;
+// twice, because the numbers are one box's on one day.  The smallest winning len m / nnz is 2.02 (2048 x 64 half full:
+// 87.8 us against 129.7 us; the assembly gains 4.3x, the one-thread-per-row slack loses 0.63x); a fully dense 401 x 61
+// loses (87.6 us against 82.7 us) and never moves.  The smallest swept shape, 401 x 61 (len m^2 = 1 492 121), wins at
+// 3 nonzeros per row (51.4 us against 79.7 us); nothing smaller was measured, so nothing smaller moves.
+// CXK_SPARSE_SOC_MIN_RATIO moves R for comparison runs.  No default anywhere asks for this mode.
+constexpr double kSparseSocMinRatio = 4.04;
+constexpr long long kSparseSocMinWork = 2ll * 401 * 61 * 61;  // 2 984 242
+inline bool SocSparsePays(double len, double m, double nnz, double ratio) {
+  return ratio * nnz <= len * m && len * m * m >= (double)kSparseSocMinWork;
+}
+
 // Automatic mode (cxk_set_streamed_quadratic(ctx, -1)) sends a quadratic cone to the streamed route from this many
 // doubles streamed per pass, (Q ? n n : 0) + (n + 1) m, on.  Measured (tools/quad_stream_speed.py):
 // the smallest shape of the sweep, n = 32 with Q over m = 8 (32 * 32 + 33 * 8), where assembly + PrepareStep +
@@ -108,6 +125,8 @@ struct FinalizeSwitches {
   long long streamed_quadratic_min_work = kQuadStreamMinWork;  // CXK_STREAMED_QUADRATIC_MIN_WORK (comparison runs)
   int sparse_linear = 0;        // CXK_SPARSE_LINEAR=0 / 1: linear blocks never / always on the sparse route (cxk_set_sparse_linear)
   double sparse_linear_min_ratio = kSparseLinearMinRatio;  // CXK_SPARSE_LINEAR_MIN_RATIO (comparison runs)
+  int sparse_soc = 0;           // CXK_SPARSE_SOC=0 / 1: second-order cones never / always on the sparse route (cxk_set_sparse_soc)
+  double sparse_soc_min_ratio = kSparseSocMinRatio;  // CXK_SPARSE_SOC_MIN_RATIO (comparison runs)
 };
 
 // ---- kkt_context.hip

@@ -80,6 +80,7 @@ struct Program {
   int streamed_cones = 1;       // second-order cones beyond LDS run from HBM; see CONEX_HIP_SetStreamedCones
   int tiled_linear = -1;        // linear blocks on the tiled kernels: -1 by size; see CONEX_HIP_SetTiledLinear
   int sparse_linear = -1;       // linear blocks from their nonzeros: -1 by pattern; see CONEX_HIP_SetSparseLinear
+  int sparse_soc = 0;           // second-order cones from their nonzeros: 0 none; see CONEX_HIP_SetSparseSoc
   int streamed_quadratic = -1;  // quadratic cones held in HBM: -1 beyond LDS or by size; see CONEX_HIP_SetStreamedQuadratic
   // multi-GPU (one process per GPU, every rank builds the same program): see CONEX_HIP_SetCommunicator
   int shard_rank = 0, shard_world = 1;
@@ -154,6 +155,8 @@ int BuildContext(Program* p) {
   if (p->tiled_linear >= 0) cxk_set_tiled_linear(p->ctx, p->tiled_linear);
   // (automatic, where the cxk_* interface defaults to never: bounds and polytopic rows are almost empty)
   cxk_set_sparse_linear(p->ctx, p->sparse_linear);
+  // (never, as the cxk_* interface defaults: every program keeps its route and its bits unless asked)
+  cxk_set_sparse_soc(p->ctx, p->sparse_soc);
   // (likewise no quadratic cone is refused for its size: automatic, where the cxk_* interface defaults to never)
   cxk_set_streamed_quadratic(p->ctx, p->streamed_quadratic);
   if (p->shard_world > 1) {
@@ -1334,6 +1337,22 @@ int CONEX_HIP_SetSparseLinear(void* x, int mode) {
   p->sparse_linear = mode;
   p->dirty = true;
   return CONEX_SUCCESS;
+}
+
+/* not part of conex.h: which second-order cones are evaluated from their nonzeros (conex_kkt_hip.h,
+ * cxk_set_sparse_soc): 0 (the default) none; 1 every cone; -1 those that can run nowhere else or whose pattern makes
+ * it pay */
+int CONEX_HIP_SetSparseSoc(void* x, int mode) {
+  Program* p = static_cast<Program*>(x);
+  if (!p || mode < -1 || mode > 1) return CONEX_FAILURE;
+  p->sparse_soc = mode;
+  p->dirty = true;
+  return CONEX_SUCCESS;
+}
+/* second-order cones of the program's device context on the sparse route (cxk_count_sparse_soc); -1 before a first solve */
+int CONEX_HIP_CountSparseSoc(void* x) {
+  Program* p = static_cast<Program*>(x);
+  return p && p->ctx ? cxk_count_sparse_soc(p->ctx) : -1;
 }
 
 /* not part of conex.h: which quadratic cones are held in HBM and run on the streamed kernels (conex_kkt_hip.h,

@@ -135,6 +135,10 @@ _SIGNATURES = {
     "cxk_set_sparse_linear": (C.c_int, [C.c_void_p, C.c_int]),
     "cxk_count_sparse_linear": (C.c_int, [C.c_void_p]),
     "cxk_add_linear_csr": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_int_p, c_int_p, c_double_p, c_double_p, c_int_p]),
+    "cxk_set_sparse_soc": (C.c_int, [C.c_void_p, C.c_int]),
+    "cxk_count_sparse_soc": (C.c_int, [C.c_void_p]),
+    "cxk_sparse_soc_setup_ms": (C.c_double, [C.c_void_p]),
+    "cxk_add_soc_csr": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_int_p, c_int_p, c_double_p, c_double_p, c_int_p]),
     "cxk_count_tiled_linear": (C.c_int, [C.c_void_p]),
     "cxk_fused_tree_timed_out": (C.c_int, [C.c_void_p]),
     "cxk_debug_force_fused_timeout": (C.c_int, [C.c_void_p]),
@@ -261,6 +265,24 @@ class KktContext:
         r = self.L.cxk_add_linear_csr(self.h, rows, m, _ip(rp), _ip(cl), _dp(vl), _dp(cc), vp)
         if r >= 0:
             self.cons.append(("linear", rows, m))
+        return r
+
+    def add_soc_csr(self, rowptr, col, val, c, vars_=None):
+        """The constraint of add_soc by the nonzeros of its (n + 1) x m matrix: row r holds col / val
+        [rowptr[r]:rowptr[r + 1]], columns in any order; n + 1 = len(c).  The number of variables is len(vars_), or the
+        context's.  Such a cone takes the sparse route only."""
+        rp = np.ascontiguousarray(rowptr, dtype=np.int32)
+        cl = np.ascontiguousarray(col, dtype=np.int32)
+        vl = np.ascontiguousarray(val, dtype=np.float64)
+        cc = np.ascontiguousarray(np.asarray(c, dtype=np.float64).ravel())
+        rows = len(cc)
+        if len(rp) != rows + 1 or len(cl) != len(vl) or (len(rp) and rp[-1] > len(cl)):
+            raise ValueError("add_soc_csr: rowptr has len(c) + 1 entries and points into col / val of equal length")
+        keep, vp = self._vars(vars_)
+        m = self.num_vars if vars_ is None else len(keep)
+        r = self.L.cxk_add_soc_csr(self.h, rows - 1, m, _ip(rp), _ip(cl), _dp(vl), _dp(cc), vp)
+        if r >= 0:
+            self.cons.append(("soc", rows - 1, m))
         return r
 
     def add_hermitian(self, A, Cm, vars_=None):
@@ -814,6 +836,19 @@ class KktContext:
     def count_sparse_linear(self):
         """Constraints this context owns that run on the sparse linear kernels."""
         return self.L.cxk_count_sparse_linear(self.h)
+
+    def set_sparse_soc(self, mode=1):
+        """Second-order cones evaluated from their nonzeros: 1 every cone, 0 none, -1 those that can run nowhere else or
+        whose pattern makes it pay (before initialize; default: CXK_SPARSE_SOC in the environment, else 0)."""
+        self._check(self.L.cxk_set_sparse_soc(self.h, int(mode)), "cxk_set_sparse_soc")
+
+    def count_sparse_soc(self):
+        """Constraints this context owns that run on the sparse second-order-cone kernels."""
+        return self.L.cxk_count_sparse_soc(self.h)
+
+    def sparse_soc_setup_ms(self):
+        """Device milliseconds initialize() spent forming the constants H, h, z of the sparse second-order cones."""
+        return self.L.cxk_sparse_soc_setup_ms(self.h)
 
     def fused_tree_timed_out(self):
         return bool(self.L.cxk_fused_tree_timed_out(self.h))

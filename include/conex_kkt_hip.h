@@ -180,6 +180,42 @@ int cxk_count_sparse_linear(const cxk_context* ctx);
 int cxk_add_linear_csr(cxk_context* ctx, int rows, int m, const int* rowptr /* rows + 1 */, const int* col,
                        const double* val, const double* c /* rows */, const int* vars);
 
+/* Second-order cones evaluated from their nonzeros.  The LDS and the streamed route hold a cone as a dense
+ * (n + 1) x variables matrix; the cones of ||A x - b|| <= t with a sparse A, of robust LP rows or of trajectory norms
+ * are almost empty.  The sparse route (kernels_soc_sparse.hip.h) holds a cone on the device by rows and by columns
+ * (CSR and CSC), never uploads its dense matrix and evaluates, with J = diag(-1, 1, .., 1), u = A' w,
+ *   G = 4 u u' + 2 det(w) H,  AW = 2 u,  AQc = 2 (2 (w . c) u + det(w) h),  sc = (2 w . c, 2 (2 (w . c)^2 + det(w) z)),
+ * where H = A' J A, h = A' J c and z = c' J c are formed once, on the device, at cxk_finalize: one assembly is nnz
+ * multiply-adds, one read of H and one write of G, with no (n + 1) x variables work space, no GEMM and no square
+ * root.  These are quad_schur's expressions in w itself (Q = NULL); they differ from the literal 2 WA' WA of the other
+ * two routes by rounding only.  No atomics, fixed summation orders: two runs give the same bits, G
+ * comes out exactly symmetric, and the slack, the eigenvalue query, normsqrd, norminfd, the w^{1/2} PrepareStep leaves
+ * in W and W after a step are the streamed route's bit for bit (its step kernels are reused).  Every output, getter
+ * and setter is that of any second-order cone; cxk_line_search keeps refusing second-order cones.
+ * cxk_set_sparse_soc, before cxk_finalize: mode 1 every second-order cone takes the sparse route; 0 none does; -1 a
+ * cone does when it can run nowhere else (added by cxk_add_soc_csr, or (n + 1) x variables beyond the int range), or
+ * when kSparseSocMinRatio x nnz <= (n + 1) x variables and (n + 1) x variables^2 is at least kSparseSocMinWork
+ * (kkt_launch.h, measured; CXK_SPARSE_SOC_MIN_RATIO moves the ratio for comparison runs).  Without a call: the
+ * environment's CXK_SPARSE_SOC = 0 | 1, else 0.  A sparse cone needs neither cxk_set_streamed_cones nor LDS room.
+ * Refused on the sparse route at cxk_finalize, by name: variables^2 beyond the int range; a group of equal-shaped
+ * cones with more than 2^31 nonzeros, column chunks, row tiles or tiles of the Schur block.
+ * cxk_count_sparse_soc: constraints this context owns on the sparse route (-1 before cxk_finalize; 0 on a host-only
+ * context); cxk_count_streamed_cones does not count them.
+ * cxk_sparse_soc_setup_ms: device milliseconds the last cxk_finalize spent forming H, h and z of this context's sparse
+ * cones (hipEvent pair around those launches; 0 without such cones, before cxk_finalize and on a host-only context).
+ * cxk_add_soc_csr: the constraint of cxk_add_soc given by the nonzeros of its (n + 1) x m matrix, rowptr[r] ..
+ * rowptr[r + 1] being row r's entries of col / val.  Columns within a row come in any order (the library sorts them);
+ * explicit zeros are dropped.  Returns -1 (cxk_last_error names the reason) for rowptr[0] != 0, a decreasing rowptr, a
+ * column outside [0, m), a column named twice in a row, null pointers.  Such a cone has no dense matrix and can only
+ * take the sparse route: cxk_finalize refuses it by name when the mode in force is 0.  A cone added by cxk_add_soc
+ * takes the sparse route under mode 1 or when the automatic rule picks it (its nonzeros are read off A at
+ * cxk_finalize) and keeps its present kernels and bits otherwise. */
+int cxk_set_sparse_soc(cxk_context* ctx, int mode);
+int cxk_count_sparse_soc(const cxk_context* ctx);
+double cxk_sparse_soc_setup_ms(const cxk_context* ctx);
+int cxk_add_soc_csr(cxk_context* ctx, int n, int m, const int* rowptr /* n + 2 */, const int* col, const double* val,
+                    const double* c /* n + 1 */, const int* vars);
+
 /* Quadratic cones { x0 >= sqrt(x1' Q x1) } of real size.  The LDS route (quad_schur, quad_prepare, quad_take_step)
  * gives a cone one workgroup and runs its maps, the products with Q among them, on one thread; a cone whose
  * variables + 4 (dimension + 1) doubles exceed LDS is refused at cxk_finalize.  The streamed route
