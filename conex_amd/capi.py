@@ -69,6 +69,8 @@ def api():
         # not in conex.h (the reference reaches these cones through its C++ API only)
         "CONEX_HIP_AddQuadraticConstraint": (ci, [vp, c_double_p, ci, c_double_p, ci, ci, c_double_p, ci,
                                                   C.POINTER(C.c_long), ci]),
+        "CONEX_HIP_AddFactoredLMIConstraint": (ci, [vp, ci, c_double_p, ci, c_double_p, ip, ci, c_double_p,
+                                                    C.POINTER(C.c_long)]),
         "CONEX_HIP_AddQuadraticCostEpigraph": (ci, [vp, c_double_p, ci, C.POINTER(C.c_long), C.c_long]),
         "CONEX_HIP_SetStreamedCones": (ci, [vp, ci]),
         "CONEX_HIP_SetTiledLinear": (ci, [vp, ci]),

@@ -798,16 +798,16 @@ inline dim3 ElemGrid(int n, int count) {
   return dim3(blocks < 256 ? blocks : 256, count);
 }
 
+// The stages behind the slack S (count x n^2 at ws.tmp, whoever wrote it): W S, then the spectrum or the affine branch.
 // mode 0: PrepareStep (stores WS in g.T1; affine branch updates W), mode 1: eigenvalue query
-inline hipError_t LmiLargePrepare(const LmiGroup& g, const StepArgs& sa, const LmiLargeWs& ws, int mode,
-                                  hipStream_t st) {
+inline hipError_t LmiLargeAfterSlack(const LmiGroup& g, const StepArgs& sa, const LmiLargeWs& ws, int mode,
+                                     hipStream_t st) {
   const int n = g.n;
   const int64_t nn = (int64_t)n * n;
   double* S = ws.tmp;                        // count x nn
   double* WS = (mode == 0) ? g.T1 : ws.tmp + (size_t)g.count * nn;
   double* T = ws.tmp + 2 * (size_t)g.count * nn;
   hipError_t e;
-  lmi_large_slack<<<ElemGrid(n, g.count), 256, sizeof(double) * g.m, st>>>(g, sa, S);
   GemmArgs a = SquareGemm(n, g.W, nn, S, nn, WS, nn);
   if ((e = LaunchGemm(a, false, false, g.count, st)) != hipSuccess) return e;
   if (mode == 0 && sa.affine) {
@@ -821,6 +821,12 @@ inline hipError_t LmiLargePrepare(const LmiGroup& g, const StepArgs& sa, const L
   else
     lmi_large_spectrum<1><<<g.count, 512, LmiLargeSpectrumLds(n), st>>>(g, sa, WS, S);
   return hipGetLastError();
+}
+
+inline hipError_t LmiLargePrepare(const LmiGroup& g, const StepArgs& sa, const LmiLargeWs& ws, int mode,
+                                  hipStream_t st) {
+  lmi_large_slack<<<ElemGrid(g.n, g.count), 256, sizeof(double) * g.m, st>>>(g, sa, ws.tmp);
+  return LmiLargeAfterSlack(g, sa, ws, mode, st);
 }
 
 // W <- sym( pade33( (WS + e I) alpha ) W )

@@ -12,6 +12,7 @@
 #include "kernels_lmi_sparse.hip.h"
 #include "kernels_lmi_rows.hip.h"
 #include "kernels_lmi_large.hip.h"
+#include "kernels_lmi_factored.hip.h"
 #include "kernels_quad.hip.h"
 #include "kernels_soc_stream.hip.h"
 #include "kernels_linear_tiled.hip.h"
@@ -232,6 +233,25 @@ LmiLargeWs MakeLargeWs(Group& g) {
   return w;
 }
 
+LmiFactoredGroup MakeLmiFactored(Group& g) {
+  LmiFactoredGroup f{};
+  const size_t cnt = g.ids.size(), nr = (size_t)g.n * g.f_R;
+  f.R = g.f_R;
+  f.rank_one = g.f_rank_one;
+  f.F = g.f_F.p;
+  f.sigma = g.f_sigma.p;
+  f.ptr = g.f_ptr.p;
+  f.var = g.f_var.p;
+  f.Z = g.f_ws.p;  // (the layout UploadGroup sizes: LmiFactoredWsDoubles)
+  f.Y = f.Z + cnt * nr;
+  f.Fs = f.Y + cnt * nr;
+  f.P = f.Fs + cnt * nr;
+  f.part = g.ws_part.p;
+  f.npart = kSparseCParts;
+  return f;
+}
+size_t LmiFactoredWsDoubles(size_t cnt, size_t n, size_t R) { return cnt * (3 * n * R + R * R); }
+
 size_t LmiGenericLds(int n) { return sizeof(double) * (size_t)(4 * n * n); }
 size_t LmiPrepareLds(int n, int m) {
   return sizeof(double) * (size_t)(3 * n * n + 6 * n + 2 * (n / 2 + 2) + m + 8);
@@ -339,6 +359,9 @@ bool IsPrepareRows(LmiKernel k) {
 bool IsTakeRows(LmiKernel k) { return k >= kTakeRows20 && k <= kTakeTaylor32Pad; }
 
 LmiKernel LmiSchurKernel(const Group& g) {
+  // not one of the instances: a code outside the reported range, which no Is*() test accepts and
+  // cxk_lmi_kernel_name has no name for (LaunchSchur and cxk_lmi_kernels ask g.factored first)
+  if (g.factored) return kLmiKernelCount;
   if (g.sparse) return (LmiKernel)((g.sp_small ? kSchurSparseSmall : kSchurSparse) + (g.sp_cdense ? 1 : 0));
   if (g.schur_gemm) {  // (fold and split counts as LmiLargeSchur reads them: MakeLargeWs, LmiFoldedSplits)
     const bool fold = g.Aleft.n != 0;
@@ -789,7 +812,9 @@ int LaunchSchur(cxk_context* ctx) {
         const LmiKernel kern = LmiSchurKernel(g);
         // (lmi_schur_mfma carries the pair on its dispatch instead: no marker packets)
         if (sample && !IsSchurMfma(kern)) CXK_TRY(hipEventRecord(e0, ctx->stream));
-        if (IsSchurSparse(kern)) {
+        if (g.factored) {  // (not one of the reported instances: `kern` is not looked at)
+          CXK_TRY(LmiFactoredSchur(MakeLmi(g), MakeLmiFactored(g), ar, MakeLargeWs(g), ctx->stream));
+        } else if (IsSchurSparse(kern)) {
           CXK_TRY(LaunchLmiSchurSparse(g, kern, ar, ctx->stream));
         } else if (IsSchurGemm(kern)) {
           CXK_TRY(LmiLargeSchur(MakeLmi(g), ar, MakeLargeWs(g), ctx->stream));
@@ -929,7 +954,7 @@ static int UploadSparseLinear(cxk_context* ctx, Group& g) {
 // cxk_finalize, per-group stages.  Groups of identically shaped constraints (owned ones only carry data).
 int GroupConstraints(cxk_context* ctx, const FinalizeSwitches& sw) {
   const int K = (int)ctx->cons.size();
-  std::map<std::tuple<int, int, int, int>, int> gmap;
+  std::map<std::tuple<int, int, int, int, int>, int> gmap;  // (the last: a factored LMI's R)
   ctx->groups.clear();
   // second-order cones beyond LDS: refused, or held in HBM (cxk_set_streamed_cones, else CXK_STREAMED_CONES)
   const bool stream_on = ctx->streamed_cones >= 0 ? ctx->streamed_cones != 0 : sw.streamed_cones;
@@ -997,7 +1022,11 @@ int GroupConstraints(cxk_context* ctx, const FinalizeSwitches& sw) {
                    "route (cxk_set_tiled_linear / CXK_TILED_LINEAR, which was set to 0)");
       }
     }
-    if (c.type == CXK_LMI) {
+    if (c.type == CXK_LMI && c.factored) {
+      // held by its factors (kernels_lmi_factored.hip.h) in front of the large-order route (FinalizeImpl has checked
+      // the order and the int indexing of the kernels)
+      c.sparse = false;
+    } else if (c.type == CXK_LMI) {
       // sparse evaluation when it pays (CXK_SPARSE_LMI=0 / 1 forces never / always: tests)
       double nnz = 0;
       for (double v : c.A) nnz += (v != 0.0);
@@ -1077,7 +1106,9 @@ int GroupConstraints(cxk_context* ctx, const FinalizeSwitches& sw) {
                  "dimension + 1) is not supported");
     auto key = std::make_tuple(c.type, c.n, c.m, c.herm_d + (c.sparse ? 16 : 0) + (c.type == CXK_LMI && !c.symmetric ? 32 : 0) +
                                                      (c.type == CXK_QUAD && !c.Q.empty() ? 64 : 0) + (c.streamed ? 128 : 0) +
-                                                     (c.tiled ? 256 : 0) + (c.qstream ? 512 : 0) + (c.lsparse ? 1024 : 0) + (c.ssparse ? 2048 : 0));
+                                                     (c.tiled ? 256 : 0) + (c.qstream ? 512 : 0) + (c.lsparse ? 1024 : 0) + (c.ssparse ? 2048 : 0) +
+                                                     (c.factored ? 4096 : 0),
+                              c.factored ? c.f_R : 0);
     auto it = gmap.find(key);
     if (it == gmap.end()) {
       it = gmap.emplace(key, (int)ctx->groups.size()).first;
@@ -1094,6 +1125,8 @@ int GroupConstraints(cxk_context* ctx, const FinalizeSwitches& sw) {
       ctx->groups.back().qstream = c.qstream;
       ctx->groups.back().lsparse = c.lsparse;
       ctx->groups.back().ssparse = c.ssparse;
+      ctx->groups.back().factored = c.factored;
+      ctx->groups.back().f_R = c.factored ? c.f_R : 0;
     }
     c.group = it->second;
     c.member = (int)ctx->groups[it->second].ids.size();
@@ -1111,7 +1144,12 @@ int UploadGroup(cxk_context* ctx, Group& g, const FinalizeSwitches& sw) {
       a_sz = (size_t)g.m * g.n * g.n;
       c_sz = w_sz = (size_t)g.n * g.n;
       g.large = !(LmiTakeLds(g.n) <= kLdsLimit && LmiPrepareLds(g.n, g.m) <= kLdsLimit);
-      {
+      if (g.factored) {
+        // held by its factors in front of the large-order route, whatever its order (kernels_lmi_factored.hip.h)
+        a_sz = 0;  // the matrices are never formed
+        g.large = true;
+        g.mfma = g.schur_gemm = false;
+      } else {
         // shapes past the register kernels' instances assemble through the batched GEMM (measured
         // 1.5 - 3.3x faster than lmi_schur_generic at 1000 constraints: orders 25 up, and smaller
         // orders with more variables than lmi_schur_mfma's LDS images hold, e.g. order 22, m = 20
@@ -1192,7 +1230,7 @@ int UploadGroup(cxk_context* ctx, Group& g, const FinalizeSwitches& sw) {
     }
     CXK_TRY(g.Aleft.upload(hl));
   }
-  if (g.type == CXK_LMI && !g.literal && !sw.no_packed_slack && g.n == 20 &&
+  if (g.type == CXK_LMI && !g.factored && !g.literal && !sw.no_packed_slack && g.n == 20 &&
       LmiPrepareRowsSupports(g.n, g.m, g.herm_d, g.sparse)) {
     // the slack pass of PrepareStep / the eigenvalue query streams every A_i once more per call: a
     // packed copy of the lower triangles (the data is exactly symmetric) halves those bytes
@@ -1304,6 +1342,31 @@ int UploadGroup(cxk_context* ctx, Group& g, const FinalizeSwitches& sw) {
     CXK_TRY(g.st_vec.alloc(SocSparseVecDoubles(cnt, len, m)));
     CXK_TRY(g.ss_const.alloc(SocSparseConstDoubles(cnt, m)));
     if (SocSparseConstants(ctx, g)) return CXK_FAILURE;
+  }
+  if (g.factored) {
+    const size_t n = (size_t)g.n, R = (size_t)g.f_R, m = (size_t)g.m;
+    CXK_DEMAND(cnt <= 65535, "a group of more than 65535 equal-shaped factored LMIs is not supported");
+    std::vector<double> hF(cnt * n * R), hs(cnt * R);
+    std::vector<int> hp(cnt * (m + 1)), hv(cnt * R);
+    g.f_rank_one = true;
+    for (size_t k = 0; k < cnt; k++) {
+      const ConstraintRec& c = ctx->cons[g.ids[k]];
+      std::copy(c.f_F.begin(), c.f_F.end(), hF.begin() + k * n * R);
+      std::copy(c.f_sigma.begin(), c.f_sigma.end(), hs.begin() + k * R);
+      std::copy(c.f_ptr.begin(), c.f_ptr.end(), hp.begin() + k * (m + 1));
+      for (size_t i = 0; i < m; i++) {
+        g.f_rank_one = g.f_rank_one && c.f_ptr[i + 1] - c.f_ptr[i] == 1;
+        for (int q = c.f_ptr[i]; q < c.f_ptr[i + 1]; q++) hv[k * R + (size_t)q] = (int)i;
+      }
+    }
+    CXK_TRY(g.f_F.upload(hF));
+    CXK_TRY(g.f_sigma.upload(hs));
+    CXK_TRY(g.f_ptr.upload(hp));
+    CXK_TRY(g.f_var.upload(hv));
+    CXK_TRY(g.f_ws.alloc(LmiFactoredWsDoubles(cnt, n, R)));
+    CXK_TRY(g.ws_main.alloc(cnt * 8 * n * n));  // step temporaries; C W and W C W during assembly
+    CXK_TRY(g.ws_part.alloc(cnt * 2 * kSparseCParts));
+    CXK_TRY(g.ws_piv.alloc(cnt * n));
   }
   if (g.schur_gemm) {
     const size_t nn = (size_t)g.n * g.n, m1 = (size_t)g.m + 1;
@@ -1519,7 +1582,7 @@ int ReduceStepInfoAndSync(cxk_context* ctx, int mode, const double* info, const 
 int cxk_lmi_kernels(const cxk_context* ctx, int constraint, int out[5]) {
   if (!ctx || !ctx->device_ready || !out || constraint < 0 || constraint >= (int)ctx->cons.size()) return CXK_FAILURE;
   const ConstraintRec& c = ctx->cons[constraint];
-  if (c.type != CXK_LMI || !ctx->owned[constraint]) return CXK_FAILURE;
+  if (c.type != CXK_LMI || c.factored || !ctx->owned[constraint]) return CXK_FAILURE;
   const Group& g = ctx->groups[c.group];
   out[CXK_LMI_STAGE_SCHUR] = LmiSchurKernel(g);
   out[CXK_LMI_STAGE_PREPARE] = LmiPrepareKernel(ctx, g, 0);
@@ -1647,7 +1710,12 @@ int LaunchPrepareGroups(cxk_context* ctx, int pmode, const StepArgs& sa, const S
     if (g.type == CXK_LMI) {
       switch (AsPrepareKernel(LmiPrepareKernel(ctx, g, pmode))) {
         case kPrepareLarge:
-          CXK_TRY(LmiLargePrepare(MakeLmi(g), sa, MakeLargeWs(g), MODE, ctx->stream));
+          if (g.factored) {
+            CXK_TRY(LmiFactoredSlack(MakeLmi(g), MakeLmiFactored(g), sa, MakeLargeWs(g), ctx->stream));
+            CXK_TRY(LmiLargeAfterSlack(MakeLmi(g), sa, MakeLargeWs(g), MODE, ctx->stream));
+          } else {
+            CXK_TRY(LmiLargePrepare(MakeLmi(g), sa, MakeLargeWs(g), MODE, ctx->stream));
+          }
           break;
         case kPrepareRowsPacked:
         case kPrepareRowsExact:  // (the instance reads g.Apk when there is one)

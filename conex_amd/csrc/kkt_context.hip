@@ -209,6 +209,12 @@ static int AllocateSystemBuffers(cxk_context* ctx) {
 
 static int FinalizeImpl(cxk_context* ctx) {
   const FinalizeSwitches sw = ReadFinalizeSwitches();
+  for (const ConstraintRec& c : ctx->cons)
+    if (c.factored) {  // the limit of LmiLargeLuSolve, and the int indexing of kernels_lmi_factored.hip.h
+      CXK_DEMAND(c.n <= 1024, "a factored LMI of order above 1024 is not supported (one panel row per thread in the Pade LU)");
+      CXK_DEMAND((int64_t)c.n * c.f_R <= INT_MAX && (int64_t)c.f_R * c.f_R <= INT_MAX && (int64_t)c.m * c.m <= INT_MAX,
+                 "a factored LMI whose n x R, R x R or m x m entries exceed the int range is not supported");
+    }
   if (ChooseEliminationStructure(ctx, sw)) return CXK_FAILURE;
   ctx->finalized = true;
   if (ctx->device < 0) return CXK_SUCCESS;  // symbolic-only context
@@ -299,6 +305,46 @@ int cxk_add_lmi(cxk_context* ctx, int n, int m, const double* A, const double* C
   };
   r.symmetric = symmetric(C);
   for (int i = 0; i < m && r.symmetric; i++) r.symmetric = symmetric(A + (size_t)i * n * n);
+  return AddConstraint(ctx, std::move(r), vars);
+}
+
+int cxk_add_lmi_factored(cxk_context* ctx, int n, int m, const int* rank_ptr, const double* F, const double* sigma,
+                         const double* C, const int* vars) {
+  if (!ctx) return -1;
+  auto refuse = [ctx](const char* msg) {
+    ctx->err = std::string("cxk_add_lmi_factored: ") + msg;
+    return -1;
+  };
+  if (n < 1 || m < 0) return refuse("n is at least 1 and m at least 0");
+  if (!rank_ptr || !C) return refuse("rank_ptr or C is null");
+  if (rank_ptr[0] != 0) return refuse("rank_ptr[0] is not 0");
+  for (int i = 0; i < m; i++)
+    if (rank_ptr[i + 1] < rank_ptr[i]) return refuse("rank_ptr decreases");
+  const int R = rank_ptr[m];
+  if (R > 0 && !F) return refuse("F is null");
+  const size_t nr = (size_t)n * R, nn = (size_t)n * n;
+  for (size_t q = 0; q < nr; q++)
+    if (!std::isfinite(F[q])) return refuse("F holds a value that is not finite");
+  for (int k = 0; sigma && k < R; k++)
+    if (!std::isfinite(sigma[k])) return refuse("sigma holds a value that is not finite");
+  for (size_t q = 0; q < nn; q++)
+    if (!std::isfinite(C[q])) return refuse("C holds a value that is not finite");
+  for (int c = 0; c < n; c++)
+    for (int q = c + 1; q < n; q++)
+      if (C[q + (size_t)c * n] != C[c + (size_t)q * n]) return refuse("C is not symmetric");
+  ConstraintRec r;
+  r.type = CXK_LMI;
+  r.n = n;
+  r.m = m;
+  r.factored = true;
+  r.f_R = R;
+  r.f_ptr.assign(rank_ptr, rank_ptr + m + 1);
+  r.f_F.assign(F, F + nr);
+  if (sigma)
+    r.f_sigma.assign(sigma, sigma + R);
+  else
+    r.f_sigma.assign((size_t)R, 1.0);
+  r.C.assign(C, C + nn);
   return AddConstraint(ctx, std::move(r), vars);
 }
 
@@ -1302,6 +1348,13 @@ int cxk_count_sparse_lmi(const cxk_context* ctx) {
   return k;
 }
 
+int cxk_count_factored_lmi(const cxk_context* ctx) {
+  if (!ctx || !ctx->finalized) return -1;
+  int k = 0;  // (how a constraint was added, not a choice of cxk_finalize: a host-only context counts them too)
+  for (size_t i = 0; i < ctx->cons.size(); i++) k += ctx->cons[i].type == CXK_LMI && ctx->owned[i] && ctx->cons[i].factored;
+  return k;
+}
+
 int cxk_fused_assembly(const cxk_context* ctx) { return ctx && ctx->fused_asm ? 1 : 0; }
 /* 1 when assembly, factorization and solve of a KKT solve run as one launch (tree_fused.hip) */
 int cxk_fused_tree(const cxk_context* ctx) { return ctx && ctx->fused_tree ? 1 : 0; }
@@ -1346,7 +1399,7 @@ int cxk_count_lmi_kernel(const cxk_context* ctx, int which) {
   if (!ctx || !ctx->device_ready) return -1;
   int k = 0;
   for (const Group& g : ctx->groups) {
-    if (g.type != CXK_LMI) continue;
+    if (g.type != CXK_LMI || g.factored) continue;
     const int kind = g.sparse ? 4 : g.schur_gemm ? 3 : g.mfma ? 2 : 0;
     if (kind == which) k += (int)g.ids.size();
   }
@@ -1360,6 +1413,20 @@ int cxk_assembly_work(const cxk_context* ctx, double* bytes, double* flops) {
     const ConstraintRec& c = ctx->cons[i];
     if (c.type != CXK_LMI || !ctx->owned[i]) continue;
     const double n = c.n, m = c.m;
+    if (c.factored) {
+      // Z = W F, Y = C Z, P = F' Z (lower), C W and W (C W), then the sums of the finalize kernel; bytes: F, W, C,
+      // Z (written, read twice), Y, P, the two squares of the scalars, G's triangle and the three vectors
+      const double R = c.f_R;
+      double terms = 0;  // sum over i >= j of r_i r_j
+      for (int i = 0, below = 0; i < c.m; i++) {
+        const double ri = c.f_ptr[i + 1] - c.f_ptr[i];
+        below += (int)ri;
+        terms += ri * below;
+      }
+      F += 4 * n * n * R + n * R * (R + 1) + 4 * n * n * n + 4 * n * n + 3 * terms + 2 * n * R + 2 * R;
+      B += 8.0 * (n * R + 2 * n * n + 4 * n * R + n * R + R * (R + 1) / 2 + 4 * n * n + m * (m + 1) / 2 + 2 * m + R + m);
+      continue;
+    }
     // FLOPs = 4 n^3 (m+1) + n^2 (m^2 + 3m + 4) + n m ; bytes = 8 [m n^2 + 2 n^2 + m(m+1)/2 + 2m]
     F += 4 * n * n * n * (m + 1) + n * n * (m * m + 3 * m + 4) + n * m;
     B += 8.0 * (m * n * n + 2 * n * n + m * (m + 1) / 2 + 2 * m);

@@ -55,6 +55,12 @@ struct ConstraintRec {
   bool ssparse = false;
   std::vector<int> sp_rowptr, sp_col;
   std::vector<double> sp_val;
+  // CXK_LMI given by factors (cxk_add_lmi_factored, kernels_lmi_factored.hip.h): A_i = sum sigma_k f_k f_k', k in
+  // [f_ptr[i], f_ptr[i + 1]); F is n x f_R column-major.  A stays empty: the matrices are never formed.
+  bool factored = false;
+  int f_R = 0;
+  std::vector<int> f_ptr;
+  std::vector<double> f_F, f_sigma;
 };
 
 template <typename T>
@@ -153,6 +159,15 @@ struct Group {
   // both out).  No dense A, no WA, no GEMM output.
   bool ssparse = false;
   DevBuf<double> ss_const;
+  // LMIs given by factors (cxk_add_lmi_factored): the kernels of kernels_lmi_factored.hip.h in front of the large-order
+  // route's (`large` is set: HBM-resident W, ws_main's step temporaries, ws_piv).  Every member's F, sigma, column
+  // pointers and column -> variable map; Z, Y, Fs and P in f_ws (MakeLmiFactored lays it out); the slices of the two
+  // scalars in ws_part.  No dense A.
+  bool factored = false;
+  bool f_rank_one = false;
+  int f_R = 0;
+  DevBuf<double> f_F, f_sigma, f_ws;
+  DevBuf<int> f_ptr, f_var;
 };
 
 
@@ -463,6 +478,12 @@ constexpr int kChainMaxLevels = 1 << 30;  // no limit: the kernel keeps the last
 constexpr int kSplitTopLevels = 8;  // tops of at most this many levels may be swept level by level
 
 int Fail(cxk_context* ctx, const char* msg);
+// a constraint added by cxk_add_lmi_factored: such a context keeps its assembly and its tree in separate launches
+inline bool HasFactoredLmi(const cxk_context* ctx) {
+  for (const ConstraintRec& c : ctx->cons)
+    if (c.factored) return true;
+  return false;
+}
 // two-shape chains tree_chain_lean is compiled for (kkt_tree_launch.hip, LaunchChain)
 bool ChainPairCompiled(int sa, int sb);
 // dynamic-LDS limit of the tree_top_dense instances, raised on the current device (kkt_tree_launch.hip)

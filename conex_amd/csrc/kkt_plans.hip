@@ -41,7 +41,9 @@ void ComputeTreeStructure(cxk_context* ctx) {
 double ConstraintWork(const ConstraintRec& c) {
   const double n = c.n, m = c.m;
   switch (c.type) {
-    case CXK_LMI: return 4 * n * n * n * (m + 1) + n * n * m * m;
+    case CXK_LMI:
+      if (c.factored) return 4 * n * n * c.f_R + 2 * n * (double)c.f_R * c.f_R + 4 * n * n * n;
+      return 4 * n * n * n * (m + 1) + n * n * m * m;
     case CXK_LINEAR: return n * m * m;
     case CXK_SOC: return (n + 1) * m * m;
     case CXK_QUAD: return (n + 1) * m * m;
@@ -924,6 +926,7 @@ int PlanFusedAssembly(cxk_context* ctx, const PlanSwitches& sw, const AsmGather&
   Verdict v;
   v.check((ctx->world <= 1 || ctx->cut_level >= 1) && !ctx->use_ldlt && !ctx->no_lean && !sw.no_fused_asm,
           "sharded without subtrees, LDLT, generic kernels or CXK_NO_FUSED_ASM");
+  v.check(!HasFactoredLmi(ctx), "an LMI given by factors");
   v.check(nlev >= 2 && (ctx->level_segs[0].size() == 1 || ctx->level_segs[0].size() == 2) && ctx->level_lean[0] &&
               ctx->top_level >= 1 && ctx->chain_level >= 1 && ctx->level_segs[0][0].shape != 0 && 4 * ctx->chol_lds <= kLdsLimit,
           "level 0 is not a lean launch of its own");
@@ -1390,6 +1393,7 @@ int PlanFusedTree(cxk_context* ctx, const PlanSwitches& sw, const AsmGather& ag,
   v.check((!sharded || (!sw.no_fused_shard && ctx->cut_level >= 1 && ctx->cut_level < nlev)) && !ctx->use_ldlt &&
               !ctx->no_lean && !sw.no_fused_tree && nlev >= 1 && N < (1 << 26),
           "LDLT, generic kernels, CXK_NO_FUSED_TREE / CXK_NO_FUSED_SHARD or no subtrees below the cut");
+  v.check(!HasFactoredLmi(ctx), "an LMI given by factors");
   if (!v.ok) return v.refuse(sw, "whole-tree launch");
   const int cnt_all = (int)ctx->level_sn.size();
   const int cnt_up = sharded ? ctx->level_ptr[ctx->cut_level] : cnt_all;  // positions below the cut

@@ -63,6 +63,11 @@ struct Cone {
   std::vector<double> A;
   std::vector<double> c;
   std::vector<double> Q;  // kQuadCone: inner-product matrix (order x order), empty = identity
+  // kLmi added by CONEX_HIP_AddFactoredLMIConstraint: A_v = sum_k sigma[k] f_k f_k', k in rank_ptr[v] .. rank_ptr[v + 1] - 1,
+  // f_k the columns of F (order x rank_ptr.back()); `mats` stays empty, `affine` holds C
+  bool factored = false;
+  std::vector<double> F, sigma;
+  std::vector<int> rank_ptr;
 };
 
 struct Program {
@@ -175,6 +180,11 @@ int BuildContext(Program* p) {
     const int m = static_cast<int>(c.vars.size());
     switch (c.kind) {
       case kLmi: {  // (hyper is 1 for a DenseLMIConstraint)
+        if (c.factored) {  // the factors go to the device as they are: the matrices are never formed
+          id = cxk_add_lmi_factored(p->ctx, c.order, m, c.rank_ptr.data(), c.F.data(), c.sigma.data(), c.affine.data(),
+                                    c.vars.data());
+          break;
+        }
         const size_t sz = (size_t)c.order * c.order * c.hyper;
         std::vector<double> A((size_t)m * sz, 0.0), C(sz, 0.0);
         for (int v = 0; v < m && v < (int)c.mats.size(); v++)
@@ -999,6 +1009,7 @@ CONEX_STATUS CONEX_UpdateLinearOperator(void* x, int constraint, double value, i
   const int dim = hyper_complex_dim;
   switch (k.kind) {
     case kLmi: {  // hermitian_psd.cc:249-275
+      CONEX_DEMAND(!k.factored, "A constraint given by factors does not support updates of linear operator.");
       CONEX_DEMAND(dim >= 0 && dim < k.hyper, "Complex dimension out of bounds.");
       CONEX_DEMAND(row >= 0 && col >= 0 && row < k.order && col < k.order,
                    "Matrix dimension out of bounds.");
@@ -1053,6 +1064,7 @@ CONEX_STATUS CONEX_UpdateAffineTerm(void* x, int constraint, double value, int r
   const int dim = hyper_complex_dim;
   switch (k.kind) {
     case kLmi: {  // hermitian_psd.cc:286-313
+      CONEX_DEMAND(!k.factored, "A constraint given by factors does not support updates of affine term.");
       CONEX_DEMAND(dim >= 0 && dim < k.hyper, "Complex dimension out of bounds.");
       CONEX_DEMAND(row >= 0 && col >= 0 && row < k.order && col < k.order,
                    "Matrix dimension out of bounds.");
@@ -1225,6 +1237,50 @@ int CONEX_HIP_AddQuadraticConstraint(void* x, const double* Q, int n, const doub
   if (Q) k.Q.assign(Q, Q + (size_t)n * n);
   if (vars) {
     for (int i = 0; i < Ac; i++) {
+      if (vars[i] < 0 || vars[i] >= p->num_vars) return -1;
+      k.vars.push_back((int)vars[i]);
+    }
+  } else {
+    k.vars = AllVars(*p);
+  }
+  return AddCone(p, std::move(k));
+}
+
+/* not part of conex.h: a DenseLMIConstraint whose matrices are low-rank and given by their factors,
+ *   A_v = sum_k sigma[k] f_k f_k',  k = rank_ptr[v] .. rank_ptr[v + 1] - 1,  v < num_vars,
+ * f_k the columns of F (n x R column-major, R = rank_ptr[num_vars]); sigma NULL = all +1; c the n x n affine term
+ * (symmetric); vars: num_vars variable ids (NULL: all variables in order).  The matrices are never formed
+ * (cxk_add_lmi_factored).  CONEX_UpdateLinearOperator and CONEX_UpdateAffineTerm fail on such a constraint.
+ * Returns the constraint id, -1 on invalid arguments. */
+int CONEX_HIP_AddFactoredLMIConstraint(void* x, int n, const double* F, int R, const double* sigma, const int* rank_ptr,
+                                       int num_vars, const double* c, const long* vars) {
+  Program* p = static_cast<Program*>(x);
+  if (!p || p->magic != 0xC0DEC0DEu || n < 1 || R < 0 || num_vars < 0 || !rank_ptr || !c || (R > 0 && !F)) return -1;
+  if (vars ? false : num_vars != p->num_vars) return -1;
+  if (rank_ptr[0] != 0 || rank_ptr[num_vars] != R) return -1;
+  for (int v = 0; v < num_vars; v++)
+    if (rank_ptr[v + 1] < rank_ptr[v]) return -1;
+  const size_t nn = (size_t)n * n, nr = (size_t)n * R;
+  for (size_t q = 0; q < nr; q++)
+    if (!std::isfinite(F[q])) return -1;
+  for (int k = 0; sigma && k < R; k++)
+    if (!std::isfinite(sigma[k])) return -1;
+  for (int col = 0; col < n; col++)
+    for (int row = col; row < n; row++)
+      if (!std::isfinite(c[row + (size_t)col * n]) || c[row + (size_t)col * n] != c[col + (size_t)row * n]) return -1;
+  Cone k;
+  k.kind = kLmi;
+  k.order = n;
+  k.factored = true;
+  k.F.assign(F, F + nr);
+  if (sigma)
+    k.sigma.assign(sigma, sigma + R);
+  else
+    k.sigma.assign((size_t)R, 1.0);
+  k.rank_ptr.assign(rank_ptr, rank_ptr + num_vars + 1);
+  k.affine.assign(c, c + nn);
+  if (vars) {
+    for (int i = 0; i < num_vars; i++) {
       if (vars[i] < 0 || vars[i] >= p->num_vars) return -1;
       k.vars.push_back((int)vars[i]);
     }

@@ -33,6 +33,8 @@ _SIGNATURES = {
     "cxk_destroy": (None, [C.c_void_p]),
     "cxk_last_error": (C.c_char_p, [C.c_void_p]),
     "cxk_add_lmi": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_double_p, c_double_p, c_int_p]),
+    "cxk_add_lmi_factored": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_int_p, c_double_p, c_double_p, c_double_p, c_int_p]),
+    "cxk_count_factored_lmi": (C.c_int, [C.c_void_p]),
     "cxk_add_linear": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_double_p, c_double_p, c_int_p]),
     "cxk_add_soc": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_double_p, c_double_p, c_int_p]),
     "cxk_add_quadratic": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p, c_int_p]),
@@ -235,6 +237,24 @@ class KktContext:
         a, c = _colmajor(A), _colmajor(np.asarray(Cm, dtype=np.float64))
         keep, vp = self._vars(vars_)
         r = self.L.cxk_add_lmi(self.h, n, m, _dp(a), _dp(c), vp)
+        if r >= 0:
+            self.cons.append(("lmi", n, m))
+        return r
+
+    def add_lmi_factored(self, F, rank_ptr, sigma, Cm, vars_=None):
+        """The constraint of add_lmi with A_i = sum_k sigma[k] F[:, k] F[:, k]', k in rank_ptr[i]:rank_ptr[i + 1]: F is
+        n x R, rank_ptr has m + 1 entries, sigma R signs or weights (None: all +1).  The A_i are never formed."""
+        Cm = np.asarray(Cm, dtype=np.float64)
+        n = Cm.shape[0]
+        rp = np.ascontiguousarray(rank_ptr, dtype=np.int32)
+        F = np.asarray(F, dtype=np.float64).reshape(n, -1)
+        sg = None if sigma is None else np.ascontiguousarray(np.asarray(sigma, dtype=np.float64).ravel())
+        if len(rp) < 1 or (len(rp) and rp[-1] != F.shape[1]) or (sg is not None and len(sg) != F.shape[1]):
+            raise ValueError("add_lmi_factored: rank_ptr ends at the number of columns of F, which sigma has one entry for")
+        f, c = _colmajor(F), _colmajor(Cm)
+        keep, vp = self._vars(vars_)
+        m = len(rp) - 1
+        r = self.L.cxk_add_lmi_factored(self.h, n, m, _ip(rp), _dp(f), None if sg is None else _dp(sg), _dp(c), vp)
         if r >= 0:
             self.cons.append(("lmi", n, m))
         return r
@@ -845,6 +865,10 @@ class KktContext:
     def count_sparse_soc(self):
         """Constraints this context owns that run on the sparse second-order-cone kernels."""
         return self.L.cxk_count_sparse_soc(self.h)
+
+    def count_factored_lmi(self):
+        """Constraints this context owns that were added by add_lmi_factored (kernels_lmi_factored.hip.h)."""
+        return self.L.cxk_count_factored_lmi(self.h)
 
     def sparse_soc_setup_ms(self):
         """Device milliseconds initialize() spent forming the constants H, h, z of the sparse second-order cones."""

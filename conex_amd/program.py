@@ -82,6 +82,26 @@ class _LinearOperator:
         return self.A.T @ np.asarray(x, dtype=np.float64).ravel()
 
 
+class _FactoredLMIOperator:
+    """y -> sum_i y_i A_i with A_i = sum_k sigma_k f_k f_k', k in rank_ptr[i]:rank_ptr[i + 1], and its adjoint, from the
+    factors (the matrices are never formed)."""
+
+    def __init__(self, F, rank_ptr, sigma, num_vars, variables):
+        self.F, self.sigma = F, sigma
+        self.var = np.repeat(np.arange(len(rank_ptr) - 1), np.diff(rank_ptr))
+        self.m = num_vars
+        self.variables = np.arange(len(rank_ptr) - 1) if variables is None else np.asarray(variables, dtype=np.int64)
+
+    def apply(self, y):
+        y = np.asarray(y, dtype=np.float64).ravel()[self.variables]
+        return (self.F * (self.sigma * y[self.var])) @ self.F.T
+
+    def adjoint(self, X):
+        out = np.zeros(self.m)
+        np.add.at(out, self.variables[self.var], self.sigma * np.einsum("ak,ab,bk->k", self.F, np.asarray(X), self.F))
+        return out
+
+
 def _f64(a):
     return np.ascontiguousarray(np.asarray(a, dtype=np.float64))
 
@@ -185,6 +205,36 @@ class Conex:
         self.A.append(LMIOperator(A, self.m, variables))
         self.c.append(c.copy())
         self.num_constraints += 1
+
+    def AddFactoredLinearMatrixInequality(self, F, rank_ptr, sigma, c, variables=None):
+        """c - sum_i y_i A_i positive semidefinite with low-rank A_i = sum_k sigma[k] F[:, k] F[:, k]',
+        k in rank_ptr[i]:rank_ptr[i + 1], given by its factors and never expanded (CONEX_HIP_AddFactoredLMIConstraint,
+        an extra next to the reference's surface).  F is n x R, rank_ptr has one entry more than the constraint has
+        variables (len(variables), or all when None), sigma R entries or None (all +1), c is n x n symmetric.
+        Returns the constraint id."""
+        c = np.asarray(c, dtype=np.float64)
+        if c.ndim != 2 or c.shape[0] != c.shape[1]:
+            raise ConexError("Invalid LMI")
+        n = c.shape[0]
+        F = np.asarray(F, dtype=np.float64).reshape(n, -1)
+        rp = np.ascontiguousarray(np.asarray(rank_ptr).ravel(), dtype=np.int32)
+        R = F.shape[1]
+        sg = np.ones(R) if sigma is None else _f64(np.asarray(sigma, dtype=np.float64).ravel())
+        if len(rp) < 1 or len(sg) != R:
+            raise ConexError("Invalid LMI")
+        v = None if variables is None else np.ascontiguousarray(np.asarray(variables).ravel(), dtype=np.int64)
+        if len(rp) - 1 != (self.m if v is None else len(v)):
+            raise ConexError("Invalid LMI")
+        Ff, cf = capi.colmajor(F), capi.colmajor(c)
+        cid = self._L.CONEX_HIP_AddFactoredLMIConstraint(
+            self.a, n, capi.dp(Ff), R, capi.dp(sg), rp.ctypes.data_as(C.POINTER(C.c_int)), len(rp) - 1, capi.dp(cf),
+            None if v is None else v.ctypes.data_as(C.POINTER(C.c_long)))
+        if cid < 0:
+            raise ConexError("Failed to add constraint.")
+        self.A.append(_FactoredLMIOperator(F, rp, sg, self.m, v))
+        self.c.append(c.copy())
+        self.num_constraints += 1
+        return cid
 
     def AddQuadraticConstraint(self, Q, A, c, variables=None):
         """c - A y in {(x0, x1): x0 >= sqrt(x1' Q x1)}: the reference's QuadraticConstraint(Q, A, c), which it reaches

@@ -54,6 +54,63 @@ def lmi_problem(K=1000, n=20, m=20, branching=8, overlap=5, seed=SEED):
     return dict(A=A, C=Cm, cliques=cliques, num_vars=num_vars, b=b, n=n, m=m)
 
 
+def expand_factors(F, rank_ptr, sigma):
+    """The dense matrices of a factored LMI: A_i = sum_k sigma[k] F[:, k] F[:, k]', k in rank_ptr[i]:rank_ptr[i + 1],
+    columns added in increasing k (exactly symmetric: every term is)."""
+    F = np.asarray(F, dtype=np.float64)
+    n, m = F.shape[0], len(rank_ptr) - 1
+    A = np.zeros((m, n, n))
+    for i in range(m):
+        for k in range(rank_ptr[i], rank_ptr[i + 1]):
+            A[i] += sigma[k] * np.outer(F[:, k], F[:, k])
+    return A
+
+
+def factored_lmi_problem(K=4, n=12, ranks=(1,) * 8, branching=2, overlap=2, seed=SEED, signs="plus", nonneg=False,
+                         factors=None):
+    """K low-rank LMIs of order n on the clique tree of lmi_problem, given by factors and expanded.
+
+    ranks: the rank of every A_i (m entries, 0 allowed), or K such lists; member c has F[c] (n x R), rank_ptr[c]
+    (m + 1) and sigma[c] (R).  Vectors are Gaussian, or uniform in [0, 1] with nonneg (then the terms of an A_i do not
+    cancel when its sigma share a sign).  signs: "plus" all +1, "matrix" one random sign per A_i, "mixed" one per
+    column.  factors: K triples (F, rank_ptr, sigma) to use instead.  C is positive definite (y = 0 is strictly
+    feasible) and b_i = sum_c <A_ci, X_c> for positive definite X_c (so is the dual): every program is strictly
+    feasible on both sides.  Returns dict(F, rank_ptr, sigma, A (the expansion), C, cliques, num_vars, b, n, m)."""
+    rng = np.random.default_rng(seed)
+    per = [list(r) for r in ranks] if len(ranks) and np.ndim(ranks[0]) else [list(ranks)] * K
+    m = len(factors[0][1]) - 1 if factors is not None else len(per[0])
+    cliques, num_vars = tree_cliques(K, branching, m, min(overlap, m)) if m else ([[] for _ in range(K)], 0)
+    Fs, ptrs, sigs = [], [], []
+    for c in range(K):
+        if factors is not None:
+            F, ptr, sg = factors[c]
+            F = np.asarray(F, dtype=np.float64).reshape(n, -1)
+            ptr = np.asarray(ptr, dtype=np.int32)
+            sg = np.ones(F.shape[1]) if sg is None else np.asarray(sg, dtype=np.float64)
+        else:
+            ptr = np.concatenate([[0], np.cumsum(per[c])]).astype(np.int32)
+            R = int(ptr[-1])
+            F = rng.uniform(0.0, 1.0, (n, R)) if nonneg else rng.standard_normal((n, R))
+            if signs == "plus":
+                sg = np.ones(R)
+            elif signs == "matrix":
+                sg = np.repeat(rng.choice([-1.0, 1.0], m), per[c])
+            else:
+                sg = rng.choice([-1.0, 1.0], R)
+        Fs.append(F)
+        ptrs.append(ptr)
+        sigs.append(sg)
+    A = np.stack([expand_factors(Fs[c], ptrs[c], sigs[c]) for c in range(K)]) if K else np.zeros((0, m, n, n))
+    Cm = np.empty((K, n, n))
+    b = np.zeros(num_vars)
+    for c in range(K):
+        Cm[c] = np.eye(n) + 0.2 * random_sym(rng, n) / n
+        X = random_sym(rng, n) / n
+        X = X @ X + np.eye(n) / n
+        b[cliques[c]] += np.einsum("iab,ab->i", A[c], X)
+    return dict(F=Fs, rank_ptr=ptrs, sigma=sigs, A=A, C=Cm, cliques=cliques, num_vars=num_vars, b=b, n=n, m=m)
+
+
 def sparsify(prob, density, seed=SEED + 7):
     """Zero all but about `density` of the entries of every A_i of an lmi_problem / hermitian_problem
     (symmetric pattern, the diagonal of the first plane kept with the same probability plus one
@@ -270,6 +327,10 @@ def build(ctx_cls, prob, kind="lmi", **kw):
         p = ctx_cls(prob["num_vars"], **kw)
         for c, cl in enumerate(prob["cliques"]):
             assert p.add_lmi(prob["A"][c], prob["C"][c], cl) == c
+    elif kind == "factored":
+        p = ctx_cls(prob["num_vars"], **kw)
+        for c, cl in enumerate(prob["cliques"]):
+            assert p.add_lmi_factored(prob["F"][c], prob["rank_ptr"][c], prob["sigma"][c], prob["C"][c], cl) == c
     elif kind == "herm":
         p = ctx_cls(prob["num_vars"], **kw)
         for c, cl in enumerate(prob["cliques"]):

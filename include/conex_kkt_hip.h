@@ -216,6 +216,31 @@ double cxk_sparse_soc_setup_ms(const cxk_context* ctx);
 int cxk_add_soc_csr(cxk_context* ctx, int n, int m, const int* rowptr /* n + 2 */, const int* col, const double* val,
                     const double* c /* n + 1 */, const int* vars);
 
+/* Low-rank matrix inequalities given by their factors (kernels_lmi_factored.hip.h).  cxk_add_lmi_factored adds the
+ * constraint of cxk_add_lmi (DenseLMIConstraint semantics, real symmetric) with
+ *   A_i = sum_k sigma_k f_k f_k',  k = rank_ptr[i] .. rank_ptr[i + 1] - 1,
+ * f_k the columns of F (n x R, column-major, R = rank_ptr[m]); sigma = NULL means all +1; rank_ptr[i + 1] == rank_ptr[i]
+ * makes A_i the zero matrix.  The A_i are never formed, on the host or on the device: with Z = W F, P = F' Z, Y = C Z
+ * (three products on the fp64 MFMA GEMM) G(i,j) = sum sigma_k sigma_l P_kl^2, AW(i) = sum sigma_k P_kk,
+ * AQc(i) = sum sigma_k z_k' y_k, and the slack is F diag(sigma_k y_i(k)) F' - kC; O(n^2 R + n R^2) work per assembly
+ * instead of O(n^3 m + n^2 m^2).  Behind the slack the constraint runs the large-order LMI route unchanged, whatever
+ * its order, and every getter, setter and output is that of an LMI (cxk_set_W, cxk_get_W, cxk_dual_size, ..).  Fixed
+ * summation orders, no atomics: two runs give the same bits.  Constraints of equal n, m and R share launches; their
+ * rank_ptr and sigma may differ.
+ * Returns the constraint id, or -1 (cxk_last_error names the reason) for: n < 1, m < 0; null rank_ptr, C or (R > 0) F;
+ * rank_ptr[0] != 0; a decreasing rank_ptr; a value of F, sigma or C that is not finite; a C that is not symmetric.
+ * Refused at cxk_finalize, by name: n > 1024 (the Pade LU of the large-order TakeStep); n R, R R or m m beyond the
+ * int range; more than 65535 such constraints of one shape.
+ * A context holding such a constraint reports cxk_device_mu_supported == 0 and cxk_triple_supported == 0, keeps its
+ * assembly and its tree in separate launches, and cxk_line_search refuses it as it refuses every non-linear cone.
+ * The route is not one of the LMI kernel instances: cxk_lmi_kernels fails for such a constraint and
+ * cxk_count_lmi_kernel does not count it.  cxk_assembly_work counts the route's own flops and bytes.
+ * cxk_count_factored_lmi: constraints this context owns on this route (-1 before cxk_finalize; a host-only context
+ * counts them too: the route is how they were added, not a choice of cxk_finalize). */
+int cxk_add_lmi_factored(cxk_context* ctx, int n, int m, const int* rank_ptr /* m + 1 */, const double* F /* n x R */,
+                         const double* sigma /* R, NULL = all +1 */, const double* C /* n x n */, const int* vars);
+int cxk_count_factored_lmi(const cxk_context* ctx);
+
 /* Quadratic cones { x0 >= sqrt(x1' Q x1) } of real size.  The LDS route (quad_schur, quad_prepare, quad_take_step)
  * gives a cone one workgroup and runs its maps, the products with Q among them, on one thread; a cone whose
  * variables + 4 (dimension + 1) doubles exceed LDS is refused at cxk_finalize.  The streamed route
