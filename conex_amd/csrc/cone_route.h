@@ -1,0 +1,298 @@
+// Which set of kernels a constraint runs on, as ONE pure function of its shape and the modes in force at
+// cxk_finalize; and, for a group of matrix inequalities, how its Schur complement is assembled.  Plain C++17: no
+// HIP, no I/O, no allocation (tests/test_cone_route.py compiles it alone and walks the modes and the shape edges).
+// Also here, because admission and the launch sites must read ONE definition: the dynamic-LDS need of every
+// LDS-resident kernel, and the thresholds of the automatic modes.
+//
+// GroupConstraints (kkt_cone_launch.hip) measures a constraint, asks Choose, and raises the refusal or stores the
+// route; every stage of the cxk_* path then switches on Group::route with a case for every enumerator.
+#pragma once
+#include <climits>
+#include <cstddef>
+#include <cstdint>
+
+#include "../../include/conex_kkt_hip.h"  // the CXK_* constraint types (a C header)
+
+namespace cxk_host {
+
+constexpr size_t kLdsLimit = 160 * 1024 - 512;
+
+// One enumerator per set of kernels.
+enum class ConeRoute {
+  kLinearLds,     // one workgroup per block (kernels_cone.hip.h)
+  kLinearTiled,   // kernels_linear_tiled.hip.h
+  kLinearSparse,  // from the nonzeros (kernels_linear_sparse.hip.h)
+  kSocLds,        // one wavefront per cone, its image in LDS (kernels_cone.hip.h)
+  kSocStreamed,   // held in HBM (kernels_soc_stream.hip.h)
+  kSocSparse,     // from the nonzeros (kernels_soc_sparse.hip.h)
+  kQuadLds,       // one workgroup per cone (kernels_quad.hip.h)
+  kQuadStreamed,  // held in HBM (kernels_quad_stream.hip.h)
+  kLmiDense,      // dense matrices: the LmiKernel choosers name the instance of each stage
+  kLmiSparse,     // from the nonzeros (kernels_lmi_sparse.hip.h)
+  kLmiFactored,   // from the factors, in front of the large-order kernels (kernels_lmi_factored.hip.h)
+  kStatic,        // constant Schur block
+  kOct            // kernels_oct.hip.h
+};
+
+// How a group of matrix inequalities assembles its Schur complement.
+enum class LmiAssembly {
+  kGeneric,  // the route's own kernels (lmi_schur_generic, the sparse sums, the factored products)
+  kMfma,     // lmi_schur_mfma (lmi_fused_mfma.hip)
+  kGemm      // the batched MFMA GEMM pipeline (kernels_lmi_large.hip.h)
+};
+
+// The widest linear block the LDS route can run: linear_line_search is launched with 16 m bytes of dynamic LDS
+// and has the default limit of 64 KB (linear_prepare's 8 m bytes reach it at 8192).
+constexpr int kLinearLdsMaxVars = 4096;
+// Automatic mode sends a linear block of rows x m to the tiled route from rows m^2 >= this on.  Measured
+// (tools/linear_tiled_speed.py against the build before the tiled route): twice the smallest
+// rows m^2 among the measured shapes from which assembly, PrepareStep and the eigenvalue query are each faster on
+// the tiled route at that shape and at every larger one, 2000 x 64 (at 256 x 32 the assembly is five times faster
+// but the two-launch PrepareStep and query cost 2 us more); twice, because the numbers are one box's on one day.
+constexpr long long kTiledLinearMinWork = 2ll * 2000 * 64 * 64;  // 16 384 000
+
+// Automatic mode (cxk_set_sparse_linear(ctx, -1)) sends a linear block to the sparse route when
+// R sum_r nnz_r^2 <= rows m^2: the sparse assembly forms about sum_r nnz_r^2 products one fma at a time, the dense
+// routes rows m^2 on the matrix pipe.  Measured (tools/linear_sparse_speed.py against the build before the sparse
+// route on its own choice): R is twice the smallest rows m^2 / sum_r nnz_r^2 among the measured
+// shapes at which assembly, PrepareStep and the eigenvalue query are each faster on the sparse route, 3.9 at the
+// half-full 2000 x 64; twice, because the numbers are one box's on one day.  A fully dense block (ratio 1) never moves.
+// CXK_SPARSE_LINEAR_MIN_RATIO moves R for comparison runs.  Two more conditions, both from shapes that lost:
+//  - a column's rows are one wavefront's dependent chain, 0.33 us per row (100 000 x 50 with one full column: 32.6 ms
+//    against 0.38 ms): no column longer than kSparseLinearMaxColumn, twice the longest measured to win (about 1050);
+//  - a thousand 20 x 10 blocks with 3 nonzeros per row are 20 % slower at every stage than on the LDS route's one
+//    launch per stage: nothing below the rows m^2 of the smallest measured shape that won, 2000 x 64, moves.
+constexpr double kSparseLinearMinRatio = 7.8;
+constexpr int kSparseLinearMaxColumn = 2048;
+constexpr long long kSparseLinearMinWork = 2000ll * 64 * 64;  // 8 192 000
+inline bool LinearSparsePays(double rows, double m, double sum_nnz_sq, int longest_column, double ratio) {
+  return ratio * sum_nnz_sq <= rows * m * m && rows * m * m >= (double)kSparseLinearMinWork &&
+         longest_column <= kSparseLinearMaxColumn;
+}
+
+// Automatic mode (cxk_set_sparse_soc(ctx, -1)) sends a second-order cone of dimension len = n + 1 over m variables to
+// the sparse route when it can run nowhere else (added by cxk_add_soc_csr, or len m beyond the int range), or when
+// R nnz <= len m and len m^2 >= kSparseSocMinWork: the sparse assembly reads the nnz nonzeros and moves the m x m
+// square twice, the dense routes stream len m entries (and the streamed one multiplies len m^2).  Measured
+// (tools/soc_sparse_speed.py --sweep against the streamed route): each constant is twice the smallest
+// value among the swept shapes at which assembly + query + PrepareStep + TakeStep are faster on the sparse route;
+// twice, because the numbers are one box's on one day.  The smallest winning len m / nnz is 2.02 (2048 x 64 half full:
+// 87.8 us against 129.7 us; the assembly gains 4.3x, the one-thread-per-row slack loses 0.63x); a fully dense 401 x 61
+// loses (87.6 us against 82.7 us) and never moves.  The smallest swept shape, 401 x 61 (len m^2 = 1 492 121), wins at
+// 3 nonzeros per row (51.4 us against 79.7 us); nothing smaller was measured, so nothing smaller moves.
+// CXK_SPARSE_SOC_MIN_RATIO moves R for comparison runs.  No default anywhere asks for this mode.
+constexpr double kSparseSocMinRatio = 4.04;
+constexpr long long kSparseSocMinWork = 2ll * 401 * 61 * 61;  // 2 984 242
+inline bool SocSparsePays(double len, double m, double nnz, double ratio) {
+  return ratio * nnz <= len * m && len * m * m >= (double)kSparseSocMinWork;
+}
+
+// Automatic mode (cxk_set_streamed_quadratic(ctx, -1)) sends a quadratic cone to the streamed route from this many
+// doubles streamed per pass, (Q ? n n : 0) + (n + 1) m, on.  Measured (tools/quad_stream_speed.py):
+// the smallest shape of the sweep, n = 32 with Q over m = 8 (32 * 32 + 33 * 8), where assembly + PrepareStep +
+// TakeStep already take 48 us on the streamed route against 333 us on the LDS route; every larger swept shape gains
+// more.  Nothing smaller was measured, so nothing smaller moves (the cones of a handful of doubles stay where they are).
+constexpr long long kQuadStreamMinWork = 32 * 32 + 33 * 8;  // 1288
+
+// Dynamic LDS of the LDS-resident kernels: what the launch sites ask for and what Choose admits a constraint by,
+// so that an admitted constraint can be launched at every stage.  Every product is taken in size_t.
+inline size_t LmiGenericLds(int n) { return sizeof(double) * 4 * (size_t)n * (size_t)n; }
+inline size_t LmiPrepareLds(int n, int m) { return sizeof(double) * (3 * (size_t)n * n + 6 * (size_t)n + 2 * ((size_t)n / 2 + 2) + m + 8); }
+inline size_t LmiTakeLds(int n) { return sizeof(double) * 5 * (size_t)n * (size_t)n; }
+inline size_t SocSchurLds(int n, int m, bool staged) { return sizeof(double) * ((size_t)n + 1) * (staged ? 2 * (size_t)m + 4 : (size_t)m + 2); }
+inline size_t SocPrepareLds(int n, int m) { return sizeof(double) * ((size_t)m + 3 * ((size_t)n + 1)); }
+inline size_t SocTakeLds(int n) { return sizeof(double) * 4 * ((size_t)n + 1); }
+inline size_t QuadSchurLds(int n, int m) { return sizeof(double) * (2 * (size_t)n + (size_t)m + 4); }
+inline size_t QuadPrepareLds(int n, int m) { return sizeof(double) * ((size_t)m + 4 * ((size_t)n + 1)); }
+inline size_t QuadTakeLds(int n) { return sizeof(double) * 3 * ((size_t)n + 1); }
+// the LDS-resident orders of a matrix inequality: beyond them the large-order kernels (Group::large)
+inline bool LmiLdsResident(int n, int m) { return LmiTakeLds(n) <= kLdsLimit && LmiPrepareLds(n, m) <= kLdsLimit; }
+
+// What is known of one constraint when its route is chosen.
+struct ConeShape {
+  int type = 0, n = 0, m = 0, herm_d = 0;  // CXK_LMI ..., the sizes as cxk_add_* took them
+  bool symmetric = true;  // CXK_LMI: every A_i and C equals its transpose
+  // added by its nonzeros (no dense matrix); CXK_LMI given by factors; CXK_QUAD with an inner-product matrix
+  bool csr_only = false, factored = false, has_q = false;
+  // the nonzeros of a linear block or a second-order cone, measured only while its sparse mode is not 0
+  bool nnz_fits_int = true;  // their count is within the int range
+  double nnz = 0;            // their count
+  double sum_nnz_sq = 0;     // sum over the rows of the squared count
+  int longest_column = 0;
+  // CXK_LMI: the predicates that live beside the kernels, already evaluated
+  bool mfma_supports = false;  // LmiMfmaSupports(n, m, herm_d)
+  bool sparse_pays = false;    // LmiSparsePays(n, m, nonzeros of A, LmiLdsResident(n, m), mfma_supports)
+};
+
+// The modes in force: what the context was told (cxk_set_*), else the environment's word, else the default here
+// (GroupConstraints resolves them once), and the thresholds of the automatic ones.
+struct RouteModes {
+  bool streamed_cones = false;  // CXK_STREAMED_CONES=1: second-order cones beyond LDS are held in HBM (else refused)
+  int tiled_linear = -1;        // CXK_TILED_LINEAR: -1 by size, 0 never, 1 every block
+  int streamed_quadratic = 0;   // CXK_STREAMED_QUADRATIC: -1 by size, 0 never, 1 every cone
+  int sparse_linear = 0;        // CXK_SPARSE_LINEAR: -1 by pattern, 0 never, 1 every block
+  int sparse_soc = 0;           // CXK_SPARSE_SOC: -1 by pattern, 0 never, 1 every cone
+  int sparse_lmi = -1;          // CXK_SPARSE_LMI: -1 when it pays, 0 never, 1 always (tests)
+  long long tiled_linear_min_work = kTiledLinearMinWork;            // CXK_TILED_LINEAR_MIN_WORK (comparison runs)
+  long long streamed_quadratic_min_work = kQuadStreamMinWork;       // CXK_STREAMED_QUADRATIC_MIN_WORK (comparison runs)
+  double sparse_linear_min_ratio = kSparseLinearMinRatio;           // CXK_SPARSE_LINEAR_MIN_RATIO (comparison runs)
+  double sparse_soc_min_ratio = kSparseSocMinRatio;                 // CXK_SPARSE_SOC_MIN_RATIO (comparison runs)
+};
+
+// The route, or why there is none (`refusal` is the message cxk_finalize fails with; null with a route).
+struct RouteChoice {
+  ConeRoute route;
+  const char* refusal;
+};
+
+namespace route_detail {
+constexpr RouteChoice Take(ConeRoute r) { return RouteChoice{r, nullptr}; }
+constexpr RouteChoice Refuse(const char* why) { return RouteChoice{ConeRoute::kStatic, why}; }
+// (rows x max(m, 1) entries indexed with ints by the kernels and by the GEMM)
+inline bool EntriesFitInt(int64_t rows, int m) { return rows * (m > 1 ? m : 1) <= INT_MAX - 1024; }
+inline bool SquareFitsInt(int m) { return (int64_t)m * m <= INT_MAX; }
+
+inline RouteChoice ChooseLinear(const ConeShape& s, const RouteModes& md) {
+  if (s.csr_only && md.sparse_linear == 0)
+    return Refuse("a linear block added by cxk_add_linear_csr has no dense matrix and can only take the sparse route "
+                  "(cxk_set_sparse_linear / CXK_SPARSE_LINEAR, which is 0)");
+  if (!s.nnz_fits_int && md.sparse_linear == 1)  // (the pointers are ints)
+    return Refuse("a sparse linear block with more than 2^31 nonzeros is not supported");
+  bool sparse = s.csr_only || md.sparse_linear == 1;
+  // automatic mode yields to an explicit tiled mode, which asks for the dense kernels
+  if (md.sparse_linear == -1 && !s.csr_only && md.tiled_linear < 0 && s.nnz_fits_int)
+    sparse = LinearSparsePays(s.n, s.m, s.sum_nnz_sq, s.longest_column, md.sparse_linear_min_ratio);
+  if (sparse) {
+    if (!SquareFitsInt(s.m))
+      return Refuse("a sparse linear block whose variables x variables Schur block exceeds the int range is not supported");
+    return Take(ConeRoute::kLinearSparse);
+  }
+  const bool tiled = md.tiled_linear >= 0 ? md.tiled_linear != 0
+                                          : s.m > kLinearLdsMaxVars ||
+                                                (double)s.n * s.m * s.m >= (double)md.tiled_linear_min_work;
+  if (tiled) {
+    // what remains is the int indexing of the kernels and of the GEMM
+    if (!EntriesFitInt(s.n, s.m))
+      return Refuse("a tiled linear block whose rows x variables entries exceed the int range is not supported");
+    if (!SquareFitsInt(s.m))
+      return Refuse("a tiled linear block whose variables x variables Schur block exceeds the int range is not supported");
+    return Take(ConeRoute::kLinearTiled);
+  }
+  // linear_line_search keeps two vectors of m doubles in 64 KB of dynamic LDS
+  if (s.m > kLinearLdsMaxVars)
+    return Refuse("a linear block over more than 4096 variables does not fit the LDS route's kernels: it needs the tiled "
+                  "route (cxk_set_tiled_linear / CXK_TILED_LINEAR, which was set to 0)");
+  return Take(ConeRoute::kLinearLds);
+}
+
+inline RouteChoice ChooseSoc(const ConeShape& s, const RouteModes& md) {
+  if (s.csr_only && md.sparse_soc == 0)
+    return Refuse("a second-order cone added by cxk_add_soc_csr has no dense matrix and can only take the sparse route "
+                  "(cxk_set_sparse_soc / CXK_SPARSE_SOC, which is 0)");
+  if (!s.nnz_fits_int && md.sparse_soc == 1)  // (the pointers are ints)
+    return Refuse("a sparse second-order cone with more than 2^31 nonzeros is not supported");
+  // (a dense route indexes the (n + 1) x m entries with ints)
+  const bool dense_ok = EntriesFitInt((int64_t)s.n + 1, s.m);
+  bool sparse = s.csr_only || md.sparse_soc == 1;
+  if (md.sparse_soc == -1 && !s.csr_only && s.nnz_fits_int)
+    sparse = !dense_ok || SocSparsePays((double)s.n + 1, s.m, s.nnz, md.sparse_soc_min_ratio);
+  if (sparse) {
+    // held as nonzeros: no LDS room, no streamed switch; what remains is the int indexing of the m x m squares H and G
+    if (!SquareFitsInt(s.m))
+      return Refuse("a sparse second-order cone whose variables x variables Schur block exceeds the int range is not supported");
+    return Take(ConeRoute::kSocSparse);
+  }
+  const bool steps_fit = SocTakeLds(s.n) <= kLdsLimit && SocPrepareLds(s.n, s.m) <= kLdsLimit;
+  const bool image_fits = SocSchurLds(s.n, s.m, false) <= kLdsLimit;
+  if (md.streamed_cones && !(image_fits && steps_fit)) {
+    // held in HBM: what remains is the int indexing of the kernels and of the GEMM
+    if (!dense_ok)
+      return Refuse("a streamed second-order cone whose (dimension + 1) x variables entries exceed the int range is not supported");
+    if (!SquareFitsInt(s.m))
+      return Refuse("a streamed second-order cone whose variables x variables Schur block exceeds the int range is not supported");
+    return Take(ConeRoute::kSocStreamed);
+  }
+  // soc_schur keeps a cone's (n + 1) x (m + 2) image in LDS (CONEX_NewLorentzConeConstraint makes a
+  // cone's matrix as wide as its largest variable index: thousands of columns are possible there)
+  if (!image_fits)
+    return Refuse("a second-order cone whose (dimension + 1) x (variables + 2) image exceeds LDS (160 KB) is not supported");
+  // soc_take_step keeps four vectors of the cone in LDS, soc_prepare three and y: with one variable
+  // they, not the image above, are what has to fit
+  if (!steps_fit)
+    return Refuse("a second-order cone whose step kernels need more than the 163 328 B of LDS (four vectors of dimension + 1) is "
+                  "not supported");
+  return Take(ConeRoute::kSocLds);
+}
+
+inline RouteChoice ChooseQuad(const ConeShape& s, const RouteModes& md) {
+  // quad_prepare keeps y and four vectors of the cone in LDS; quad_schur and quad_take_step need less
+  const bool fits = QuadPrepareLds(s.n, s.m) <= kLdsLimit && QuadSchurLds(s.n, s.m) <= kLdsLimit && QuadTakeLds(s.n) <= kLdsLimit;
+  const double work = (s.has_q ? (double)s.n * s.n : 0.0) + ((double)s.n + 1) * s.m;  // doubles streamed per pass
+  const bool streamed = md.streamed_quadratic >= 0 ? md.streamed_quadratic != 0
+                                                   : !fits || work >= (double)md.streamed_quadratic_min_work;
+  if (streamed) {
+    // held in HBM: what remains is the int indexing of the kernels and of the GEMM
+    if (!EntriesFitInt((int64_t)s.n + 1, s.m))
+      return Refuse("a streamed quadratic cone whose (dimension + 1) x variables entries exceed the int range is not supported");
+    if (!SquareFitsInt(s.m))
+      return Refuse("a streamed quadratic cone whose variables x variables Schur block exceeds the int range is not supported");
+    if (s.has_q && !SquareFitsInt(s.n))
+      return Refuse("a streamed quadratic cone whose inner-product matrix has more than 2^31 entries is not supported");
+    return Take(ConeRoute::kQuadStreamed);
+  }
+  if (!fits)
+    return Refuse("a quadratic cone whose step kernels need more than the 163 328 B of LDS (variables + four vectors of "
+                  "dimension + 1) is not supported");
+  return Take(ConeRoute::kQuadLds);
+}
+
+inline RouteChoice ChooseLmi(const ConeShape& s, const RouteModes& md) {
+  // held by its factors in front of the large-order route (cxk_finalize has checked the order and the int indexing
+  // of the kernels)
+  if (s.factored) return Take(ConeRoute::kLmiFactored);
+  // The reference accepts non-symmetric matrices and evaluates <W A_i W, A_j> as written; only the literal LDS
+  // kernels do the same.
+  if (!s.symmetric && !LmiLdsResident(s.n, s.m))
+    return Refuse("non-symmetric LMI data beyond the LDS-resident orders is not supported: "
+                  "the large-order kernels use tr(W A_i W A_j) = tr(P_i P_j), which needs A_i = A_i^T");
+  // sparse evaluation when it pays (CXK_SPARSE_LMI=0 / 1 forces never / always: tests); its entries are packed
+  // row | col << 16
+  const bool sparse = (md.sparse_lmi >= 0 ? md.sparse_lmi != 0 : s.sparse_pays) && s.n <= 65535 && s.symmetric;
+  return Take(sparse ? ConeRoute::kLmiSparse : ConeRoute::kLmiDense);
+}
+}  // namespace route_detail
+
+inline RouteChoice Choose(const ConeShape& shape, const RouteModes& modes) {
+  switch (shape.type) {
+    case CXK_LMI: return route_detail::ChooseLmi(shape, modes);
+    case CXK_LINEAR: return route_detail::ChooseLinear(shape, modes);
+    case CXK_SOC: return route_detail::ChooseSoc(shape, modes);
+    case CXK_QUAD: return route_detail::ChooseQuad(shape, modes);
+    case CXK_OCT: return route_detail::Take(ConeRoute::kOct);
+    default: return route_detail::Take(ConeRoute::kStatic);
+  }
+}
+
+// The assembly of a group of `count` matrix inequalities on `route`, and whether the group runs on the large-order
+// kernels (HBM-resident matrices).  Shapes past the register kernels' instances assemble through the batched GEMM
+// (measured 1.5 - 3.3x faster than lmi_schur_generic at 1000 constraints: orders 25 up, and smaller orders with
+// more variables than lmi_schur_mfma's LDS images hold, e.g. order 22, m = 20 285 -> 133 us, order 10, m = 60
+// 496 -> 148 us; CXK_GEMM_MIN_N moves the threshold for comparison runs), while its work space stays within 8 GB.
+struct LmiAssemblyChoice {
+  bool large;
+  LmiAssembly assembly;
+};
+inline LmiAssemblyChoice ChooseLmiAssembly(ConeRoute route, int n, int m, size_t count, bool literal, bool mfma_supports,
+                                           bool schur_generic, int gemm_min_n) {
+  // held by its factors in front of the large-order route, whatever its order
+  if (route == ConeRoute::kLmiFactored) return {true, LmiAssembly::kGeneric};
+  const bool large = !LmiLdsResident(n, m);
+  if (route != ConeRoute::kLmiDense || literal) return {large, LmiAssembly::kGeneric};
+  if (large) return {true, LmiAssembly::kGemm};
+  if (!schur_generic && mfma_supports) return {false, LmiAssembly::kMfma};
+  const bool gemm = n >= gemm_min_n &&
+                    count * 2 * ((size_t)m + 1) * (size_t)n * (size_t)n * sizeof(double) <= ((size_t)8 << 30);
+  return {false, gemm ? LmiAssembly::kGemm : LmiAssembly::kGeneric};
+}
+
+}  // namespace cxk_host

@@ -22,27 +22,134 @@
 
 namespace cxk_host {
 
+// ---- The views the kernels take of a group, each beside the stage of cxk_finalize (UploadGroup) that allocates what
+// it lays out, so that a layout and its size are read together.  What those stages call further down:
+int UploadSparseLmi(cxk_context* ctx, Group& g);
+int QuadStreamConstants(cxk_context* ctx, Group& g);
+int SocSparseConstants(cxk_context* ctx, Group& g);
+static int UploadSparseNonzeros(cxk_context* ctx, Group& g);
+static int SocSparseGramChunks(int m);
+static int SocSparseCombineTiles(int m);
+
 LmiGroup MakeLmi(Group& g) {
   LmiGroup d;
   d.n = g.n;
   d.m = g.m;
   d.count = static_cast<int>(g.ids.size());
   d.A = g.A.p;
-  d.a_stride = (long long)((g.mfma || g.schur_gemm) ? g.m + 1 : g.m) * g.n * g.n;
+  d.a_stride = (long long)(g.assembly != LmiAssembly::kGeneric ? g.m + 1 : g.m) * g.n * g.n;
   d.C = g.C.p;
   d.W = g.W.p;
   d.T1 = g.T1.p;
   d.ids = g.dids.p;
   d.Apk = g.Apk.n ? g.Apk.p : nullptr;
   d.herm_d = g.herm_d;
-  d.sp_eptr = g.sparse ? g.sp_eptr.p : nullptr;
-  d.sp_erc = g.sparse ? g.sp_erc.p : nullptr;
-  d.sp_pairs = g.sparse ? g.sp_pairs.p : nullptr;
-  d.sp_eval = g.sparse ? g.sp_eval.p : nullptr;
-  d.sp_pptr = g.sparse ? g.sp_pptr.p : nullptr;
-  d.sp_pvar = g.sparse ? g.sp_pvar.p : nullptr;
-  d.sp_pval = g.sparse ? g.sp_pval.p : nullptr;
+  const bool sparse = g.route == ConeRoute::kLmiSparse;
+  d.sp_eptr = sparse ? g.sp_eptr.p : nullptr;
+  d.sp_erc = sparse ? g.sp_erc.p : nullptr;
+  d.sp_pairs = sparse ? g.sp_pairs.p : nullptr;
+  d.sp_eval = sparse ? g.sp_eval.p : nullptr;
+  d.sp_pptr = sparse ? g.sp_pptr.p : nullptr;
+  d.sp_pvar = sparse ? g.sp_pvar.p : nullptr;
+  d.sp_pval = sparse ? g.sp_pval.p : nullptr;
   return d;
+}
+// Doubles of one member's A, C and W (T1, T2 and the quadratic cone's S are W's size).
+struct GroupSizes {
+  size_t a = 0, c = 0, w = 0;
+};
+static GroupSizes SizesOf(const Group& g) {
+  const size_t n = (size_t)g.n, m = (size_t)g.m;
+  switch (g.type) {
+    case CXK_LMI: return {m * n * n, n * n, n * n};
+    case CXK_LINEAR: return {n * m, n, n};
+    case CXK_SOC: case CXK_QUAD: return {(n + 1) * m, n + 1, n + 1};
+    case CXK_STATIC: return {m * m, m, 0};  // constant AQc (zeros for a quadratic-cost block)
+    case CXK_OCT: return {m * 8 * n * n, 8 * n * n, 8 * n * n};
+  }
+  return {};
+}
+// The dense A and C of every member as the kernels of every route but the sparse and factored ones read them
+// (`a_sz` 0: no dense copy of A on the device).
+static int UploadDenseData(cxk_context* ctx, Group& g, size_t a_sz, size_t c_sz) {
+  const size_t cnt = g.ids.size();
+  // lmi_schur_mfma reads [A_1 .. A_m | C] of a constraint as one contiguous array of stacked
+  // rows: such groups keep a copy of C right behind the A_i (LmiGroup::a_stride)
+  const size_t a_blk = a_sz + (g.assembly != LmiAssembly::kGeneric ? c_sz : 0);
+  std::vector<double> hA(a_blk * cnt), hC(c_sz * cnt);
+  for (size_t k = 0; k < cnt; k++) {
+    const ConstraintRec& c = ctx->cons[g.ids[k]];
+    if (a_sz) std::copy(c.A.begin(), c.A.end(), hA.begin() + k * a_blk);
+    if (a_blk > a_sz) std::copy(c.C.begin(), c.C.end(), hA.begin() + k * a_blk + a_sz);
+    std::copy(c.C.begin(), c.C.end(), hC.begin() + k * c_sz);
+  }
+  CXK_TRY(g.A.upload(hA));
+  CXK_TRY(g.C.upload(hC));
+  return CXK_SUCCESS;
+}
+static int AllocGemmAssembly(cxk_context* ctx, Group& g, const FinalizeSwitches& sw);
+// The three side copies of a dense LMI group's matrices: Apad (lmi_schur_mfma at a padded order), Aleft (the folded
+// form of a Hermitian group on the GEMM assembly), Apk (the packed lower triangles of the slack pass); then the work
+// space of the GEMM assembly (beside MakeLargeWs).
+static int UploadLmiDense(cxk_context* ctx, Group& g, const FinalizeSwitches& sw) {
+  const size_t cnt = g.ids.size();
+  if (g.assembly == LmiAssembly::kMfma && LmiMfmaPaddedOrder(g.n) != g.n && !(g.herm_d == 2 && g.n == 24)) {
+    const int np = LmiMfmaPaddedOrder(g.n), n = g.n;
+    const size_t blk = (size_t)(g.m + 1) * np * np;
+    std::vector<double> hp(blk * cnt, 0.0);
+    for (size_t k = 0; k < cnt; k++) {
+      const ConstraintRec& c = ctx->cons[g.ids[k]];
+      for (int i = 0; i <= g.m; i++) {
+        const double* src = i < g.m ? c.A.data() + (size_t)i * n * n : c.C.data();
+        double* dst = hp.data() + k * blk + (size_t)i * np * np;
+        for (int col = 0; col < n; col++) std::copy(src + (size_t)col * n, src + (size_t)col * n + n, dst + (size_t)col * np);
+      }
+    }
+    CXK_TRY(g.Apad.upload(hp));
+  }
+  if (g.herm_d > 1 && g.assembly == LmiAssembly::kGemm && !g.literal && !sw.no_herm_fold) {
+    // Hermitian cones over C / H on the batched-GEMM assembly: the folded form needs only the first
+    // n / herm_d columns of every matrix of the real representation (kernels_lmi_large.hip.h)
+    const int n = g.n, n0 = g.n / g.herm_d;
+    const size_t per = (size_t)n * n0, m1 = (size_t)g.m + 1;
+    std::vector<double> hl(per * m1 * cnt);
+    for (size_t k = 0; k < cnt; k++) {
+      const ConstraintRec& c = ctx->cons[g.ids[k]];
+      for (size_t i = 0; i < m1; i++) {
+        const double* src = i < (size_t)g.m ? c.A.data() + i * (size_t)n * n : c.C.data();
+        std::copy(src, src + per, hl.begin() + (k * m1 + i) * per);
+      }
+    }
+    CXK_TRY(g.Aleft.upload(hl));
+  }
+  if (!g.literal && !sw.no_packed_slack && g.n == 20 && LmiPrepareRowsSupports(g.n, g.m, g.herm_d, false)) {
+    // the slack pass of PrepareStep / the eigenvalue query streams every A_i once more per call: a
+    // packed copy of the lower triangles (the data is exactly symmetric) halves those bytes
+    const int n = g.n, pk = n * (n + 1) / 2;
+    std::vector<double> hp((size_t)pk * g.m * cnt);
+    for (size_t k = 0; k < cnt; k++) {
+      const ConstraintRec& c = ctx->cons[g.ids[k]];
+      for (int i = 0; i < g.m; i++) {
+        const double* src = c.A.data() + (size_t)i * n * n;
+        double* dst = hp.data() + (k * g.m + i) * (size_t)pk;
+        for (int col = 0; col < n; col++)
+          for (int row = col; row < n; row++) *dst++ = src[row + (size_t)col * n];
+      }
+    }
+    CXK_TRY(g.Apk.upload(hp));
+  }
+  return g.assembly == LmiAssembly::kGemm ? AllocGemmAssembly(ctx, g, sw) : CXK_SUCCESS;
+}
+// A sparse LMI group: its entry lists, and beyond the LDS-resident shapes the large-order work space.
+static int UploadLmiSparse(cxk_context* ctx, Group& g) {
+  const size_t cnt = g.ids.size(), nn = (size_t)g.n * g.n;
+  if (UploadSparseLmi(ctx, g)) return CXK_FAILURE;
+  if (g.large || !g.sp_small) {
+    CXK_TRY(g.ws_main.alloc(cnt * 8 * nn));  // step temporaries; C W and W C W during assembly
+    CXK_TRY(g.ws_part.alloc(cnt * 2 * kSparseCParts));
+    CXK_TRY(g.ws_piv.alloc(cnt * (size_t)g.n));
+  }
+  return CXK_SUCCESS;
 }
 QuadGroup MakeQuad(Group& g) {
   QuadGroup d;
@@ -58,6 +165,36 @@ QuadGroup MakeQuad(Group& g) {
   d.S = g.qS.p;
   d.ids = g.dids.p;
   return d;
+}
+// A_gram = A1' (Q A1) of a group of quadratic cones on the LDS route, made once on the host
+// (QuadraticConstraintBase::Initialize, quadratic_cone_constraint.cc:216-219), Q, and the state S.
+static int UploadQuadGram(cxk_context* ctx, Group& g) {
+  const size_t cnt = g.ids.size();
+  const int n = g.n, m = g.m, len = n + 1;
+  std::vector<double> hQ(g.has_q ? (size_t)n * n * cnt : 0), hG((size_t)m * m * cnt, 0.0), qa((size_t)n);
+  for (size_t k = 0; k < cnt; k++) {
+    const ConstraintRec& c = ctx->cons[g.ids[k]];
+    if (g.has_q) std::copy(c.Q.begin(), c.Q.end(), hQ.begin() + k * (size_t)n * n);
+    for (int j = 0; j < m; j++) {
+      const double* aj = c.A.data() + (size_t)j * len + 1;
+      for (int i = 0; i < n; i++) {
+        double s2 = g.has_q ? 0.0 : aj[i];
+        if (g.has_q)
+          for (int q2 = 0; q2 < n; q2++) s2 += c.Q[(size_t)q2 * n + i] * aj[q2];
+        qa[(size_t)i] = s2;
+      }
+      for (int i = 0; i < m; i++) {
+        const double* ai = c.A.data() + (size_t)i * len + 1;
+        double s2 = 0;
+        for (int q2 = 0; q2 < n; q2++) s2 += ai[q2] * qa[(size_t)q2];
+        hG[k * (size_t)m * m + (size_t)j * m + i] = s2;
+      }
+    }
+  }
+  CXK_TRY(g.qQ.upload(hQ));
+  CXK_TRY(g.qGram.upload(hG));
+  CXK_TRY(g.qS.alloc((size_t)len * cnt));
+  return CXK_SUCCESS;
 }
 OctGroup MakeOct(Group& g) {
   OctGroup d;
@@ -96,6 +233,27 @@ SocStreamGroup MakeSocStream(Group& g) {
   d.Gf = g.ws_gf.p;
   return d;
 }
+// The work space of the Gram product of LaunchGramLower, for streamed second-order cones (len = n + 1) and tiled
+// linear blocks (len = n) alike: the scaled copy of A in ws_main, the products in ws_gf, the split partials in ws_part.
+static int AllocGramWorkspace(cxk_context* ctx, Group& g, size_t len, const FinalizeSwitches& sw) {
+  const size_t cnt = g.ids.size(), m = (size_t)g.m;
+  g.splits = SocStreamSplits((int)len, g.m, (long long)cnt);
+  if (sw.gram_splits > 0) g.splits = sw.gram_splits;  // (comparison runs)
+  CXK_TRY(g.ws_main.alloc(cnt * len * m));
+  CXK_TRY(g.ws_gf.alloc(cnt * m * m));
+  CXK_TRY(g.ws_part.alloc(g.splits > 1 ? (size_t)g.splits * std::min<size_t>(cnt, 65535) * m * m : 0));
+  return CXK_SUCCESS;
+}
+static int UploadSocStream(cxk_context* ctx, Group& g, const FinalizeSwitches& sw) {
+  const size_t cnt = g.ids.size(), len = (size_t)g.n + 1, m = (size_t)g.m;
+  CXK_DEMAND(cnt * std::max<size_t>(m, (len + kSocStreamRowTile - 1) / kSocStreamRowTile) <= (size_t)INT_MAX,
+             "a group of streamed second-order cones with more than 2^31 columns or row tiles is not supported");
+  g.st_stages = sw.soc_stream_stages;
+  if (AllocGramWorkspace(ctx, g, len, sw)) return CXK_FAILURE;
+  CXK_TRY(g.st_vec.alloc(3 * cnt * len));
+  CXK_TRY(g.st_det.alloc(cnt));
+  return CXK_SUCCESS;
+}
 QuadStreamGroup MakeQuadStream(Group& g) {
   QuadStreamGroup d;
   const size_t cnt = g.ids.size(), n = (size_t)g.n, m = (size_t)g.m;
@@ -112,7 +270,7 @@ QuadStreamGroup MakeQuadStream(Group& g) {
   d.S = g.qS.p;
   d.ids = g.dids.p;
   d.part = g.ws_part.p;
-  double* p = g.st_vec.p;  // (the layout UploadGroup sizes: QuadStreamVecDoubles)
+  double* p = g.st_vec.p;  // (the layout UploadQuadStream sizes: QuadStreamVecDoubles)
   d.qc1 = p;
   d.qw = (p += cnt * n);
   d.dv = (p += cnt * n);
@@ -125,6 +283,27 @@ QuadStreamGroup MakeQuadStream(Group& g) {
   return d;
 }
 size_t QuadStreamVecDoubles(size_t cnt, size_t n, size_t m) { return cnt * (4 * n + (n + 1) + 2 * m + 8 + 1); }
+// A group of streamed quadratic cones: Q as it is, the work space, and the constants (Q c1, c1' Q c1, A_gram) on the
+// device (QuadStreamConstants).
+static int UploadQuadStream(cxk_context* ctx, Group& g, const FinalizeSwitches& sw) {
+  const size_t cnt = g.ids.size();
+  const size_t n = (size_t)g.n, m = (size_t)g.m, tiles = (n + kQuadStreamRowTile - 1) / kQuadStreamRowTile;
+  g.splits = g.has_q ? QuadStreamSplits(g.n, (long long)cnt) : 1;
+  if (g.has_q && sw.gram_splits > 0) g.splits = sw.gram_splits;  // (comparison runs)
+  CXK_DEMAND(cnt * std::max<size_t>(std::max<size_t>(m, (m * m + kQuadStreamBlock - 1) / kQuadStreamBlock),
+                                    std::max<size_t>(tiles * (size_t)g.splits, (n + 1 + kSocStreamRowTile - 1) / kSocStreamRowTile)) <=
+                 (size_t)INT_MAX,
+             "a group of streamed quadratic cones with more than 2^31 columns, row tiles or blocks is not supported");
+  std::vector<double> hQ(g.has_q ? n * n * cnt : 0);
+  if (g.has_q)
+    for (size_t k = 0; k < cnt; k++) std::copy(ctx->cons[g.ids[k]].Q.begin(), ctx->cons[g.ids[k]].Q.end(), hQ.begin() + k * n * n);
+  CXK_TRY(g.qQ.upload(hQ));
+  CXK_TRY(g.qGram.alloc(m * m * cnt));
+  CXK_TRY(g.qS.alloc((n + 1) * cnt));
+  CXK_TRY(g.st_vec.alloc(QuadStreamVecDoubles(cnt, n, m)));
+  CXK_TRY(g.ws_part.alloc(g.has_q ? cnt * (size_t)g.splits * 2 * n : 0));
+  return QuadStreamConstants(ctx, g);
+}
 // soc_stream_slack serves the streamed quadratic cone as it is (same layout, same formula): what it reads of the group.
 SocStreamGroup QuadStreamSlackView(Group& g, const QuadStreamGroup& d) {
   SocStreamGroup s{};
@@ -140,6 +319,14 @@ LinTiledGroup MakeLinTiled(Group& g) {
   d.part = g.lt_part.p;
   return d;
 }
+static int UploadLinearTiled(cxk_context* ctx, Group& g, const FinalizeSwitches& sw) {
+  const size_t cnt = g.ids.size(), len = (size_t)g.n, m = (size_t)g.m, tiles = (len + kLinTiledRowTile - 1) / kLinTiledRowTile;
+  CXK_DEMAND(cnt * std::max(m, tiles) <= (size_t)INT_MAX,
+             "a group of tiled linear blocks with more than 2^31 columns or row tiles is not supported");
+  if (AllocGramWorkspace(ctx, g, len, sw)) return CXK_FAILURE;
+  CXK_TRY(g.lt_part.alloc(cnt * tiles * 4));
+  return CXK_SUCCESS;
+}
 LinSparseGroup MakeLinSparse(Group& g) {
   LinSparseGroup d;
   d.t = MakeLinTiled(g);  // (A is null, WA and Gf unused: the scalars and finish kernels read v and part only)
@@ -152,11 +339,20 @@ LinSparseGroup MakeLinSparse(Group& g) {
   d.cval = g.ls_cval.p;
   return d;
 }
+static int UploadLinearSparse(cxk_context* ctx, Group& g) {
+  const size_t cnt = g.ids.size(), len = (size_t)g.n, m = (size_t)g.m, tiles = (len + kLinTiledRowTile - 1) / kLinTiledRowTile;
+  const size_t chunks = m <= (size_t)kLinSparseWaveCols ? 1 : (m + kLinSparseColChunk - 1) / kLinSparseColChunk;
+  if (UploadSparseNonzeros(ctx, g)) return CXK_FAILURE;
+  CXK_DEMAND(cnt * std::max(m * chunks, tiles) <= (size_t)INT_MAX,
+             "a group of sparse linear blocks with more than 2^31 column chunks or row tiles is not supported");
+  CXK_TRY(g.lt_part.alloc(cnt * tiles * 4));
+  return CXK_SUCCESS;
+}
 SocSparseGroup MakeSocSparse(Group& g) {
   SocSparseGroup d{};
   const size_t cnt = g.ids.size(), len = (size_t)g.n + 1, m = (size_t)g.m;
   d.st.v = MakeVec(g);  // (A is null; WA, wc, dets and Gf stay null: the step kernels read v, s and ms only)
-  double* p = g.st_vec.p;  // (the layouts UploadGroup sizes: SocSparseVecDoubles, SocSparseConstDoubles)
+  double* p = g.st_vec.p;  // (the layouts UploadSocSparse sizes: SocSparseVecDoubles, SocSparseConstDoubles)
   d.st.s = p;
   d.st.ms = (p += cnt * len);
   d.u = (p += cnt * len);
@@ -176,6 +372,18 @@ SocSparseGroup MakeSocSparse(Group& g) {
 }
 size_t SocSparseVecDoubles(size_t cnt, size_t len, size_t m) { return cnt * (2 * len + m + 2); }
 size_t SocSparseConstDoubles(size_t cnt, size_t m) { return cnt * (m * m + m + 1); }
+// A group of sparse second-order cones: the nonzeros, the work space, and the constants on the device (SocSparseConstants).
+static int UploadSocSparse(cxk_context* ctx, Group& g) {
+  const size_t cnt = g.ids.size(), len = (size_t)g.n + 1, m = (size_t)g.m, tiles = (len + kSocStreamRowTile - 1) / kSocStreamRowTile;
+  if (UploadSparseNonzeros(ctx, g)) return CXK_FAILURE;
+  CXK_DEMAND(cnt * std::max(std::max(m * (size_t)SocSparseGramChunks(g.m), tiles), (size_t)SocSparseCombineTiles(g.m)) <=
+                 (size_t)INT_MAX,
+             "a group of sparse second-order cones with more than 2^31 column chunks, row tiles or tiles of the Schur "
+             "block is not supported");
+  CXK_TRY(g.st_vec.alloc(SocSparseVecDoubles(cnt, len, m)));
+  CXK_TRY(g.ss_const.alloc(SocSparseConstDoubles(cnt, m)));
+  return SocSparseConstants(ctx, g);
+}
 StaticGroup MakeStatic(Group& g) {
   StaticGroup d;
   d.m = g.m;
@@ -196,11 +404,8 @@ Arena MakeArena(cxk_context* ctx) {
   return a;
 }
 StepArgs MakeStep(cxk_context* ctx, double* info, int affine, double cw, double ew, double ss) {
-  StepArgs s;
+  StepArgs s{};  // (no three-part direction, no step length, cost weight or skip flag from the device: null)
   s.y = ctx->y.p;
-  s.y3 = nullptr;
-  s.y3_stride = 0;
-  s.y3_k = nullptr;
   s.cl_ptr = ctx->cl_ptr.p;
   s.cl_perm = ctx->cl_perm.p;
   s.info = info;
@@ -208,11 +413,7 @@ StepArgs MakeStep(cxk_context* ctx, double* info, int affine, double cw, double 
   s.c_weight = cw;
   s.e_weight = ew;
   s.step_size = ss;
-  s.step_from = nullptr;
-  s.cw_from = nullptr;
   s.cw_scale = 1.0;
-  s.skip_if = nullptr;
-  s.skip_tag = 0;
   s.call = ctx->lanczos_calls;
   s.no_clamp = ctx->reference_identity > 0;
   return s;
@@ -233,6 +434,24 @@ LmiLargeWs MakeLargeWs(Group& g) {
   return w;
 }
 
+// The work space of the batched-GEMM assembly (P and P' in ws_main, which the step kernels of a large group reuse),
+// and the number of K splits of its contraction.
+static int AllocGemmAssembly(cxk_context* ctx, Group& g, const FinalizeSwitches& sw) {
+  const size_t cnt = g.ids.size(), nn = (size_t)g.n * g.n, m1 = (size_t)g.m + 1;
+  // split-K of the contraction: enough workgroups to fill the chip, at most one K step each
+  const int ksteps = (int)((nn + kGemmBK - 1) / kGemmBK);
+  const int tiles = (int)(((m1 + 63) / 64) * ((m1 + 63) / 64));
+  // (measured on BASELINE config 2, one constraint, K = 40 000: 39 / 78 / 156 / 312 / 512 / 768 / 1024
+  // splits -> 115 / 93 / 82 / 81 / 76 / 80 / 82 us per KKT solve)
+  g.splits = std::max(1, std::min(std::max(1, ksteps / 4), (int)((512 + cnt * tiles - 1) / (cnt * tiles))));
+  if (sw.gram_splits > 0) g.splits = sw.gram_splits;  // (comparison runs)
+  CXK_TRY(g.ws_main.alloc(cnt * std::max(2 * m1 * nn, 8 * nn)));
+  CXK_TRY(g.ws_gf.alloc(cnt * m1 * m1));
+  CXK_TRY(g.ws_piv.alloc(cnt * (size_t)g.n));
+  CXK_TRY(g.ws_part.alloc(g.splits > 1 ? (size_t)g.splits * cnt * m1 * m1 : 0));
+  return CXK_SUCCESS;
+}
+
 LmiFactoredGroup MakeLmiFactored(Group& g) {
   LmiFactoredGroup f{};
   const size_t cnt = g.ids.size(), nr = (size_t)g.n * g.f_R;
@@ -242,7 +461,7 @@ LmiFactoredGroup MakeLmiFactored(Group& g) {
   f.sigma = g.f_sigma.p;
   f.ptr = g.f_ptr.p;
   f.var = g.f_var.p;
-  f.Z = g.f_ws.p;  // (the layout UploadGroup sizes: LmiFactoredWsDoubles)
+  f.Z = g.f_ws.p;  // (the layout UploadLmiFactored sizes: LmiFactoredWsDoubles)
   f.Y = f.Z + cnt * nr;
   f.Fs = f.Y + cnt * nr;
   f.P = f.Fs + cnt * nr;
@@ -252,19 +471,34 @@ LmiFactoredGroup MakeLmiFactored(Group& g) {
 }
 size_t LmiFactoredWsDoubles(size_t cnt, size_t n, size_t R) { return cnt * (3 * n * R + R * R); }
 
-size_t LmiGenericLds(int n) { return sizeof(double) * (size_t)(4 * n * n); }
-size_t LmiPrepareLds(int n, int m) {
-  return sizeof(double) * (size_t)(3 * n * n + 6 * n + 2 * (n / 2 + 2) + m + 8);
+// A group of LMIs given by factors: every member's F, sigma, column pointers and column -> variable map, the work
+// space of the factored kernels and of the large-order step kernels behind them.
+static int UploadLmiFactored(cxk_context* ctx, Group& g) {
+  const size_t cnt = g.ids.size(), n = (size_t)g.n, R = (size_t)g.f_R, m = (size_t)g.m;
+  CXK_DEMAND(cnt <= 65535, "a group of more than 65535 equal-shaped factored LMIs is not supported");
+  std::vector<double> hF(cnt * n * R), hs(cnt * R);
+  std::vector<int> hp(cnt * (m + 1)), hv(cnt * R);
+  g.f_rank_one = true;
+  for (size_t k = 0; k < cnt; k++) {
+    const ConstraintRec& c = ctx->cons[g.ids[k]];
+    std::copy(c.f_F.begin(), c.f_F.end(), hF.begin() + k * n * R);
+    std::copy(c.f_sigma.begin(), c.f_sigma.end(), hs.begin() + k * R);
+    std::copy(c.f_ptr.begin(), c.f_ptr.end(), hp.begin() + k * (m + 1));
+    for (size_t i = 0; i < m; i++) {
+      g.f_rank_one = g.f_rank_one && c.f_ptr[i + 1] - c.f_ptr[i] == 1;
+      for (int q = c.f_ptr[i]; q < c.f_ptr[i + 1]; q++) hv[k * R + (size_t)q] = (int)i;
+    }
+  }
+  CXK_TRY(g.f_F.upload(hF));
+  CXK_TRY(g.f_sigma.upload(hs));
+  CXK_TRY(g.f_ptr.upload(hp));
+  CXK_TRY(g.f_var.upload(hv));
+  CXK_TRY(g.f_ws.alloc(LmiFactoredWsDoubles(cnt, n, R)));
+  CXK_TRY(g.ws_main.alloc(cnt * 8 * n * n));  // step temporaries; C W and W C W during assembly
+  CXK_TRY(g.ws_part.alloc(cnt * 2 * kSparseCParts));
+  CXK_TRY(g.ws_piv.alloc(cnt * n));
+  return CXK_SUCCESS;
 }
-size_t LmiTakeLds(int n) { return sizeof(double) * (size_t)(5 * n * n); }
-// Dynamic LDS of the second-order and quadratic cone kernels: what the launch sites ask for and what
-// GroupConstraints admits a cone by, so that an admitted cone can be launched at every stage.
-size_t SocSchurLds(int n, int m, bool staged) { return sizeof(double) * (size_t)(n + 1) * (size_t)(staged ? 2 * m + 4 : m + 2); }
-size_t SocPrepareLds(int n, int m) { return sizeof(double) * ((size_t)m + 3 * ((size_t)n + 1)); }
-size_t SocTakeLds(int n) { return sizeof(double) * 4 * ((size_t)n + 1); }
-size_t QuadSchurLds(int n, int m) { return sizeof(double) * (2 * (size_t)n + (size_t)m + 4); }
-size_t QuadPrepareLds(int n, int m) { return sizeof(double) * ((size_t)m + 4 * ((size_t)n + 1)); }
-size_t QuadTakeLds(int n) { return sizeof(double) * 3 * ((size_t)n + 1); }
 
 // ---- The kernel instance each per-constraint stage of an LMI group runs.  One chooser per stage: the
 // launch sites switch on its answer and cxk_lmi_kernels reports it, so the two cannot disagree.  The
@@ -360,15 +594,15 @@ bool IsTakeRows(LmiKernel k) { return k >= kTakeRows20 && k <= kTakeTaylor32Pad;
 
 LmiKernel LmiSchurKernel(const Group& g) {
   // not one of the instances: a code outside the reported range, which no Is*() test accepts and
-  // cxk_lmi_kernel_name has no name for (LaunchSchur and cxk_lmi_kernels ask g.factored first)
-  if (g.factored) return kLmiKernelCount;
-  if (g.sparse) return (LmiKernel)((g.sp_small ? kSchurSparseSmall : kSchurSparse) + (g.sp_cdense ? 1 : 0));
-  if (g.schur_gemm) {  // (fold and split counts as LmiLargeSchur reads them: MakeLargeWs, LmiFoldedSplits)
+  // cxk_lmi_kernel_name has no name for (LaunchSchur switches on the route first, cxk_lmi_kernels refuses the constraint)
+  if (g.route == ConeRoute::kLmiFactored) return kLmiKernelCount;
+  if (g.route == ConeRoute::kLmiSparse) return (LmiKernel)((g.sp_small ? kSchurSparseSmall : kSchurSparse) + (g.sp_cdense ? 1 : 0));
+  if (g.assembly == LmiAssembly::kGemm) {  // (fold and split counts as LmiLargeSchur reads them: MakeLargeWs, LmiFoldedSplits)
     const bool fold = g.Aleft.n != 0;
     const int splits = fold ? LmiFoldedSplits(g.splits, g.n, g.n / g.herm_d) : g.splits;
     return (LmiKernel)(kSchurGemm + (fold ? 4 : 0) + (g.large ? 2 : 0) + (splits > 1 ? 1 : 0));
   }
-  if (g.mfma) {
+  if (g.assembly == LmiAssembly::kMfma) {
     const LmiMfmaInstance inst = LmiMfmaChoose(g.n, g.m, g.herm_d);
     if (inst.folded) return inst.single ? kSchurMfma24FoldedSingle : kSchurMfma24Folded;
     const bool pad = g.Apad.p != nullptr;
@@ -387,7 +621,7 @@ LmiKernel LmiSchurKernel(const Group& g) {
 LmiKernel LmiPrepareKernel(const cxk_context* ctx, const Group& g, int mode) {
   const int base = mode == 0 ? kPrepareRowsPacked : kQueryRowsPacked;
   if (g.large) return mode == 2 ? kAffineLarge : (LmiKernel)(base + 6);
-  if (mode != 2 && !ctx->prepare_lds && !g.literal && LmiPrepareRowsSupports(g.n, g.m, g.herm_d, g.sparse)) {
+  if (mode != 2 && !ctx->prepare_lds && !g.literal && LmiPrepareRowsSupports(g.n, g.m, g.herm_d, g.route == ConeRoute::kLmiSparse)) {
     if (g.n == 20) return (LmiKernel)(base + (g.Apk.p ? 0 : 1));
     return (LmiKernel)(base + ((g.n & 1) ? 2 : 3));
   }
@@ -560,8 +794,36 @@ hipError_t LaunchLmiSchurSparse(Group& g, LmiKernel kern, const Arena& ar, hipSt
   return LaunchLmiSparseKernel<false>(g, d, ar, X, st);
 }
 
-// The Schur complement of a group of streamed second-order cones: vectors, apply, Gram (the batched GEMM with
-// SYRK-shaped output, split along len when that is long), mirror.  Stream order is the only dependency.
+// Gf = alpha WA' WA of every member of a group (WA: len x m per member), lower triangles only: the batched GEMM with
+// SYRK-shaped output, split along len when that is long (the work space of AllocGramWorkspace).
+static hipError_t LaunchGramLower(Group& g, const double* WA, double* Gf, int cnt, int len, int m, double alpha, hipStream_t st) {
+  const int64_t mm = (int64_t)m * m;
+  constexpr int kMaxBatch = 65535;  // gridDim.z
+  for (int b0 = 0; b0 < cnt; b0 += kMaxBatch) {
+    const int nb = std::min(kMaxBatch, cnt - b0);
+    GemmArgs a{};
+    a.M = a.N = m;
+    a.K = len;
+    a.A = a.B = WA + (size_t)b0 * len * m;
+    a.lda = a.ldb = len;
+    a.sA1 = a.sB1 = (int64_t)len * m;
+    a.C = Gf + (size_t)b0 * mm;
+    a.ldc = m;
+    a.sC1 = mm;
+    a.inner = 1;
+    a.alpha = alpha;
+    a.beta = 0.0;
+    a.lower_only = 1;
+    a.splits = g.splits;
+    a.sCs = (int64_t)std::min(cnt, kMaxBatch) * mm;
+    const hipError_t e = LaunchGemmSplitK(a, true, false, nb, g.ws_part.p, st);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+// The Schur complement of a group of streamed second-order cones: vectors, apply, Gram (LaunchGramLower, alpha = 2),
+// mirror.  Stream order is the only dependency.
 hipError_t LaunchSocStreamSchur(Group& g, const Arena& ar, hipStream_t st) {
   const SocStreamGroup d = MakeSocStream(g);
   const int cnt = d.v.count, len = d.v.len, m = d.v.m;
@@ -569,63 +831,23 @@ hipError_t LaunchSocStreamSchur(Group& g, const Arena& ar, hipStream_t st) {
   if (m == 0 || g.st_stages == 1) return hipGetLastError();
   soc_stream_apply<<<(unsigned)((size_t)cnt * m), kSocStreamBlock, 0, st>>>(d, ar);
   if (g.st_stages == 2) return hipGetLastError();
-  const int64_t mm = (int64_t)m * m;
-  constexpr int kMaxBatch = 65535;  // gridDim.z
-  for (int b0 = 0; b0 < cnt; b0 += kMaxBatch) {
-    const int nb = std::min(kMaxBatch, cnt - b0);
-    GemmArgs a{};
-    a.M = a.N = m;
-    a.K = len;
-    a.A = a.B = d.WA + (size_t)b0 * len * m;
-    a.lda = a.ldb = len;
-    a.sA1 = a.sB1 = (int64_t)len * m;
-    a.C = d.Gf + (size_t)b0 * mm;
-    a.ldc = m;
-    a.sC1 = mm;
-    a.inner = 1;
-    a.alpha = 2.0;
-    a.beta = 0.0;
-    a.lower_only = 1;
-    a.splits = g.splits;
-    a.sCs = (int64_t)std::min(cnt, kMaxBatch) * mm;
-    const hipError_t e = LaunchGemmSplitK(a, true, false, nb, g.ws_part.p, st);
-    if (e != hipSuccess) return e;
-  }
-  soc_stream_mirror<<<GridFor((size_t)cnt * mm, kSocStreamBlock), kSocStreamBlock, 0, st>>>(d, ar);
+  const hipError_t e = LaunchGramLower(g, d.WA, d.Gf, cnt, len, m, 2.0, st);
+  if (e != hipSuccess) return e;
+  soc_stream_mirror<<<GridFor((size_t)cnt * m * m, kSocStreamBlock), kSocStreamBlock, 0, st>>>(d, ar);
   return hipGetLastError();
 }
 
-// The Schur complement of a group of linear blocks on the tiled route: scalars, apply, Gram (the batched GEMM as
-// LaunchSocStreamSchur sets it up, alpha = 1), mirror.  Stream order is the only dependency.
+// The Schur complement of a group of linear blocks on the tiled route: scalars, apply, Gram (LaunchGramLower,
+// alpha = 1), mirror.  Stream order is the only dependency.
 hipError_t LaunchLinearTiledSchur(Group& g, const Arena& ar, hipStream_t st) {
   const LinTiledGroup d = MakeLinTiled(g);
   const int cnt = d.v.count, len = d.v.len, m = d.v.m;
   linear_tiled_scalars<<<cnt, kLinTiledBlock, 0, st>>>(d, ar);
   if (m == 0) return hipGetLastError();
   linear_tiled_apply<<<(unsigned)((size_t)cnt * m), kLinTiledBlock, 0, st>>>(d, ar);
-  const int64_t mm = (int64_t)m * m;
-  constexpr int kMaxBatch = 65535;  // gridDim.z
-  for (int b0 = 0; b0 < cnt; b0 += kMaxBatch) {
-    const int nb = std::min(kMaxBatch, cnt - b0);
-    GemmArgs a{};
-    a.M = a.N = m;
-    a.K = len;
-    a.A = a.B = d.WA + (size_t)b0 * len * m;
-    a.lda = a.ldb = len;
-    a.sA1 = a.sB1 = (int64_t)len * m;
-    a.C = d.Gf + (size_t)b0 * mm;
-    a.ldc = m;
-    a.sC1 = mm;
-    a.inner = 1;
-    a.alpha = 1.0;
-    a.beta = 0.0;
-    a.lower_only = 1;
-    a.splits = g.splits;
-    a.sCs = (int64_t)std::min(cnt, kMaxBatch) * mm;
-    const hipError_t e = LaunchGemmSplitK(a, true, false, nb, g.ws_part.p, st);
-    if (e != hipSuccess) return e;
-  }
-  linear_tiled_mirror<<<GridFor((size_t)cnt * mm, kLinTiledBlock), kLinTiledBlock, 0, st>>>(d, ar);
+  const hipError_t e = LaunchGramLower(g, d.WA, d.Gf, cnt, len, m, 1.0, st);
+  if (e != hipSuccess) return e;
+  linear_tiled_mirror<<<GridFor((size_t)cnt * m * m, kLinTiledBlock), kLinTiledBlock, 0, st>>>(d, ar);
   return hipGetLastError();
 }
 
@@ -800,91 +1022,92 @@ bool ClockSample(cxk_context* ctx, int slot, hipEvent_t* e0, hipEvent_t* e1) {
   return true;
 }
 
+namespace {
+// Kernel clocks (CXK_CLOCK_*): a slot whose launches are ONE register kernel carries the event pair on that
+// dispatch; anything else is bracketed by event records around its launches.
+struct StepClock {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  bool sample = false, on_dispatch = false;
+};
+StepClock BeginStepClock(cxk_context* ctx, int slot, bool one_register_kernel) {
+  StepClock c;
+  c.sample = ClockSample(ctx, slot, &c.e0, &c.e1);
+  c.on_dispatch = c.sample && one_register_kernel;
+  if (c.sample && !c.on_dispatch) (void)hipEventRecord(c.e0, ctx->stream);
+  return c;
+}
+void EndStepClock(cxk_context* ctx, const StepClock& c) {
+  if (c.sample && !c.on_dispatch) (void)hipEventRecord(c.e1, ctx->stream);
+}
+// The assembly clock around the launches of one group, for the scope it is declared in.
+struct AssemblyClock {
+  cxk_context* ctx;
+  StepClock clk;
+  explicit AssemblyClock(cxk_context* c, bool on_dispatch = false) : ctx(c), clk(BeginStepClock(c, CXK_CLOCK_ASSEMBLY, on_dispatch)) {}
+  ~AssemblyClock() { EndStepClock(ctx, clk); }
+};
+}  // namespace
+
+// The Schur complement of a group of dense LMIs, on the instance LmiSchurKernel names.
+static int LaunchLmiDenseSchur(cxk_context* ctx, Group& g, const Arena& ar) {
+  const LmiKernel kern = LmiSchurKernel(g);
+  // (lmi_schur_mfma carries the pair on its dispatch instead: no marker packets)
+  const AssemblyClock clock(ctx, IsSchurMfma(kern));
+  if (IsSchurGemm(kern)) {
+    CXK_TRY(LmiLargeSchur(MakeLmi(g), ar, MakeLargeWs(g), ctx->stream));
+  } else if (IsSchurMfma(kern)) {
+    LmiGroup lg = MakeLmi(g);
+    if (g.Apad.p) {  // the order runs on the next instance up (masked W loads in the kernel)
+      const int np = LmiMfmaPaddedOrder(g.n);
+      lg.A = g.Apad.p;
+      lg.a_stride = (long long)(g.m + 1) * np * np;
+    }
+    // every other launch of the group last to first: a launch then starts on the operands the previous one
+    // ended with, which shortens its fill (the results are the same bits either way)
+    const int rev = ctx->lmi_order_forward ? 0 : (int)(g.schur_launches & 1);
+    g.schur_launches++;
+    CXK_TRY(LaunchLmiSchurMfma(lg, ar, ctx->cus, rev, ctx->stream, clock.clk.e0, clock.clk.e1));
+  } else {
+    lmi_schur_generic<<<(int)g.ids.size(), 256, LmiGenericLds(g.n), ctx->stream>>>(MakeLmi(g), ar);
+  }
+  return CXK_SUCCESS;
+}
+
+// The Schur complement of a group of second-order cones on the LDS route: one wavefront per cone, up to four cones per
+// workgroup; the cone's data staged in LDS when four staged images fit, read in place otherwise.
+static void LaunchSocLdsSchur(cxk_context* ctx, Group& g, const Arena& ar) {
+  const int count = (int)g.ids.size();
+  const size_t staged = SocSchurLds(g.n, g.m, true), plain = SocSchurLds(g.n, g.m, false);
+  if (4 * staged <= kLdsLimit) {
+    soc_schur<true><<<(count + 3) / 4, 256, 4 * staged, ctx->stream>>>(MakeVec(g), ar);
+  } else {
+    const int w = (int)std::max<size_t>(1, std::min<size_t>(4, kLdsLimit / plain));
+    soc_schur<false><<<(count + w - 1) / w, 64 * w, w * plain, ctx->stream>>>(MakeVec(g), ar);
+  }
+}
+
+// The routes of more than one launch, and both quadratic ones (tools/quad_stream_speed.py compares them), carry the
+// assembly clock when timing is on.
 int LaunchSchur(cxk_context* ctx) {
   Arena ar = MakeArena(ctx);
+  hipStream_t st = ctx->stream;
   for (Group& g : ctx->groups) {
     const int count = (int)g.ids.size();
     if (count == 0) continue;
-    switch (g.type) {
-      case CXK_LMI: {
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        const bool sample = ClockSample(ctx, CXK_CLOCK_ASSEMBLY, &e0, &e1);
-        const LmiKernel kern = LmiSchurKernel(g);
-        // (lmi_schur_mfma carries the pair on its dispatch instead: no marker packets)
-        if (sample && !IsSchurMfma(kern)) CXK_TRY(hipEventRecord(e0, ctx->stream));
-        if (g.factored) {  // (not one of the reported instances: `kern` is not looked at)
-          CXK_TRY(LmiFactoredSchur(MakeLmi(g), MakeLmiFactored(g), ar, MakeLargeWs(g), ctx->stream));
-        } else if (IsSchurSparse(kern)) {
-          CXK_TRY(LaunchLmiSchurSparse(g, kern, ar, ctx->stream));
-        } else if (IsSchurGemm(kern)) {
-          CXK_TRY(LmiLargeSchur(MakeLmi(g), ar, MakeLargeWs(g), ctx->stream));
-        } else if (IsSchurMfma(kern)) {
-          LmiGroup lg = MakeLmi(g);
-          if (g.Apad.p) {  // the order runs on the next instance up (masked W loads in the kernel)
-            const int np = LmiMfmaPaddedOrder(g.n);
-            lg.A = g.Apad.p;
-            lg.a_stride = (long long)(g.m + 1) * np * np;
-          }
-          // every other launch of the group last to first: a launch then starts on the operands the previous one
-          // ended with, which shortens its fill (the results are the same bits either way)
-          const int rev = ctx->lmi_order_forward ? 0 : (int)(g.schur_launches & 1);
-          g.schur_launches++;
-          CXK_TRY(LaunchLmiSchurMfma(lg, ar, ctx->cus, rev, ctx->stream, e0, e1));
-        } else {
-          lmi_schur_generic<<<count, 256, LmiGenericLds(g.n), ctx->stream>>>(MakeLmi(g), ar);
-        }
-        if (sample && !IsSchurMfma(kern)) CXK_TRY(hipEventRecord(e1, ctx->stream));
-        break;
-      }
-      case CXK_LINEAR:
-        if (g.tiled || g.lsparse) {
-          hipEvent_t e0 = nullptr, e1 = nullptr;
-          const bool sample = ClockSample(ctx, CXK_CLOCK_ASSEMBLY, &e0, &e1);
-          if (sample) CXK_TRY(hipEventRecord(e0, ctx->stream));
-          CXK_TRY(g.lsparse ? LaunchLinearSparseSchur(g, ar, ctx->stream) : LaunchLinearTiledSchur(g, ar, ctx->stream));
-          if (sample) CXK_TRY(hipEventRecord(e1, ctx->stream));
-        } else {
-          linear_schur<<<count, 256, 0, ctx->stream>>>(MakeVec(g), ar);
-        }
-        break;
-      case CXK_SOC:
-      if (g.streamed || g.ssparse) {
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        const bool sample = ClockSample(ctx, CXK_CLOCK_ASSEMBLY, &e0, &e1);
-        if (sample) CXK_TRY(hipEventRecord(e0, ctx->stream));
-        CXK_TRY(g.ssparse ? LaunchSocSparseSchur(g, ar, ctx->stream) : LaunchSocStreamSchur(g, ar, ctx->stream));
-        if (sample) CXK_TRY(hipEventRecord(e1, ctx->stream));
-      } else {
-        // one wavefront per cone, up to four cones per workgroup; the cone's data staged in LDS when
-        // four staged images fit, read in place otherwise
-        const size_t staged = SocSchurLds(g.n, g.m, true);
-        const size_t plain = SocSchurLds(g.n, g.m, false);
-        if (4 * staged <= kLdsLimit) {
-          soc_schur<true><<<(count + 3) / 4, 256, 4 * staged, ctx->stream>>>(MakeVec(g), ar);
-        } else {
-          const int w = (int)std::max<size_t>(1, std::min<size_t>(4, kLdsLimit / plain));
-          soc_schur<false><<<(count + w - 1) / w, 64 * w, w * plain, ctx->stream>>>(MakeVec(g), ar);
-        }
-      }
-        break;
-      case CXK_STATIC:
-        static_schur<<<count, 64, 0, ctx->stream>>>(MakeStatic(g), ar);
-        break;
-      case CXK_QUAD:
-      {  // (both routes carry the assembly clock when timing is on: tools/quad_stream_speed.py compares them)
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        const bool sample = ClockSample(ctx, CXK_CLOCK_ASSEMBLY, &e0, &e1);
-        if (sample) CXK_TRY(hipEventRecord(e0, ctx->stream));
-        if (g.qstream)
-          CXK_TRY(LaunchQuadStreamSchur(g, ar, ctx->stream));
-        else
-          quad_schur<<<count, 64, QuadSchurLds(g.n, g.m), ctx->stream>>>(MakeQuad(g), ar);
-        if (sample) CXK_TRY(hipEventRecord(e1, ctx->stream));
-        break;
-      }
-      case CXK_OCT:
-        oct_schur<<<count, 64, 0, ctx->stream>>>(MakeOct(g), ar);
-        break;
+    switch (g.route) {
+      case ConeRoute::kLmiDense: if (LaunchLmiDenseSchur(ctx, g, ar)) return CXK_FAILURE; break;
+      case ConeRoute::kLmiSparse: { const AssemblyClock clock(ctx); CXK_TRY(LaunchLmiSchurSparse(g, LmiSchurKernel(g), ar, st)); break; }
+      case ConeRoute::kLmiFactored: { const AssemblyClock clock(ctx); CXK_TRY(LmiFactoredSchur(MakeLmi(g), MakeLmiFactored(g), ar, MakeLargeWs(g), st)); break; }
+      case ConeRoute::kLinearLds: linear_schur<<<count, 256, 0, st>>>(MakeVec(g), ar); break;
+      case ConeRoute::kLinearTiled: { const AssemblyClock clock(ctx); CXK_TRY(LaunchLinearTiledSchur(g, ar, st)); break; }
+      case ConeRoute::kLinearSparse: { const AssemblyClock clock(ctx); CXK_TRY(LaunchLinearSparseSchur(g, ar, st)); break; }
+      case ConeRoute::kSocLds: LaunchSocLdsSchur(ctx, g, ar); break;
+      case ConeRoute::kSocStreamed: { const AssemblyClock clock(ctx); CXK_TRY(LaunchSocStreamSchur(g, ar, st)); break; }
+      case ConeRoute::kSocSparse: { const AssemblyClock clock(ctx); CXK_TRY(LaunchSocSparseSchur(g, ar, st)); break; }
+      case ConeRoute::kQuadLds: { const AssemblyClock clock(ctx); quad_schur<<<count, 64, QuadSchurLds(g.n, g.m), st>>>(MakeQuad(g), ar); break; }
+      case ConeRoute::kQuadStreamed: { const AssemblyClock clock(ctx); CXK_TRY(LaunchQuadStreamSchur(g, ar, st)); break; }
+      case ConeRoute::kStatic: static_schur<<<count, 64, 0, st>>>(MakeStatic(g), ar); break;
+      case ConeRoute::kOct: oct_schur<<<count, 64, 0, st>>>(MakeOct(g), ar); break;
     }
   }
   CXK_TRY(hipGetLastError());
@@ -914,7 +1137,7 @@ static void LinearNonzeros(ConstraintRec* c) {
 
 // The device copy of a group of linear blocks (rows = n) or second-order cones (rows = n + 1) on the sparse route:
 // every member's nonzeros by rows and by columns.
-static int UploadSparseLinear(cxk_context* ctx, Group& g) {
+static int UploadSparseNonzeros(cxk_context* ctx, Group& g) {
   const size_t cnt = g.ids.size(), rows = (size_t)g.n + (g.type == CXK_SOC ? 1 : 0), m = (size_t)g.m;
   size_t total = 0;
   for (size_t k = 0; k < cnt; k++) total += ctx->cons[g.ids[k]].sp_col.size();
@@ -951,182 +1174,72 @@ static int UploadSparseLinear(cxk_context* ctx, Group& g) {
   return CXK_SUCCESS;
 }
 
-// cxk_finalize, per-group stages.  Groups of identically shaped constraints (owned ones only carry data).
+// The nonzero statistics Choose asks for, of a dense-added linear block (rows = n) or second-order cone (rows = n + 1)
+// whose sparse mode is not 0; and the nonzeros themselves (LinearNonzeros) when ints can point at them.
+static void MeasureNonzeros(ConstraintRec* c, ConeShape* s) {
+  if (c->sp_rowptr.empty()) {
+    size_t nnz = 0;
+    for (double v : c->A) nnz += v != 0.0;
+    s->nnz = (double)nnz;
+    s->nnz_fits_int = nnz <= (size_t)INT_MAX;
+    if (!s->nnz_fits_int) return;
+    LinearNonzeros(c);
+  }
+  s->nnz = (double)c->sp_col.size();
+  for (size_t r = 0; r + 1 < c->sp_rowptr.size(); r++) {
+    const double nz = c->sp_rowptr[r + 1] - c->sp_rowptr[r];
+    s->sum_nnz_sq += nz * nz;
+  }
+  std::vector<int> per_col((size_t)c->m, 0);
+  for (int v : c->sp_col) per_col[(size_t)v]++;
+  s->longest_column = c->m ? *std::max_element(per_col.begin(), per_col.end()) : 0;
+}
+
+// cxk_finalize, per-group stages.  Every owned constraint gets its route (cone_route.h: Choose, or the refusal
+// cxk_finalize fails with); constraints of one shape on one route form a group, numbered by first appearance.
 int GroupConstraints(cxk_context* ctx, const FinalizeSwitches& sw) {
   const int K = (int)ctx->cons.size();
-  std::map<std::tuple<int, int, int, int, int>, int> gmap;  // (the last: a factored LMI's R)
+  std::map<std::tuple<int, int, int, int, ConeRoute, bool, bool, int>, int> gmap;
   ctx->groups.clear();
-  // second-order cones beyond LDS: refused, or held in HBM (cxk_set_streamed_cones, else CXK_STREAMED_CONES)
-  const bool stream_on = ctx->streamed_cones >= 0 ? ctx->streamed_cones != 0 : sw.streamed_cones;
-  // linear blocks: the LDS route's one workgroup per block, or the tiled route (cxk_set_tiled_linear, else
-  // CXK_TILED_LINEAR, else by size)
-  const int tiled_mode = ctx->tiled_linear >= 0 ? ctx->tiled_linear : sw.tiled_linear;
-  // quadratic cones: the LDS route's one workgroup per cone, or held in HBM (cxk_set_streamed_quadratic, else
-  // CXK_STREAMED_QUADRATIC, else none)
-  const int qstream_mode = ctx->streamed_quadratic != -2 ? ctx->streamed_quadratic : sw.streamed_quadratic;
-  // linear blocks evaluated from their nonzeros (cxk_set_sparse_linear, else CXK_SPARSE_LINEAR, else none); automatic
-  // mode yields to an explicit tiled mode, which asks for the dense kernels
-  const int lsparse_mode = ctx->sparse_linear != -2 ? ctx->sparse_linear : sw.sparse_linear;
-  // second-order cones evaluated from their nonzeros (cxk_set_sparse_soc, else CXK_SPARSE_SOC, else none)
-  const int ssparse_mode = ctx->sparse_soc != -2 ? ctx->sparse_soc : sw.sparse_soc;
   ctx->sparse_soc_setup_ms = 0;
+  // what the context was told (-1 / -2: nothing) goes in front of the environment's word
+  RouteModes modes = sw.modes;
+  if (ctx->streamed_cones >= 0) modes.streamed_cones = ctx->streamed_cones != 0;
+  if (ctx->tiled_linear >= 0) modes.tiled_linear = ctx->tiled_linear;
+  if (ctx->streamed_quadratic != -2) modes.streamed_quadratic = ctx->streamed_quadratic;
+  if (ctx->sparse_linear != -2) modes.sparse_linear = ctx->sparse_linear;
+  if (ctx->sparse_soc != -2) modes.sparse_soc = ctx->sparse_soc;
   for (int i = 0; i < K; i++) {
     ConstraintRec& c = ctx->cons[i];
-    c.streamed = false;
-    c.tiled = false;
-    c.qstream = false;
-    c.lsparse = false;
-    c.ssparse = false;
+    c.route = ConeRoute::kStatic;
     if (!ctx->owned[i]) continue;
-    if (c.type == CXK_LINEAR) {
-      CXK_DEMAND(!c.csr_only || lsparse_mode != 0,
-                 "a linear block added by cxk_add_linear_csr has no dense matrix and can only take the sparse route "
-                 "(cxk_set_sparse_linear / CXK_SPARSE_LINEAR, which is 0)");
-      bool countable = true;  // (the pointers are ints)
-      if (lsparse_mode != 0 && !c.csr_only && c.sp_rowptr.empty()) {
-        size_t nnz = 0;
-        for (double v : c.A) nnz += v != 0.0;
-        countable = nnz <= (size_t)INT_MAX;
-        CXK_DEMAND(countable || lsparse_mode != 1, "a sparse linear block with more than 2^31 nonzeros is not supported");
-        if (countable) LinearNonzeros(&c);
-      }
-      c.lsparse = c.csr_only || lsparse_mode == 1;
-      if (lsparse_mode == -1 && !c.csr_only && tiled_mode < 0 && countable) {
-        double sq = 0;
-        std::vector<int> per_col((size_t)c.m, 0);
-        for (int r = 0; r < c.n; r++) {
-          const double nz = c.sp_rowptr[(size_t)r + 1] - c.sp_rowptr[(size_t)r];
-          sq += nz * nz;
-        }
-        for (int v : c.sp_col) per_col[(size_t)v]++;
-        const int longest = c.m ? *std::max_element(per_col.begin(), per_col.end()) : 0;
-        c.lsparse = LinearSparsePays(c.n, c.m, sq, longest, sw.sparse_linear_min_ratio);
-      }
-    }
-    if (c.type == CXK_LINEAR && c.lsparse) {
-      CXK_DEMAND((int64_t)c.m * c.m <= INT_MAX,
-                 "a sparse linear block whose variables x variables Schur block exceeds the int range is not supported");
-    } else if (c.type == CXK_LINEAR) {
-      c.tiled = tiled_mode >= 0 ? tiled_mode != 0
-                                : c.m > kLinearLdsMaxVars || (double)c.n * c.m * c.m >= (double)sw.tiled_linear_min_work;
-      if (c.tiled) {
-        // what remains is the int indexing of the kernels and of the GEMM
-        CXK_DEMAND((int64_t)c.n * std::max(c.m, 1) <= INT_MAX - 1024,
-                   "a tiled linear block whose rows x variables entries exceed the int range is not supported");
-        CXK_DEMAND((int64_t)c.m * c.m <= INT_MAX,
-                   "a tiled linear block whose variables x variables Schur block exceeds the int range is not supported");
-      } else {
-        // linear_line_search keeps two vectors of m doubles in 64 KB of dynamic LDS
-        CXK_DEMAND(c.m <= kLinearLdsMaxVars,
-                   "a linear block over more than 4096 variables does not fit the LDS route's kernels: it needs the tiled "
-                   "route (cxk_set_tiled_linear / CXK_TILED_LINEAR, which was set to 0)");
-      }
-    }
-    if (c.type == CXK_LMI && c.factored) {
-      // held by its factors (kernels_lmi_factored.hip.h) in front of the large-order route (FinalizeImpl has checked
-      // the order and the int indexing of the kernels)
-      c.sparse = false;
-    } else if (c.type == CXK_LMI) {
-      // sparse evaluation when it pays (CXK_SPARSE_LMI=0 / 1 forces never / always: tests)
+    ConeShape s{c.type, c.n, c.m, c.herm_d, c.symmetric, c.csr_only, c.factored, c.type == CXK_QUAD && !c.Q.empty()};
+    const int sparse_mode = c.type == CXK_LINEAR ? modes.sparse_linear : c.type == CXK_SOC ? modes.sparse_soc : 0;
+    if (sparse_mode != 0 && !c.csr_only) MeasureNonzeros(&c, &s);
+    if (c.type == CXK_LMI && !c.factored) {
       double nnz = 0;
       for (double v : c.A) nnz += (v != 0.0);
-      const bool lds_resident = LmiTakeLds(c.n) <= kLdsLimit && LmiPrepareLds(c.n, c.m) <= kLdsLimit;
-      c.sparse = sw.sparse_lmi >= 0 ? (sw.sparse_lmi != 0)
-                                    : LmiSparsePays(c.n, c.m, nnz, lds_resident, LmiMfmaSupports(c.n, c.m, c.herm_d));
-      if (c.n > 65535) c.sparse = false;  // packed row | col << 16
-      if (!c.symmetric) {
-        // The reference accepts non-symmetric matrices and evaluates <W A_i W, A_j> as written;
-        // only the literal LDS kernels do the same.
-        c.sparse = false;
-        CXK_DEMAND(lds_resident, "non-symmetric LMI data beyond the LDS-resident orders is not supported: "
-                                 "the large-order kernels use tr(W A_i W A_j) = tr(P_i P_j), which needs A_i = A_i^T");
-      }
+      s.mfma_supports = LmiMfmaSupports(c.n, c.m, c.herm_d);
+      s.sparse_pays = LmiSparsePays(c.n, c.m, nnz, LmiLdsResident(c.n, c.m), s.mfma_supports);
     }
-    if (c.type == CXK_SOC) {
-      CXK_DEMAND(!c.csr_only || ssparse_mode != 0,
-                 "a second-order cone added by cxk_add_soc_csr has no dense matrix and can only take the sparse route "
-                 "(cxk_set_sparse_soc / CXK_SPARSE_SOC, which is 0)");
-      // (a dense route indexes the (n + 1) x m entries with ints)
-      const bool dense_ok = (int64_t)(c.n + 1) * std::max(c.m, 1) <= INT_MAX - 1024;
-      bool countable = true;  // (the pointers are ints)
-      if (ssparse_mode != 0 && !c.csr_only && c.sp_rowptr.empty()) {
-        size_t nnz = 0;
-        for (double v : c.A) nnz += v != 0.0;
-        countable = nnz <= (size_t)INT_MAX;
-        CXK_DEMAND(countable || ssparse_mode != 1, "a sparse second-order cone with more than 2^31 nonzeros is not supported");
-        if (countable) LinearNonzeros(&c);
-      }
-      c.ssparse = c.csr_only || ssparse_mode == 1;
-      if (ssparse_mode == -1 && !c.csr_only && countable)
-        c.ssparse = !dense_ok || SocSparsePays((double)c.n + 1, c.m, (double)c.sp_col.size(), sw.sparse_soc_min_ratio);
-    }
-    if (c.type == CXK_SOC && !c.ssparse) {
-      c.streamed = stream_on && !(SocSchurLds(c.n, c.m, false) <= kLdsLimit && SocTakeLds(c.n) <= kLdsLimit &&
-                                  SocPrepareLds(c.n, c.m) <= kLdsLimit);
-    }
-    if (c.type == CXK_SOC && c.ssparse) {
-      // held as nonzeros (kernels_soc_sparse.hip.h): no LDS room, no streamed switch; what remains is the int indexing
-      // of the m x m squares H and G
-      CXK_DEMAND((int64_t)c.m * c.m <= INT_MAX,
-                 "a sparse second-order cone whose variables x variables Schur block exceeds the int range is not supported");
-    } else if (c.type == CXK_SOC && c.streamed) {
-      // held in HBM (kernels_soc_stream.hip.h): what remains is the int indexing of the kernels and of the GEMM
-      CXK_DEMAND((int64_t)(c.n + 1) * std::max(c.m, 1) <= INT_MAX - 1024,
-                 "a streamed second-order cone whose (dimension + 1) x variables entries exceed the int range is not supported");
-      CXK_DEMAND((int64_t)c.m * c.m <= INT_MAX,
-                 "a streamed second-order cone whose variables x variables Schur block exceeds the int range is not supported");
-    } else if (c.type == CXK_SOC) {
-      // soc_schur keeps a cone's (n + 1) x (m + 2) image in LDS (CONEX_NewLorentzConeConstraint makes a
-      // cone's matrix as wide as its largest variable index: thousands of columns are possible there)
-      CXK_DEMAND(SocSchurLds(c.n, c.m, false) <= kLdsLimit,
-                 "a second-order cone whose (dimension + 1) x (variables + 2) image exceeds LDS (160 KB) is not supported");
-      // soc_take_step keeps four vectors of the cone in LDS, soc_prepare three and y: with one variable
-      // they, not the image above, are what has to fit
-      CXK_DEMAND(SocTakeLds(c.n) <= kLdsLimit && SocPrepareLds(c.n, c.m) <= kLdsLimit,
-                 "a second-order cone whose step kernels need more than the 163 328 B of LDS (four vectors of dimension + 1) is "
-                 "not supported");
-    }
-    if (c.type == CXK_QUAD) {
-      const bool fits = QuadPrepareLds(c.n, c.m) <= kLdsLimit && QuadSchurLds(c.n, c.m) <= kLdsLimit && QuadTakeLds(c.n) <= kLdsLimit;
-      const double work = (c.Q.empty() ? 0.0 : (double)c.n * c.n) + ((double)c.n + 1) * c.m;  // doubles streamed per pass
-      c.qstream = qstream_mode >= 0 ? qstream_mode != 0 : !fits || work >= (double)sw.streamed_quadratic_min_work;
-    }
-    if (c.type == CXK_QUAD && c.qstream) {
-      // held in HBM (kernels_quad_stream.hip.h): what remains is the int indexing of the kernels and of the GEMM
-      CXK_DEMAND((int64_t)(c.n + 1) * std::max(c.m, 1) <= INT_MAX - 1024,
-                 "a streamed quadratic cone whose (dimension + 1) x variables entries exceed the int range is not supported");
-      CXK_DEMAND((int64_t)c.m * c.m <= INT_MAX,
-                 "a streamed quadratic cone whose variables x variables Schur block exceeds the int range is not supported");
-      CXK_DEMAND(c.Q.empty() || (int64_t)c.n * c.n <= INT_MAX,
-                 "a streamed quadratic cone whose inner-product matrix has more than 2^31 entries is not supported");
-    } else if (c.type == CXK_QUAD)
-      // quad_prepare keeps y and four vectors of the cone in LDS; quad_schur and quad_take_step need less
-      CXK_DEMAND(QuadPrepareLds(c.n, c.m) <= kLdsLimit && QuadSchurLds(c.n, c.m) <= kLdsLimit && QuadTakeLds(c.n) <= kLdsLimit,
-                 "a quadratic cone whose step kernels need more than the 163 328 B of LDS (variables + four vectors of "
-                 "dimension + 1) is not supported");
-    auto key = std::make_tuple(c.type, c.n, c.m, c.herm_d + (c.sparse ? 16 : 0) + (c.type == CXK_LMI && !c.symmetric ? 32 : 0) +
-                                                     (c.type == CXK_QUAD && !c.Q.empty() ? 64 : 0) + (c.streamed ? 128 : 0) +
-                                                     (c.tiled ? 256 : 0) + (c.qstream ? 512 : 0) + (c.lsparse ? 1024 : 0) + (c.ssparse ? 2048 : 0) +
-                                                     (c.factored ? 4096 : 0),
-                              c.factored ? c.f_R : 0);
+    const RouteChoice choice = Choose(s, modes);
+    CXK_DEMAND(!choice.refusal, choice.refusal);
+    c.route = choice.route;
+    const bool literal = c.type == CXK_LMI && !c.symmetric;
+    const int f_R = c.factored ? c.f_R : 0;
+    const auto key = std::make_tuple(c.type, c.n, c.m, c.herm_d, c.route, literal, s.has_q, f_R);
     auto it = gmap.find(key);
     if (it == gmap.end()) {
       it = gmap.emplace(key, (int)ctx->groups.size()).first;
-      ctx->groups.emplace_back();
-      ctx->groups.back().type = c.type;
-      ctx->groups.back().n = c.n;
-      ctx->groups.back().m = c.m;
-      ctx->groups.back().herm_d = c.herm_d;
-      ctx->groups.back().sparse = c.sparse;
-      ctx->groups.back().literal = c.type == CXK_LMI && !c.symmetric;
-      ctx->groups.back().has_q = c.type == CXK_QUAD && !c.Q.empty();
-      ctx->groups.back().streamed = c.streamed;
-      ctx->groups.back().tiled = c.tiled;
-      ctx->groups.back().qstream = c.qstream;
-      ctx->groups.back().lsparse = c.lsparse;
-      ctx->groups.back().ssparse = c.ssparse;
-      ctx->groups.back().factored = c.factored;
-      ctx->groups.back().f_R = c.factored ? c.f_R : 0;
+      Group& g = ctx->groups.emplace_back();
+      g.type = c.type;
+      g.n = c.n;
+      g.m = c.m;
+      g.herm_d = c.herm_d;
+      g.route = c.route;
+      g.literal = literal;
+      g.has_q = s.has_q;
+      g.f_R = f_R;
     }
     c.group = it->second;
     c.member = (int)ctx->groups[it->second].ids.size();
@@ -1135,252 +1248,37 @@ int GroupConstraints(cxk_context* ctx, const FinalizeSwitches& sw) {
   return CXK_SUCCESS;
 }
 
-// The device copy of one group's data in the layout its kernels read, and its work space.
+// The device copy of one group's data in the layout its kernels read, and its work space: what every route shares,
+// then the route's own stage (each beside the view of what it allocates, above).
 int UploadGroup(cxk_context* ctx, Group& g, const FinalizeSwitches& sw) {
   const size_t cnt = g.ids.size();
-  size_t a_sz = 0, c_sz = 0, w_sz = 0;
-  switch (g.type) {
-    case CXK_LMI:
-      a_sz = (size_t)g.m * g.n * g.n;
-      c_sz = w_sz = (size_t)g.n * g.n;
-      g.large = !(LmiTakeLds(g.n) <= kLdsLimit && LmiPrepareLds(g.n, g.m) <= kLdsLimit);
-      if (g.factored) {
-        // held by its factors in front of the large-order route, whatever its order (kernels_lmi_factored.hip.h)
-        a_sz = 0;  // the matrices are never formed
-        g.large = true;
-        g.mfma = g.schur_gemm = false;
-      } else {
-        // shapes past the register kernels' instances assemble through the batched GEMM (measured
-        // 1.5 - 3.3x faster than lmi_schur_generic at 1000 constraints: orders 25 up, and smaller
-        // orders with more variables than lmi_schur_mfma's LDS images hold, e.g. order 22, m = 20
-        // 285 -> 133 us, order 10, m = 60 496 -> 148 us; CXK_GEMM_MIN_N moves the threshold for
-        // comparison runs)
-        g.mfma = !g.sparse && !g.large && !g.literal && !sw.schur_generic && LmiMfmaSupports(g.n, g.m, g.herm_d);
-        g.schur_gemm = !g.sparse && !g.literal && (g.large || (!g.mfma && g.n >= sw.gemm_min_n &&
-                                   cnt * 2 * ((size_t)g.m + 1) * g.n * g.n * sizeof(double) <= ((size_t)8 << 30)));
-      }
-      break;
-    case CXK_LINEAR:
-      a_sz = (size_t)g.n * g.m;
-      c_sz = w_sz = (size_t)g.n;
-      break;
-    case CXK_SOC:
-      a_sz = (size_t)(g.n + 1) * g.m;
-      c_sz = w_sz = (size_t)(g.n + 1);
-      break;
-    case CXK_STATIC:
-      a_sz = (size_t)g.m * g.m;
-      c_sz = (size_t)g.m;  // constant AQc (zeros for a quadratic-cost block)
-      break;
-    case CXK_QUAD:
-      a_sz = (size_t)(g.n + 1) * g.m;
-      c_sz = w_sz = (size_t)(g.n + 1);
-      break;
-    case CXK_OCT:
-      a_sz = (size_t)g.m * 8 * g.n * g.n;
-      c_sz = w_sz = (size_t)8 * g.n * g.n;
-      break;
+  const GroupSizes sz = SizesOf(g);
+  if (g.type == CXK_LMI) {
+    const LmiAssemblyChoice a = ChooseLmiAssembly(g.route, g.n, g.m, cnt, g.literal, LmiMfmaSupports(g.n, g.m, g.herm_d),
+                                                  sw.schur_generic, sw.gemm_min_n);
+    g.large = a.large;
+    g.assembly = a.assembly;
   }
-  if (g.type == CXK_LMI && g.sparse) {
-    if (UploadSparseLmi(ctx, g)) return CXK_FAILURE;
-    a_sz = 0;  // no dense copy of A on the device
-  }
-  if (g.lsparse || g.ssparse) {
-    if (UploadSparseLinear(ctx, g)) return CXK_FAILURE;
-    a_sz = 0;  // likewise
-  }
-  // lmi_schur_mfma reads [A_1 .. A_m | C] of a constraint as one contiguous array of stacked
-  // rows: such groups keep a copy of C right behind the A_i (LmiGroup::a_stride)
-  const size_t a_blk = a_sz + (g.type == CXK_LMI && (g.mfma || g.schur_gemm) ? c_sz : 0);
-  std::vector<double> hA(a_blk * cnt), hC(c_sz * cnt);
-  for (size_t k = 0; k < cnt; k++) {
-    const ConstraintRec& c = ctx->cons[g.ids[k]];
-    if (a_sz) std::copy(c.A.begin(), c.A.end(), hA.begin() + k * a_blk);
-    if (a_blk > a_sz) std::copy(c.C.begin(), c.C.end(), hA.begin() + k * a_blk + a_sz);
-    std::copy(c.C.begin(), c.C.end(), hC.begin() + k * c_sz);
-  }
-  CXK_TRY(g.A.upload(hA));
-  CXK_TRY(g.C.upload(hC));
-  if (g.type == CXK_LMI && g.mfma && LmiMfmaPaddedOrder(g.n) != g.n && !(g.herm_d == 2 && g.n == 24)) {
-    const int np = LmiMfmaPaddedOrder(g.n), n = g.n;
-    const size_t blk = (size_t)(g.m + 1) * np * np;
-    std::vector<double> hp(blk * cnt, 0.0);
-    for (size_t k = 0; k < cnt; k++) {
-      const ConstraintRec& c = ctx->cons[g.ids[k]];
-      for (int i = 0; i <= g.m; i++) {
-        const double* src = i < g.m ? c.A.data() + (size_t)i * n * n : c.C.data();
-        double* dst = hp.data() + k * blk + (size_t)i * np * np;
-        for (int col = 0; col < n; col++) std::copy(src + (size_t)col * n, src + (size_t)col * n + n, dst + (size_t)col * np);
-      }
-    }
-    CXK_TRY(g.Apad.upload(hp));
-  }
-  if (g.type == CXK_LMI && g.herm_d > 1 && g.schur_gemm && !g.literal && !sw.no_herm_fold) {
-    // Hermitian cones over C / H on the batched-GEMM assembly: the folded form needs only the first
-    // n / herm_d columns of every matrix of the real representation (kernels_lmi_large.hip.h)
-    const int n = g.n, n0 = g.n / g.herm_d;
-    const size_t per = (size_t)n * n0, m1 = (size_t)g.m + 1;
-    std::vector<double> hl(per * m1 * cnt);
-    for (size_t k = 0; k < cnt; k++) {
-      const ConstraintRec& c = ctx->cons[g.ids[k]];
-      for (size_t i = 0; i < m1; i++) {
-        const double* src = i < (size_t)g.m ? c.A.data() + i * (size_t)n * n : c.C.data();
-        std::copy(src, src + per, hl.begin() + (k * m1 + i) * per);
-      }
-    }
-    CXK_TRY(g.Aleft.upload(hl));
-  }
-  if (g.type == CXK_LMI && !g.factored && !g.literal && !sw.no_packed_slack && g.n == 20 &&
-      LmiPrepareRowsSupports(g.n, g.m, g.herm_d, g.sparse)) {
-    // the slack pass of PrepareStep / the eigenvalue query streams every A_i once more per call: a
-    // packed copy of the lower triangles (the data is exactly symmetric) halves those bytes
-    const int n = g.n, pk = n * (n + 1) / 2;
-    std::vector<double> hp((size_t)pk * g.m * cnt);
-    for (size_t k = 0; k < cnt; k++) {
-      const ConstraintRec& c = ctx->cons[g.ids[k]];
-      for (int i = 0; i < g.m; i++) {
-        const double* src = c.A.data() + (size_t)i * n * n;
-        double* dst = hp.data() + (k * g.m + i) * (size_t)pk;
-        for (int col = 0; col < n; col++)
-          for (int row = col; row < n; row++) *dst++ = src[row + (size_t)col * n];
-      }
-    }
-    CXK_TRY(g.Apk.upload(hp));
-  }
-  if (g.type == CXK_QUAD && g.qstream) {
-    // held in HBM: Q as it is, the constants (Q c1, c1' Q c1, A_gram) on the device (QuadStreamConstants below)
-    const size_t n = (size_t)g.n, m = (size_t)g.m, tiles = (n + kQuadStreamRowTile - 1) / kQuadStreamRowTile;
-    g.splits = g.has_q ? QuadStreamSplits(g.n, (long long)cnt) : 1;
-    if (g.has_q && sw.gram_splits > 0) g.splits = sw.gram_splits;  // (comparison runs)
-    CXK_DEMAND(cnt * std::max<size_t>(std::max<size_t>(m, (m * m + kQuadStreamBlock - 1) / kQuadStreamBlock),
-                                      std::max<size_t>(tiles * (size_t)g.splits, (n + 1 + kSocStreamRowTile - 1) / kSocStreamRowTile)) <=
-                   (size_t)INT_MAX,
-               "a group of streamed quadratic cones with more than 2^31 columns, row tiles or blocks is not supported");
-    std::vector<double> hQ(g.has_q ? n * n * cnt : 0);
-    if (g.has_q)
-      for (size_t k = 0; k < cnt; k++) std::copy(ctx->cons[g.ids[k]].Q.begin(), ctx->cons[g.ids[k]].Q.end(), hQ.begin() + k * n * n);
-    CXK_TRY(g.qQ.upload(hQ));
-    CXK_TRY(g.qGram.alloc(m * m * cnt));
-    CXK_TRY(g.qS.alloc(w_sz * cnt));
-    CXK_TRY(g.st_vec.alloc(QuadStreamVecDoubles(cnt, n, m)));
-    CXK_TRY(g.ws_part.alloc(g.has_q ? cnt * (size_t)g.splits * 2 * n : 0));
-  } else if (g.type == CXK_QUAD) {
-    // A_gram = A1' (Q A1), made once (QuadraticConstraintBase::Initialize, quadratic_cone_constraint.cc:216-219)
-    const int n = g.n, m = g.m, len = n + 1;
-    std::vector<double> hQ(g.has_q ? (size_t)n * n * cnt : 0), hG((size_t)m * m * cnt, 0.0), qa((size_t)n);
-    for (size_t k = 0; k < cnt; k++) {
-      const ConstraintRec& c = ctx->cons[g.ids[k]];
-      if (g.has_q) std::copy(c.Q.begin(), c.Q.end(), hQ.begin() + k * (size_t)n * n);
-      for (int j = 0; j < m; j++) {
-        const double* aj = c.A.data() + (size_t)j * len + 1;
-        for (int i = 0; i < n; i++) {
-          double s2 = g.has_q ? 0.0 : aj[i];
-          if (g.has_q)
-            for (int q2 = 0; q2 < n; q2++) s2 += c.Q[(size_t)q2 * n + i] * aj[q2];
-          qa[(size_t)i] = s2;
-        }
-        for (int i = 0; i < m; i++) {
-          const double* ai = c.A.data() + (size_t)i * len + 1;
-          double s2 = 0;
-          for (int q2 = 0; q2 < n; q2++) s2 += ai[q2] * qa[(size_t)q2];
-          hG[k * (size_t)m * m + (size_t)j * m + i] = s2;
-        }
-      }
-    }
-    CXK_TRY(g.qQ.upload(hQ));
-    CXK_TRY(g.qGram.upload(hG));
-    CXK_TRY(g.qS.alloc(w_sz * cnt));
-  }
-  CXK_TRY(g.W.alloc(w_sz * cnt));
-  CXK_TRY(g.T1.alloc(w_sz * cnt));
-  CXK_TRY(g.T2.alloc(g.type == CXK_LINEAR ? w_sz * cnt : 0));
+  // the routes that hold their data as nonzeros or factors keep no dense copy of A on the device
+  const bool dense_a = g.route != ConeRoute::kLmiSparse && g.route != ConeRoute::kLmiFactored &&
+                       g.route != ConeRoute::kLinearSparse && g.route != ConeRoute::kSocSparse;
+  if (UploadDenseData(ctx, g, dense_a ? sz.a : 0, sz.c)) return CXK_FAILURE;
+  CXK_TRY(g.W.alloc(sz.w * cnt));
+  CXK_TRY(g.T1.alloc(sz.w * cnt));
+  CXK_TRY(g.T2.alloc(g.type == CXK_LINEAR ? sz.w * cnt : 0));
   CXK_TRY(g.dids.upload(g.ids));
-  if (g.type == CXK_QUAD && g.qstream && QuadStreamConstants(ctx, g)) return CXK_FAILURE;
-  if (g.type == CXK_LMI && g.sparse && (g.large || !g.sp_small)) {
-    const size_t nn = (size_t)g.n * g.n;
-    CXK_TRY(g.ws_main.alloc(cnt * 8 * nn));  // step temporaries; C W and W C W during assembly
-    CXK_TRY(g.ws_part.alloc(cnt * 2 * kSparseCParts));
-    CXK_TRY(g.ws_piv.alloc(cnt * (size_t)g.n));
-  }
-  if (g.streamed) {
-    const size_t len = (size_t)g.n + 1, m = (size_t)g.m;
-    CXK_DEMAND(cnt * std::max<size_t>(m, (len + kSocStreamRowTile - 1) / kSocStreamRowTile) <= (size_t)INT_MAX,
-               "a group of streamed second-order cones with more than 2^31 columns or row tiles is not supported");
-    g.splits = SocStreamSplits((int)len, g.m, (long long)cnt);
-    g.st_stages = sw.soc_stream_stages;
-    if (sw.gram_splits > 0) g.splits = sw.gram_splits;  // (comparison runs)
-    CXK_TRY(g.ws_main.alloc(cnt * len * m));
-    CXK_TRY(g.st_vec.alloc(3 * cnt * len));
-    CXK_TRY(g.st_det.alloc(cnt));
-    CXK_TRY(g.ws_gf.alloc(cnt * m * m));
-    CXK_TRY(g.ws_part.alloc(g.splits > 1 ? (size_t)g.splits * std::min<size_t>(cnt, 65535) * m * m : 0));
-  }
-  if (g.tiled) {
-    const size_t len = (size_t)g.n, m = (size_t)g.m, tiles = (len + kLinTiledRowTile - 1) / kLinTiledRowTile;
-    CXK_DEMAND(cnt * std::max(m, tiles) <= (size_t)INT_MAX,
-               "a group of tiled linear blocks with more than 2^31 columns or row tiles is not supported");
-    g.splits = SocStreamSplits((int)len, g.m, (long long)cnt);
-    if (sw.gram_splits > 0) g.splits = sw.gram_splits;  // (comparison runs)
-    CXK_TRY(g.ws_main.alloc(cnt * len * m));
-    CXK_TRY(g.ws_gf.alloc(cnt * m * m));
-    CXK_TRY(g.ws_part.alloc(g.splits > 1 ? (size_t)g.splits * std::min<size_t>(cnt, 65535) * m * m : 0));
-    CXK_TRY(g.lt_part.alloc(cnt * tiles * 4));
-  }
-  if (g.lsparse) {
-    const size_t len = (size_t)g.n, m = (size_t)g.m, tiles = (len + kLinTiledRowTile - 1) / kLinTiledRowTile;
-    const size_t chunks = m <= (size_t)kLinSparseWaveCols ? 1 : (m + kLinSparseColChunk - 1) / kLinSparseColChunk;
-    CXK_DEMAND(cnt * std::max(m * chunks, tiles) <= (size_t)INT_MAX,
-               "a group of sparse linear blocks with more than 2^31 column chunks or row tiles is not supported");
-    CXK_TRY(g.lt_part.alloc(cnt * tiles * 4));
-  }
-  if (g.ssparse) {
-    const size_t len = (size_t)g.n + 1, m = (size_t)g.m, tiles = (len + kSocStreamRowTile - 1) / kSocStreamRowTile;
-    CXK_DEMAND(cnt * std::max(std::max(m * (size_t)SocSparseGramChunks(g.m), tiles), (size_t)SocSparseCombineTiles(g.m)) <=
-                   (size_t)INT_MAX,
-               "a group of sparse second-order cones with more than 2^31 column chunks, row tiles or tiles of the Schur "
-               "block is not supported");
-    CXK_TRY(g.st_vec.alloc(SocSparseVecDoubles(cnt, len, m)));
-    CXK_TRY(g.ss_const.alloc(SocSparseConstDoubles(cnt, m)));
-    if (SocSparseConstants(ctx, g)) return CXK_FAILURE;
-  }
-  if (g.factored) {
-    const size_t n = (size_t)g.n, R = (size_t)g.f_R, m = (size_t)g.m;
-    CXK_DEMAND(cnt <= 65535, "a group of more than 65535 equal-shaped factored LMIs is not supported");
-    std::vector<double> hF(cnt * n * R), hs(cnt * R);
-    std::vector<int> hp(cnt * (m + 1)), hv(cnt * R);
-    g.f_rank_one = true;
-    for (size_t k = 0; k < cnt; k++) {
-      const ConstraintRec& c = ctx->cons[g.ids[k]];
-      std::copy(c.f_F.begin(), c.f_F.end(), hF.begin() + k * n * R);
-      std::copy(c.f_sigma.begin(), c.f_sigma.end(), hs.begin() + k * R);
-      std::copy(c.f_ptr.begin(), c.f_ptr.end(), hp.begin() + k * (m + 1));
-      for (size_t i = 0; i < m; i++) {
-        g.f_rank_one = g.f_rank_one && c.f_ptr[i + 1] - c.f_ptr[i] == 1;
-        for (int q = c.f_ptr[i]; q < c.f_ptr[i + 1]; q++) hv[k * R + (size_t)q] = (int)i;
-      }
-    }
-    CXK_TRY(g.f_F.upload(hF));
-    CXK_TRY(g.f_sigma.upload(hs));
-    CXK_TRY(g.f_ptr.upload(hp));
-    CXK_TRY(g.f_var.upload(hv));
-    CXK_TRY(g.f_ws.alloc(LmiFactoredWsDoubles(cnt, n, R)));
-    CXK_TRY(g.ws_main.alloc(cnt * 8 * n * n));  // step temporaries; C W and W C W during assembly
-    CXK_TRY(g.ws_part.alloc(cnt * 2 * kSparseCParts));
-    CXK_TRY(g.ws_piv.alloc(cnt * n));
-  }
-  if (g.schur_gemm) {
-    const size_t nn = (size_t)g.n * g.n, m1 = (size_t)g.m + 1;
-    // split-K of the contraction: enough workgroups to fill the chip, at most one K step each
-    const int ksteps = (int)((nn + kGemmBK - 1) / kGemmBK);
-    const int tiles = (int)(((m1 + 63) / 64) * ((m1 + 63) / 64));
-    // (measured on BASELINE config 2, one constraint, K = 40 000: 39 / 78 / 156 / 312 / 512 / 768 / 1024
-    // splits -> 115 / 93 / 82 / 81 / 76 / 80 / 82 us per KKT solve)
-    g.splits = std::max(1, std::min(std::max(1, ksteps / 4), (int)((512 + cnt * tiles - 1) / (cnt * tiles))));
-    if (sw.gram_splits > 0) g.splits = sw.gram_splits;  // (comparison runs)
-    CXK_TRY(g.ws_main.alloc(cnt * std::max(2 * m1 * nn, 8 * nn)));
-    CXK_TRY(g.ws_gf.alloc(cnt * m1 * m1));
-    CXK_TRY(g.ws_piv.alloc(cnt * (size_t)g.n));
-    CXK_TRY(g.ws_part.alloc(g.splits > 1 ? (size_t)g.splits * cnt * m1 * m1 : 0));
+  switch (g.route) {
+    case ConeRoute::kLinearLds: case ConeRoute::kSocLds: case ConeRoute::kStatic: case ConeRoute::kOct:
+      return CXK_SUCCESS;  // (the dense copy is all their kernels read)
+    case ConeRoute::kLinearTiled: return UploadLinearTiled(ctx, g, sw);
+    case ConeRoute::kLinearSparse: return UploadLinearSparse(ctx, g);
+    case ConeRoute::kSocStreamed: return UploadSocStream(ctx, g, sw);
+    case ConeRoute::kSocSparse: return UploadSocSparse(ctx, g);
+    case ConeRoute::kQuadLds: return UploadQuadGram(ctx, g);
+    case ConeRoute::kQuadStreamed: return UploadQuadStream(ctx, g, sw);
+    case ConeRoute::kLmiDense: return UploadLmiDense(ctx, g, sw);
+    case ConeRoute::kLmiSparse: return UploadLmiSparse(ctx, g);
+    case ConeRoute::kLmiFactored: return UploadLmiFactored(ctx, g);
   }
   return CXK_SUCCESS;
 }
@@ -1389,13 +1287,22 @@ int LaunchSetIdentity(cxk_context* ctx) {
   for (Group& g : ctx->groups) {
     const size_t cnt = g.ids.size();
     if (cnt == 0) continue;
-    if (g.type == CXK_LMI)
-      lmi_set_identity<<<GridFor(cnt * g.n * g.n, 256), 256, 0, ctx->stream>>>(MakeLmi(g));
-    else if (g.type == CXK_LINEAR || g.type == CXK_SOC || g.type == CXK_QUAD)
-      vec_set_identity<<<GridFor(cnt * (g.n + 1), 256), 256, 0, ctx->stream>>>(MakeVec(g),
-                                                                               g.type != CXK_LINEAR);
-    else if (g.type == CXK_OCT)
-      oct_set_identity<<<GridFor(cnt * 8 * g.n * g.n, 256), 256, 0, ctx->stream>>>(MakeOct(g));
+    switch (g.route) {
+      case ConeRoute::kLmiDense: case ConeRoute::kLmiSparse: case ConeRoute::kLmiFactored:
+        lmi_set_identity<<<GridFor(cnt * g.n * g.n, 256), 256, 0, ctx->stream>>>(MakeLmi(g));
+        break;
+      case ConeRoute::kLinearLds: case ConeRoute::kLinearTiled: case ConeRoute::kLinearSparse:
+        vec_set_identity<<<GridFor(cnt * (g.n + 1), 256), 256, 0, ctx->stream>>>(MakeVec(g), false);
+        break;
+      case ConeRoute::kSocLds: case ConeRoute::kSocStreamed: case ConeRoute::kSocSparse:
+      case ConeRoute::kQuadLds: case ConeRoute::kQuadStreamed:
+        vec_set_identity<<<GridFor(cnt * (g.n + 1), 256), 256, 0, ctx->stream>>>(MakeVec(g), true);
+        break;
+      case ConeRoute::kStatic: break;  // (no scaling point)
+      case ConeRoute::kOct:
+        oct_set_identity<<<GridFor(cnt * 8 * g.n * g.n, 256), 256, 0, ctx->stream>>>(MakeOct(g));
+        break;
+    }
   }
   CXK_TRY(hipGetLastError());
   return CXK_SUCCESS;
@@ -1413,19 +1320,30 @@ int LaunchLinearLineSearch(cxk_context* ctx, double dinf_upper_bound, double c_s
   a.out = ctx->info2.p;
   for (Group& g : ctx->groups) {
     const int cnt = (int)g.ids.size();
-    if (cnt == 0 || g.type != CXK_LINEAR) continue;
-    if (g.lsparse) {
-      const LinSparseGroup d = MakeLinSparse(g);
-      const int tiles = (g.n + kLinTiledRowTile - 1) / kLinTiledRowTile;
-      linear_sparse_line_search<<<(unsigned)((size_t)cnt * tiles), kLinTiledBlock, 0, ctx->stream>>>(d, a, tiles);
-      linear_tiled_line_finish<<<cnt, kLinTiledBlock, 0, ctx->stream>>>(d.t, a, tiles);
-    } else if (g.tiled) {
-      const LinTiledGroup d = MakeLinTiled(g);
-      const int tiles = (g.n + kLinTiledRowTile - 1) / kLinTiledRowTile;
-      linear_tiled_line_search<<<(unsigned)((size_t)cnt * tiles), kLinTiledBlock, 0, ctx->stream>>>(d, a, tiles);
-      linear_tiled_line_finish<<<cnt, kLinTiledBlock, 0, ctx->stream>>>(d, a, tiles);
-    } else {
-      linear_line_search<<<cnt, 256, sizeof(double) * 2 * g.m, ctx->stream>>>(MakeVec(g), a);
+    if (cnt == 0) continue;
+    const int tiles = (g.n + kLinTiledRowTile - 1) / kLinTiledRowTile;
+    switch (g.route) {
+      case ConeRoute::kLinearLds:
+        linear_line_search<<<cnt, 256, sizeof(double) * 2 * g.m, ctx->stream>>>(MakeVec(g), a);
+        break;
+      case ConeRoute::kLinearTiled: {
+        const LinTiledGroup d = MakeLinTiled(g);
+        linear_tiled_line_search<<<(unsigned)((size_t)cnt * tiles), kLinTiledBlock, 0, ctx->stream>>>(d, a, tiles);
+        linear_tiled_line_finish<<<cnt, kLinTiledBlock, 0, ctx->stream>>>(d, a, tiles);
+        break;
+      }
+      case ConeRoute::kLinearSparse: {
+        const LinSparseGroup d = MakeLinSparse(g);
+        linear_sparse_line_search<<<(unsigned)((size_t)cnt * tiles), kLinTiledBlock, 0, ctx->stream>>>(d, a, tiles);
+        linear_tiled_line_finish<<<cnt, kLinTiledBlock, 0, ctx->stream>>>(d.t, a, tiles);
+        break;
+      }
+      // the line search bounds the step by the linear constraints only
+      case ConeRoute::kSocLds: case ConeRoute::kSocStreamed: case ConeRoute::kSocSparse:
+      case ConeRoute::kQuadLds: case ConeRoute::kQuadStreamed:
+      case ConeRoute::kLmiDense: case ConeRoute::kLmiSparse: case ConeRoute::kLmiFactored:
+      case ConeRoute::kStatic: case ConeRoute::kOct:
+        break;
     }
   }
   CXK_TRY(hipGetLastError());
@@ -1620,7 +1538,7 @@ bool StepTailOk(const cxk_context* ctx, int affine) {
     only = &g;
   }
   return only && only->type == CXK_LMI && !only->large && !only->literal && only->ids.size() == ctx->cons.size() &&
-         LmiPrepareRowsSupports(only->n, only->m, only->herm_d, only->sparse);
+         LmiPrepareRowsSupports(only->n, only->m, only->herm_d, only->route == ConeRoute::kLmiSparse);
 }
 namespace {
 int MakeStepTail(cxk_context* ctx, int mode, StepTail* t) {
@@ -1659,23 +1577,6 @@ int MakeStepTail(cxk_context* ctx, int mode, StepTail* t) {
   return CXK_SUCCESS;
 }
 
-// Kernel clocks of the step kernels (CXK_CLOCK_QUERY / _PREPARE / _TAKE): a program whose constraints
-// are ONE group on a register kernel carries the event pair on that dispatch; anything else is
-// bracketed by event records around its launches.
-struct StepClock {
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  bool sample = false, on_dispatch = false;
-};
-StepClock BeginStepClock(cxk_context* ctx, int slot, bool one_register_kernel) {
-  StepClock c;
-  c.sample = ClockSample(ctx, slot, &c.e0, &c.e1);
-  c.on_dispatch = c.sample && one_register_kernel;
-  if (c.sample && !c.on_dispatch) (void)hipEventRecord(c.e0, ctx->stream);
-  return c;
-}
-void EndStepClock(cxk_context* ctx, const StepClock& c) {
-  if (c.sample && !c.on_dispatch) (void)hipEventRecord(c.e1, ctx->stream);
-}
 int NonEmptyGroups(const cxk_context* ctx) {
   int n = 0;
   for (const Group& g : ctx->groups) n += !g.ids.empty();
@@ -1707,79 +1608,82 @@ int LaunchPrepareGroups(cxk_context* ctx, int pmode, const StepArgs& sa, const S
   for (Group& g : ctx->groups) {
     const int cnt = (int)g.ids.size();
     if (cnt == 0) continue;
-    if (g.type == CXK_LMI) {
-      switch (AsPrepareKernel(LmiPrepareKernel(ctx, g, pmode))) {
-        case kPrepareLarge:
-          if (g.factored) {
-            CXK_TRY(LmiFactoredSlack(MakeLmi(g), MakeLmiFactored(g), sa, MakeLargeWs(g), ctx->stream));
-            CXK_TRY(LmiLargeAfterSlack(MakeLmi(g), sa, MakeLargeWs(g), MODE, ctx->stream));
-          } else {
+    switch (g.route) {
+      case ConeRoute::kLmiFactored:  // (`large`: the factored slack in front of the large-order kernels)
+        CXK_TRY(LmiFactoredSlack(MakeLmi(g), MakeLmiFactored(g), sa, MakeLargeWs(g), ctx->stream));
+        CXK_TRY(LmiLargeAfterSlack(MakeLmi(g), sa, MakeLargeWs(g), MODE, ctx->stream));
+        break;
+      case ConeRoute::kLmiDense: case ConeRoute::kLmiSparse:
+        switch (AsPrepareKernel(LmiPrepareKernel(ctx, g, pmode))) {
+          case kPrepareLarge:
             CXK_TRY(LmiLargePrepare(MakeLmi(g), sa, MakeLargeWs(g), MODE, ctx->stream));
-          }
-          break;
-        case kPrepareRowsPacked:
-        case kPrepareRowsExact:  // (the instance reads g.Apk when there is one)
-          CXK_LAUNCH_CLOCKED(clk, (lmi_prepare_rows<MODE, 20, true>), (cnt + 3) / 4 + tail_blocks, 256, MakeLmi(g), sa, tail);
-          break;
-        case kPrepareRowsOdd:
-        case kPrepareRowsEven:  // (an order below 20 on the same instance)
-          CXK_LAUNCH_CLOCKED(clk, (lmi_prepare_rows<MODE, 20, false>), (cnt + 3) / 4 + tail_blocks, 256, MakeLmi(g), sa, tail);
-          break;
-        case kPrepareGeneric20:
-          lmi_prepare_generic<MODE, 20><<<cnt, 256, LmiPrepareLds(g.n, g.m), ctx->stream>>>(MakeLmi(g), sa);
-          break;
-        default:  // kPrepareGeneric
-          lmi_prepare_generic<MODE, 0><<<cnt, 256, LmiPrepareLds(g.n, g.m), ctx->stream>>>(MakeLmi(g), sa);
-          break;
+            break;
+          case kPrepareRowsPacked:
+          case kPrepareRowsExact:  // (the instance reads g.Apk when there is one)
+            CXK_LAUNCH_CLOCKED(clk, (lmi_prepare_rows<MODE, 20, true>), (cnt + 3) / 4 + tail_blocks, 256, MakeLmi(g), sa, tail);
+            break;
+          case kPrepareRowsOdd:
+          case kPrepareRowsEven:  // (an order below 20 on the same instance)
+            CXK_LAUNCH_CLOCKED(clk, (lmi_prepare_rows<MODE, 20, false>), (cnt + 3) / 4 + tail_blocks, 256, MakeLmi(g), sa, tail);
+            break;
+          case kPrepareGeneric20:
+            lmi_prepare_generic<MODE, 20><<<cnt, 256, LmiPrepareLds(g.n, g.m), ctx->stream>>>(MakeLmi(g), sa);
+            break;
+          default:  // kPrepareGeneric
+            lmi_prepare_generic<MODE, 0><<<cnt, 256, LmiPrepareLds(g.n, g.m), ctx->stream>>>(MakeLmi(g), sa);
+            break;
+        }
+        break;
+      case ConeRoute::kLinearLds: linear_prepare<MODE><<<cnt, 256, sizeof(double) * g.m, ctx->stream>>>(MakeVec(g), sa); break;
+      case ConeRoute::kLinearTiled: {
+        const LinTiledGroup d = MakeLinTiled(g);
+        const int tiles = (g.n + kLinTiledRowTile - 1) / kLinTiledRowTile;
+        linear_tiled_slack<MODE><<<(unsigned)((size_t)cnt * tiles), kLinTiledBlock, 0, ctx->stream>>>(d, sa, tiles);
+        if (MODE == 1 || !sa.affine)  // (the affine update has no reduction)
+          linear_tiled_finish<MODE><<<cnt, kLinTiledBlock, 0, ctx->stream>>>(d, sa, tiles);
+        break;
       }
+      case ConeRoute::kLinearSparse: {
+        const LinSparseGroup d = MakeLinSparse(g);
+        const int tiles = (g.n + kLinTiledRowTile - 1) / kLinTiledRowTile;
+        linear_sparse_slack<MODE><<<(unsigned)((size_t)cnt * tiles), kLinTiledBlock, 0, ctx->stream>>>(d, sa, tiles);
+        if (MODE == 1 || !sa.affine)  // (the affine update has no reduction)
+          linear_tiled_finish<MODE><<<cnt, kLinTiledBlock, 0, ctx->stream>>>(d.t, sa, tiles);
+        break;
+      }
+      case ConeRoute::kSocLds: soc_prepare<MODE><<<cnt, 64, SocPrepareLds(g.n, g.m), ctx->stream>>>(MakeVec(g), sa); break;
+      case ConeRoute::kSocStreamed: {
+        const SocStreamGroup d = MakeSocStream(g);
+        const int tiles = (g.n + 1 + kSocStreamRowTile - 1) / kSocStreamRowTile;
+        soc_stream_slack<<<(unsigned)((size_t)cnt * tiles), kSocStreamBlock, 0, ctx->stream>>>(d, sa, tiles);
+        soc_stream_prepare<MODE><<<cnt, kSocStreamBlock, 0, ctx->stream>>>(d, sa);
+        break;
+      }
+      case ConeRoute::kSocSparse: {
+        const SocSparseGroup d = MakeSocSparse(g);
+        const int tiles = (g.n + 1 + kSocStreamRowTile - 1) / kSocStreamRowTile;
+        soc_sparse_slack<<<(unsigned)((size_t)cnt * tiles), kSocStreamBlock, 0, ctx->stream>>>(d, sa, tiles);
+        soc_stream_prepare<MODE><<<cnt, kSocStreamBlock, 0, ctx->stream>>>(d.st, sa);
+        break;
+      }
+      case ConeRoute::kQuadLds: quad_prepare<MODE><<<cnt, 64, QuadPrepareLds(g.n, g.m), ctx->stream>>>(MakeQuad(g), sa); break;
+      case ConeRoute::kQuadStreamed: {
+        const QuadStreamGroup d = MakeQuadStream(g);
+        const int tiles = (g.n + 1 + kSocStreamRowTile - 1) / kSocStreamRowTile;
+        soc_stream_slack<<<(unsigned)((size_t)cnt * tiles), kSocStreamBlock, 0, ctx->stream>>>(QuadStreamSlackView(g, d), sa, tiles);
+        QuadStreamVecs x;  // Q [w1, ms1] in one pass
+        x.p[0] = d.W + 1;
+        x.p[1] = d.ms + 1;
+        x.stride[0] = x.stride[1] = (size_t)g.n + 1;
+        CXK_TRY(LaunchQuadStreamQmv<2>(d, x, ctx->stream));
+        quad_stream_prepare_mid<MODE><<<cnt, kQuadStreamBlock, 0, ctx->stream>>>(d, sa);
+        CXK_TRY(LaunchQuadStreamQmv<1>(d, QuadStreamOne(d.dv, (size_t)g.n), ctx->stream));
+        quad_stream_prepare_finish<MODE><<<cnt, kQuadStreamBlock, 0, ctx->stream>>>(d, sa);
+        break;
+      }
+      case ConeRoute::kStatic: break;  // (no cone: nothing to prepare)
+      case ConeRoute::kOct: oct_prepare<MODE><<<cnt, 64, sizeof(double) * (size_t)g.m, ctx->stream>>>(MakeOct(g), sa); break;
     }
-    else if (g.type == CXK_LINEAR && g.lsparse) {
-      const LinSparseGroup d = MakeLinSparse(g);
-      const int tiles = (g.n + kLinTiledRowTile - 1) / kLinTiledRowTile;
-      linear_sparse_slack<MODE><<<(unsigned)((size_t)cnt * tiles), kLinTiledBlock, 0, ctx->stream>>>(d, sa, tiles);
-      if (MODE == 1 || !sa.affine)  // (the affine update has no reduction)
-        linear_tiled_finish<MODE><<<cnt, kLinTiledBlock, 0, ctx->stream>>>(d.t, sa, tiles);
-    }
-    else if (g.type == CXK_LINEAR && g.tiled) {
-      const LinTiledGroup d = MakeLinTiled(g);
-      const int tiles = (g.n + kLinTiledRowTile - 1) / kLinTiledRowTile;
-      linear_tiled_slack<MODE><<<(unsigned)((size_t)cnt * tiles), kLinTiledBlock, 0, ctx->stream>>>(d, sa, tiles);
-      if (MODE == 1 || !sa.affine)  // (the affine update has no reduction)
-        linear_tiled_finish<MODE><<<cnt, kLinTiledBlock, 0, ctx->stream>>>(d, sa, tiles);
-    }
-    else if (g.type == CXK_LINEAR)
-      linear_prepare<MODE><<<cnt, 256, sizeof(double) * g.m, ctx->stream>>>(MakeVec(g), sa);
-    else if (g.type == CXK_SOC && g.ssparse) {
-      const SocSparseGroup d = MakeSocSparse(g);
-      const int tiles = (g.n + 1 + kSocStreamRowTile - 1) / kSocStreamRowTile;
-      soc_sparse_slack<<<(unsigned)((size_t)cnt * tiles), kSocStreamBlock, 0, ctx->stream>>>(d, sa, tiles);
-      soc_stream_prepare<MODE><<<cnt, kSocStreamBlock, 0, ctx->stream>>>(d.st, sa);
-    }
-    else if (g.type == CXK_SOC && g.streamed) {
-      const SocStreamGroup d = MakeSocStream(g);
-      const int tiles = (g.n + 1 + kSocStreamRowTile - 1) / kSocStreamRowTile;
-      soc_stream_slack<<<(unsigned)((size_t)cnt * tiles), kSocStreamBlock, 0, ctx->stream>>>(d, sa, tiles);
-      soc_stream_prepare<MODE><<<cnt, kSocStreamBlock, 0, ctx->stream>>>(d, sa);
-    }
-    else if (g.type == CXK_SOC)
-      soc_prepare<MODE><<<cnt, 64, SocPrepareLds(g.n, g.m), ctx->stream>>>(MakeVec(g), sa);
-    else if (g.type == CXK_QUAD && g.qstream) {
-      const QuadStreamGroup d = MakeQuadStream(g);
-      const int tiles = (g.n + 1 + kSocStreamRowTile - 1) / kSocStreamRowTile;
-      soc_stream_slack<<<(unsigned)((size_t)cnt * tiles), kSocStreamBlock, 0, ctx->stream>>>(QuadStreamSlackView(g, d), sa, tiles);
-      QuadStreamVecs x;  // Q [w1, ms1] in one pass
-      x.p[0] = d.W + 1;
-      x.p[1] = d.ms + 1;
-      x.stride[0] = x.stride[1] = (size_t)g.n + 1;
-      CXK_TRY(LaunchQuadStreamQmv<2>(d, x, ctx->stream));
-      quad_stream_prepare_mid<MODE><<<cnt, kQuadStreamBlock, 0, ctx->stream>>>(d, sa);
-      CXK_TRY(LaunchQuadStreamQmv<1>(d, QuadStreamOne(d.dv, (size_t)g.n), ctx->stream));
-      quad_stream_prepare_finish<MODE><<<cnt, kQuadStreamBlock, 0, ctx->stream>>>(d, sa);
-    }
-    else if (g.type == CXK_QUAD)
-      quad_prepare<MODE><<<cnt, 64, QuadPrepareLds(g.n, g.m), ctx->stream>>>(MakeQuad(g), sa);
-    else if (g.type == CXK_OCT)
-      oct_prepare<MODE><<<cnt, 64, sizeof(double) * (size_t)g.m, ctx->stream>>>(MakeOct(g), sa);
   }
   EndStepClock(ctx, clk);
   CXK_TRY(hipGetLastError());
@@ -1860,51 +1764,49 @@ int LaunchTakeStep(cxk_context* ctx, double e_weight, double step_size, const do
   for (Group& g : ctx->groups) {
     const int cnt = (int)g.ids.size();
     if (cnt == 0) continue;
-    if (g.type == CXK_LMI) {
-      const int blocks = (cnt + 3) / 4;
-      switch (LmiTakeKernel(g)) {
-        case kTakeLargePade:
-        case kTakeLargeTaylor:  // (Pade or Taylor by g.herm_d inside)
-          CXK_TRY(LmiLargeTakeStep(MakeLmi(g), sa, MakeLargeWs(g), ctx->stream));
-          break;
-        case kTakeRows20:
-        case kTakeRows20Pad:
-          CXK_LAUNCH_CLOCKED(clk, (lmi_take_step_rows<20>), blocks, 256, MakeLmi(g), sa);
-          break;
-        case kTakeRows32:
-        case kTakeRows32Pad:
-          CXK_LAUNCH_CLOCKED(clk, (lmi_take_step_rows<32>), blocks, 256, MakeLmi(g), sa);
-          break;
-        case kTakeTaylor24:
-        case kTakeTaylor24Pad:
-          CXK_LAUNCH_CLOCKED(clk, (lmi_take_step_rows_taylor<24>), blocks, 256, MakeLmi(g), sa);
-          break;
-        case kTakeTaylor32:
-        case kTakeTaylor32Pad:
-          CXK_LAUNCH_CLOCKED(clk, (lmi_take_step_rows_taylor<32>), blocks, 256, MakeLmi(g), sa);
-          break;
-        case kTakeGeneric20:
-          lmi_take_step_generic<20><<<cnt, 256, LmiTakeLds(g.n), ctx->stream>>>(MakeLmi(g), sa);
-          break;
-        default:  // kTakeGeneric
-          lmi_take_step_generic<0><<<cnt, 256, LmiTakeLds(g.n), ctx->stream>>>(MakeLmi(g), sa);
-          break;
-      }
+    const int blocks = (cnt + 3) / 4;
+    switch (g.route) {
+      case ConeRoute::kLmiDense: case ConeRoute::kLmiSparse: case ConeRoute::kLmiFactored:
+        switch (LmiTakeKernel(g)) {
+          case kTakeLargePade:
+          case kTakeLargeTaylor:  // (Pade or Taylor by g.herm_d inside)
+            CXK_TRY(LmiLargeTakeStep(MakeLmi(g), sa, MakeLargeWs(g), ctx->stream));
+            break;
+          case kTakeRows20:
+          case kTakeRows20Pad:
+            CXK_LAUNCH_CLOCKED(clk, (lmi_take_step_rows<20>), blocks, 256, MakeLmi(g), sa);
+            break;
+          case kTakeRows32:
+          case kTakeRows32Pad:
+            CXK_LAUNCH_CLOCKED(clk, (lmi_take_step_rows<32>), blocks, 256, MakeLmi(g), sa);
+            break;
+          case kTakeTaylor24:
+          case kTakeTaylor24Pad:
+            CXK_LAUNCH_CLOCKED(clk, (lmi_take_step_rows_taylor<24>), blocks, 256, MakeLmi(g), sa);
+            break;
+          case kTakeTaylor32:
+          case kTakeTaylor32Pad:
+            CXK_LAUNCH_CLOCKED(clk, (lmi_take_step_rows_taylor<32>), blocks, 256, MakeLmi(g), sa);
+            break;
+          case kTakeGeneric20:
+            lmi_take_step_generic<20><<<cnt, 256, LmiTakeLds(g.n), ctx->stream>>>(MakeLmi(g), sa);
+            break;
+          default:  // kTakeGeneric
+            lmi_take_step_generic<0><<<cnt, 256, LmiTakeLds(g.n), ctx->stream>>>(MakeLmi(g), sa);
+            break;
+        }
+        break;
+      case ConeRoute::kLinearLds: case ConeRoute::kLinearTiled: case ConeRoute::kLinearSparse:  // (W is a dense vector on each)
+        linear_take_step<<<GridFor((size_t)cnt * g.n, 256), 256, 0, ctx->stream>>>(MakeVec(g), sa);
+        break;
+      case ConeRoute::kSocLds: soc_take_step<<<cnt, 64, SocTakeLds(g.n), ctx->stream>>>(MakeVec(g), sa); break;
+      case ConeRoute::kSocStreamed: soc_stream_take_step<<<cnt, kSocStreamBlock, 0, ctx->stream>>>(MakeSocStream(g), sa); break;
+      case ConeRoute::kSocSparse: soc_stream_take_step<<<cnt, kSocStreamBlock, 0, ctx->stream>>>(MakeSocSparse(g).st, sa); break;
+      case ConeRoute::kQuadLds: quad_take_step<<<cnt, 64, QuadTakeLds(g.n), ctx->stream>>>(MakeQuad(g), sa); break;
+      case ConeRoute::kQuadStreamed: quad_stream_take_step<<<cnt, kQuadStreamBlock, 0, ctx->stream>>>(MakeQuadStream(g), sa); break;
+      case ConeRoute::kStatic: break;  // (no cone: no step)
+      case ConeRoute::kOct: oct_take_step<<<cnt, 64, 0, ctx->stream>>>(MakeOct(g), sa); break;
     }
-    else if (g.type == CXK_LINEAR)
-      linear_take_step<<<GridFor((size_t)cnt * g.n, 256), 256, 0, ctx->stream>>>(MakeVec(g), sa);
-    else if (g.type == CXK_SOC && g.ssparse)
-      soc_stream_take_step<<<cnt, kSocStreamBlock, 0, ctx->stream>>>(MakeSocSparse(g).st, sa);
-    else if (g.type == CXK_SOC && g.streamed)
-      soc_stream_take_step<<<cnt, kSocStreamBlock, 0, ctx->stream>>>(MakeSocStream(g), sa);
-    else if (g.type == CXK_SOC)
-      soc_take_step<<<cnt, 64, SocTakeLds(g.n), ctx->stream>>>(MakeVec(g), sa);
-    else if (g.type == CXK_QUAD && g.qstream)
-      quad_stream_take_step<<<cnt, kQuadStreamBlock, 0, ctx->stream>>>(MakeQuadStream(g), sa);
-    else if (g.type == CXK_QUAD)
-      quad_take_step<<<cnt, 64, QuadTakeLds(g.n), ctx->stream>>>(MakeQuad(g), sa);
-    else if (g.type == CXK_OCT)
-      oct_take_step<<<cnt, 64, 0, ctx->stream>>>(MakeOct(g), sa);
   }
   EndStepClock(ctx, clk);
   CXK_TRY(hipGetLastError());

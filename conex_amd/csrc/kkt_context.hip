@@ -92,23 +92,23 @@ static FinalizeSwitches ReadFinalizeSwitches() {
   const char* v = getenv("CXK_REFERENCE_QUIRKS");
   sw.quirks_off = v && atoi(v) == 0 && v[0] != '\0';
   if ((v = getenv("CXK_CHAIN_SEGMENTS"))) sw.chain_segments = atoi(v);
-  if ((v = getenv("CXK_SPARSE_LMI"))) sw.sparse_lmi = atoi(v) != 0;
+  if ((v = getenv("CXK_SPARSE_LMI"))) sw.modes.sparse_lmi = atoi(v) != 0;
   if ((v = getenv("CXK_GEMM_MIN_N"))) sw.gemm_min_n = atoi(v);
   v = getenv("CXK_LMI_SCHUR");
   sw.schur_generic = v && !strcmp(v, "generic");
   sw.no_herm_fold = getenv("CXK_NO_HERM_FOLD") != nullptr;
   sw.no_packed_slack = getenv("CXK_NO_PACKED_SLACK") != nullptr;
   if ((v = getenv("CXK_GRAM_SPLITS"))) sw.gram_splits = std::max(1, atoi(v));
-  if ((v = getenv("CXK_STREAMED_CONES"))) sw.streamed_cones = atoi(v) != 0;
+  if ((v = getenv("CXK_STREAMED_CONES"))) sw.modes.streamed_cones = atoi(v) != 0;
   if ((v = getenv("CXK_SOC_STREAM_STAGES"))) sw.soc_stream_stages = atoi(v);
-  if ((v = getenv("CXK_TILED_LINEAR")) && v[0] != '\0') sw.tiled_linear = atoi(v) != 0;
-  if ((v = getenv("CXK_STREAMED_QUADRATIC")) && v[0] != '\0') sw.streamed_quadratic = atoi(v) != 0;
-  if ((v = getenv("CXK_STREAMED_QUADRATIC_MIN_WORK")) && v[0] != '\0') sw.streamed_quadratic_min_work = std::max(0ll, atoll(v));
-  if ((v = getenv("CXK_SPARSE_LINEAR")) && v[0] != '\0') sw.sparse_linear = atoi(v) != 0;
-  if ((v = getenv("CXK_SPARSE_LINEAR_MIN_RATIO")) && v[0] != '\0') sw.sparse_linear_min_ratio = std::max(0.0, atof(v));
-  if ((v = getenv("CXK_TILED_LINEAR_MIN_WORK")) && v[0] != '\0') sw.tiled_linear_min_work = std::max(0ll, atoll(v));
-  if ((v = getenv("CXK_SPARSE_SOC")) && v[0] != '\0') sw.sparse_soc = atoi(v) != 0;
-  if ((v = getenv("CXK_SPARSE_SOC_MIN_RATIO")) && v[0] != '\0') sw.sparse_soc_min_ratio = std::max(0.0, atof(v));
+  if ((v = getenv("CXK_TILED_LINEAR")) && v[0] != '\0') sw.modes.tiled_linear = atoi(v) != 0;
+  if ((v = getenv("CXK_STREAMED_QUADRATIC")) && v[0] != '\0') sw.modes.streamed_quadratic = atoi(v) != 0;
+  if ((v = getenv("CXK_STREAMED_QUADRATIC_MIN_WORK")) && v[0] != '\0') sw.modes.streamed_quadratic_min_work = std::max(0ll, atoll(v));
+  if ((v = getenv("CXK_SPARSE_LINEAR")) && v[0] != '\0') sw.modes.sparse_linear = atoi(v) != 0;
+  if ((v = getenv("CXK_SPARSE_LINEAR_MIN_RATIO")) && v[0] != '\0') sw.modes.sparse_linear_min_ratio = std::max(0.0, atof(v));
+  if ((v = getenv("CXK_TILED_LINEAR_MIN_WORK")) && v[0] != '\0') sw.modes.tiled_linear_min_work = std::max(0ll, atoll(v));
+  if ((v = getenv("CXK_SPARSE_SOC")) && v[0] != '\0') sw.modes.sparse_soc = atoi(v) != 0;
+  if ((v = getenv("CXK_SPARSE_SOC_MIN_RATIO")) && v[0] != '\0') sw.modes.sparse_soc_min_ratio = std::max(0.0, atof(v));
   return sw;
 }
 
@@ -563,18 +563,21 @@ int cxk_set_reference_identity(cxk_context* ctx, int on) {
   return CXK_SUCCESS;
 }
 
+// The owned constraints cxk_finalize put on `route` (what the cxk_count_* of the routes report); -1 before it.
+static int CountOnRoute(const cxk_context* ctx, ConeRoute route) {
+  if (!ctx || !ctx->finalized) return -1;
+  int k = 0;
+  for (size_t i = 0; i < ctx->cons.size(); i++) k += ctx->owned[i] && ctx->cons[i].route == route;
+  return k;
+}
+
 int cxk_set_streamed_cones(cxk_context* ctx, int on) {
   if (!ctx) return CXK_FAILURE;
   CXK_DEMAND(!ctx->finalized, "cxk_set_streamed_cones: the context is finalized (the choice is made by cxk_finalize)");
   ctx->streamed_cones = on != 0;
   return CXK_SUCCESS;
 }
-int cxk_count_streamed_cones(const cxk_context* ctx) {
-  if (!ctx || !ctx->finalized) return -1;
-  int k = 0;
-  for (size_t i = 0; i < ctx->cons.size(); i++) k += ctx->owned[i] && ctx->cons[i].streamed;
-  return k;
-}
+int cxk_count_streamed_cones(const cxk_context* ctx) { return CountOnRoute(ctx, ConeRoute::kSocStreamed); }
 
 int cxk_set_tiled_linear(cxk_context* ctx, int mode) {
   if (!ctx) return CXK_FAILURE;
@@ -583,12 +586,7 @@ int cxk_set_tiled_linear(cxk_context* ctx, int mode) {
   ctx->tiled_linear = mode;
   return CXK_SUCCESS;
 }
-int cxk_count_tiled_linear(const cxk_context* ctx) {
-  if (!ctx || !ctx->finalized) return -1;
-  int k = 0;
-  for (size_t i = 0; i < ctx->cons.size(); i++) k += ctx->owned[i] && ctx->cons[i].tiled;
-  return k;
-}
+int cxk_count_tiled_linear(const cxk_context* ctx) { return CountOnRoute(ctx, ConeRoute::kLinearTiled); }
 
 int cxk_set_sparse_linear(cxk_context* ctx, int mode) {
   if (!ctx) return CXK_FAILURE;
@@ -597,12 +595,7 @@ int cxk_set_sparse_linear(cxk_context* ctx, int mode) {
   ctx->sparse_linear = mode;
   return CXK_SUCCESS;
 }
-int cxk_count_sparse_linear(const cxk_context* ctx) {
-  if (!ctx || !ctx->finalized) return -1;
-  int k = 0;
-  for (size_t i = 0; i < ctx->cons.size(); i++) k += ctx->owned[i] && ctx->cons[i].lsparse;
-  return k;
-}
+int cxk_count_sparse_linear(const cxk_context* ctx) { return CountOnRoute(ctx, ConeRoute::kLinearSparse); }
 
 int cxk_set_sparse_soc(cxk_context* ctx, int mode) {
   if (!ctx) return CXK_FAILURE;
@@ -611,12 +604,7 @@ int cxk_set_sparse_soc(cxk_context* ctx, int mode) {
   ctx->sparse_soc = mode;
   return CXK_SUCCESS;
 }
-int cxk_count_sparse_soc(const cxk_context* ctx) {
-  if (!ctx || !ctx->finalized) return -1;
-  int k = 0;
-  for (size_t i = 0; i < ctx->cons.size(); i++) k += ctx->owned[i] && ctx->cons[i].ssparse;
-  return k;
-}
+int cxk_count_sparse_soc(const cxk_context* ctx) { return CountOnRoute(ctx, ConeRoute::kSocSparse); }
 
 double cxk_sparse_soc_setup_ms(const cxk_context* ctx) { return ctx && ctx->finalized ? ctx->sparse_soc_setup_ms : 0.0; }
 
@@ -627,12 +615,7 @@ int cxk_set_streamed_quadratic(cxk_context* ctx, int mode) {
   ctx->streamed_quadratic = mode;
   return CXK_SUCCESS;
 }
-int cxk_count_streamed_quadratic(const cxk_context* ctx) {
-  if (!ctx || !ctx->finalized) return -1;
-  int k = 0;
-  for (size_t i = 0; i < ctx->cons.size(); i++) k += ctx->owned[i] && ctx->cons[i].qstream;
-  return k;
-}
+int cxk_count_streamed_quadratic(const cxk_context* ctx) { return CountOnRoute(ctx, ConeRoute::kQuadStreamed); }
 
 int cxk_finalize(cxk_context* ctx) {
   if (!ctx) return CXK_FAILURE;
@@ -1341,12 +1324,7 @@ int cxk_dense_top_columns(const cxk_context* ctx) {
   return ctx->top_dense.on ? ctx->top_dense.args.T : 0;
 }
 
-int cxk_count_sparse_lmi(const cxk_context* ctx) {
-  if (!ctx || !ctx->finalized) return -1;
-  int k = 0;
-  for (size_t i = 0; i < ctx->cons.size(); i++) k += ctx->cons[i].type == CXK_LMI && ctx->owned[i] && ctx->cons[i].sparse;
-  return k;
-}
+int cxk_count_sparse_lmi(const cxk_context* ctx) { return CountOnRoute(ctx, ConeRoute::kLmiSparse); }
 
 int cxk_count_factored_lmi(const cxk_context* ctx) {
   if (!ctx || !ctx->finalized) return -1;
@@ -1399,8 +1377,8 @@ int cxk_count_lmi_kernel(const cxk_context* ctx, int which) {
   if (!ctx || !ctx->device_ready) return -1;
   int k = 0;
   for (const Group& g : ctx->groups) {
-    if (g.type != CXK_LMI || g.factored) continue;
-    const int kind = g.sparse ? 4 : g.schur_gemm ? 3 : g.mfma ? 2 : 0;
+    if (g.type != CXK_LMI || g.route == ConeRoute::kLmiFactored) continue;
+    const int kind = g.route == ConeRoute::kLmiSparse ? 4 : g.assembly == LmiAssembly::kGemm ? 3 : g.assembly == LmiAssembly::kMfma ? 2 : 0;
     if (kind == which) k += (int)g.ids.size();
   }
   return k;

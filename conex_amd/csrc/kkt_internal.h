@@ -1,6 +1,8 @@
 // Shared by the translation units of the cxk_* path: the context, its host-side types and the
 // functions that cross between them.  kkt_plans.hip builds the symbolic plans (tree structure,
 // partition, index tables: host code only); the launches and the C-ABI are the units kkt_launch.h lists.
+// Which kernels a constraint runs on is ONE field of its record and of its group (ConeRoute, chosen by the pure
+// function of cone_route.h); what is a property of the data (symmetric, csr_only, factored, literal, has_q) stays a flag.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -22,6 +24,7 @@
 #include <vector>
 
 #include "../../include/conex_kkt_hip.h"
+#include "cone_route.h"   // ConeRoute, LmiAssembly, kLdsLimit and the dynamic-LDS formulas: plain C++
 #include "kkt_records.h"  // record and argument types, FactorPlan, TopDenseArgs: no device code
 #include "lmi_types.h"
 #include "symbolic.h"
@@ -39,20 +42,15 @@ struct ConstraintRec {
   std::vector<double> A, C;
   std::vector<double> Q;  // CXK_QUAD: n x n inner-product matrix, empty = identity
   int group = -1, member = -1;
-  bool sparse = false;  // LMI evaluated from its nonzeros (kernels_lmi_sparse.hip.h)
-  bool streamed = false;  // second-order cone beyond LDS, held in HBM (kernels_soc_stream.hip.h)
+  ConeRoute route = ConeRoute::kStatic;  // the set of kernels it runs on, chosen by cxk_finalize (cone_route.h, Choose)
   // every A_i and C equals its transpose.  The fast kernels use tr(W A_i W A_j) = tr(P_i P_j),
   // P = A W, which needs that; anything else takes the literal kernels (dense_lmi_constraint.cc:72-88)
   bool symmetric = true;
-  bool tiled = false;  // linear block on the tiled route (kernels_linear_tiled.hip.h)
-  bool qstream = false;  // quadratic cone held in HBM (kernels_quad_stream.hip.h); `streamed` stays the second-order cone's
   // linear block: its nonzeros by rows, columns ascending (cxk_add_linear_csr gives them and leaves A empty: such a
   // block can only take the sparse route; GroupConstraints reads them off the A of a dense-added block)
-  bool lsparse = false;   // linear block on the sparse route (kernels_linear_sparse.hip.h)
   bool csr_only = false;  // added by cxk_add_linear_csr / cxk_add_soc_csr: no dense A
   // second-order cone on the sparse route (kernels_soc_sparse.hip.h): the same sp_* vectors hold the nonzeros of its
   // (n + 1) x m matrix, given by cxk_add_soc_csr (csr_only) or read off the A of a cone added by cxk_add_soc
-  bool ssparse = false;
   std::vector<int> sp_rowptr, sp_col;
   std::vector<double> sp_val;
   // CXK_LMI given by factors (cxk_add_lmi_factored, kernels_lmi_factored.hip.h): A_i = sum sigma_k f_k f_k', k in
@@ -112,58 +110,52 @@ struct Group {
   DevBuf<double> Apk;             // CXK_LMI: packed lower triangles of the A_i (LmiGroup::Apk), may be empty
   DevBuf<double> qQ, qGram, qS;   // CXK_QUAD: Q, A1' Q A1, the state kept between PrepareStep and TakeStep
   int herm_d = 0;
-  bool mfma = false;     // lmi_schur_mfma (lmi_fused_mfma.hip)
+  // the set of kernels every member runs on, and for CXK_LMI how the Schur complement is assembled: the batched MFMA
+  // GEMM pipeline always when `large`, and for LDS-resident shapes from order 9 up without a register-kernel instance,
+  // where it measured 1.5-3.3x faster than the LDS kernel (cone_route.h: Choose, ChooseLmiAssembly)
+  ConeRoute route = ConeRoute::kStatic;
+  LmiAssembly assembly = LmiAssembly::kGeneric;
   // lmi_schur_mfma launches of this group so far: an odd one walks each workgroup's constraints backwards, so
   // that it starts on the operands its predecessor ended with (cxk_context::lmi_order_forward turns that off)
   unsigned schur_launches = 0;
   bool literal = false;  // non-symmetric data: literal kernels only
   // orders beyond the LDS-resident kernels: HBM-resident matrices + MFMA GEMM pipeline
   bool large = false;
-  // assembly through the batched MFMA GEMM pipeline (always when `large`; also for LDS-resident
-  // shapes from order 9 up without a register-kernel instance, where it measured 1.5-3.3x faster than the LDS kernel)
-  bool schur_gemm = false;
   DevBuf<double> ws_main, ws_gf, ws_part;
   DevBuf<int> ws_piv;
   int splits = 1;
-  // sparse LMI groups: nonzeros matrix-major and position-major instead of the dense A
-  bool sparse = false;
+  // sparse LMI groups (kLmiSparse): nonzeros matrix-major and position-major instead of the dense A
   int sp_lpp = 1;                  // lanes sharing one (i, j) pair sum
   int sp_chunks = 1, sp_emax = 0;  // sp_emax: most nonzeros in one constraint
   bool sp_cdense = false;          // dense affine term: X = W C W instead of pair sums with C
   bool sp_small = false;           // W (and X) of a constraint fit in LDS
   DevBuf<int> sp_eptr, sp_erc, sp_pptr, sp_pvar, sp_pairs;
   DevBuf<double> sp_eval, sp_pval;
-  // second-order cones beyond LDS (cxk_set_streamed_cones): the kernels of kernels_soc_stream.hip.h; WA in ws_main,
+  // second-order cones beyond LDS (kSocStreamed, cxk_set_streamed_cones): the kernels of kernels_soc_stream.hip.h; WA in ws_main,
   // the Gram product's output in ws_gf and its split partials in ws_part (`splits` of them)
-  bool streamed = false;
   DevBuf<double> st_vec;   // s, Q(s) c, the slack: three vectors per cone
   DevBuf<double> st_det;   // det(s) per cone
   int st_stages = 0;       // CXK_SOC_STREAM_STAGES: 1 / 2 = the assembly stops after the vectors / the apply stage (timing runs)
-  // linear blocks on the tiled route (cxk_set_tiled_linear): the kernels of kernels_linear_tiled.hip.h; diag(w) A in
+  // linear blocks on the tiled route (kLinearTiled, cxk_set_tiled_linear): the kernels of kernels_linear_tiled.hip.h; diag(w) A in
   // ws_main, the Gram product's output in ws_gf, its split partials in ws_part, four doubles per row tile in lt_part
-  bool tiled = false;
   DevBuf<double> lt_part;
-  // quadratic cones held in HBM (cxk_set_streamed_quadratic): the kernels of kernels_quad_stream.hip.h; the split
+  // quadratic cones held in HBM (kQuadStreamed, cxk_set_streamed_quadratic): the kernels of kernels_quad_stream.hip.h; the split
   // partials of the products with Q in ws_part (`splits` column splits), every vector and scalar of the work space
   // in st_vec (MakeQuadStream lays it out)
-  bool qstream = false;
-  // linear blocks on the sparse route (cxk_set_sparse_linear): the kernels of kernels_linear_sparse.hip.h; every
+  // linear blocks on the sparse route (kLinearSparse, cxk_set_sparse_linear): the kernels of kernels_linear_sparse.hip.h; every
   // member's nonzeros by rows (ls_col, ls_val) and by columns (ls_crow, ls_cval) from ls_eptr[member] on, the
   // pointers of its rows and columns relative to that; four doubles per row tile in lt_part.  No dense A.
-  bool lsparse = false;
   DevBuf<int> ls_eptr, ls_rowptr, ls_col, ls_colptr, ls_crow;
   DevBuf<double> ls_val, ls_cval;
-  // second-order cones on the sparse route (cxk_set_sparse_soc): the kernels of kernels_soc_sparse.hip.h; the nonzeros
+  // second-order cones on the sparse route (kSocSparse, cxk_set_sparse_soc): the kernels of kernels_soc_sparse.hip.h; the nonzeros
   // in the ls_* arrays as above (rows = n + 1); the constants H = A' J A, h = A' J c, z = c' J c of every member in
   // ss_const (formed on the device at finalize), s, ms, u = A' w and (det w, w . c) in st_vec (MakeSocSparse lays
   // both out).  No dense A, no WA, no GEMM output.
-  bool ssparse = false;
   DevBuf<double> ss_const;
-  // LMIs given by factors (cxk_add_lmi_factored): the kernels of kernels_lmi_factored.hip.h in front of the large-order
+  // LMIs given by factors (kLmiFactored, cxk_add_lmi_factored): the kernels of kernels_lmi_factored.hip.h in front of the large-order
   // route's (`large` is set: HBM-resident W, ws_main's step temporaries, ws_piv).  Every member's F, sigma, column
   // pointers and column -> variable map; Z, Y, Fs and P in f_ws (MakeLmiFactored lays it out); the slices of the two
   // scalars in ws_part.  No dense A.
-  bool factored = false;
   bool f_rank_one = false;
   int f_R = 0;
   DevBuf<double> f_F, f_sigma, f_ws;
@@ -473,7 +465,6 @@ struct cxk_context {
 
 namespace cxk_host {
 
-constexpr size_t kLdsLimit = 160 * 1024 - 512;
 constexpr int kChainMaxLevels = 1 << 30;  // no limit: the kernel keeps the last kChainRing records in LDS and re-reads the rest
 constexpr int kSplitTopLevels = 8;  // tops of at most this many levels may be swept level by level
 

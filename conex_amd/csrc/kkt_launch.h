@@ -1,6 +1,7 @@
 // What the translation units of the cxk_* path call in one another.  Every kernel is compiled in
 // exactly one unit; a unit that needs a kernel it does not own goes through a host function of the owner:
-//   kkt_cone_launch.hip  the per-cone stages (Schur, PrepareStep, eigenvalue query, TakeStep), the mailbox
+//   kkt_cone_launch.hip  the per-cone stages (Schur, PrepareStep, eigenvalue query, TakeStep), each an exhaustive
+//                        switch over Group::route (cone_route.h); the per-group stages of cxk_finalize; the mailbox
 //   kkt_tree_launch.hip  assembly gather, right-hand sides, the elimination-tree sweeps, the exchange kernels
 //   kkt_shard.hip        sharded sweeps, collectives, communicator and exchange entry points
 //   kkt_qr.hip           the host QR mode
@@ -54,79 +55,23 @@ CXK_LOCAL inline hipError_t RaiseDynamicLds(std::initializer_list<const void*> k
   return hipSuccess;
 }
 
-// The widest linear block the LDS route can run: linear_line_search is launched with 16 m bytes of dynamic LDS
-// and has the default limit of 64 KB (linear_prepare's 8 m bytes reach it at 8192).
-constexpr int kLinearLdsMaxVars = 4096;
-// Automatic mode sends a linear block of rows x m to the tiled route from rows m^2 >= this on.  Measured
-// (tools/linear_tiled_speed.py against the build before the tiled route): twice the smallest
-// rows m^2 among the measured shapes from which assembly, PrepareStep and the eigenvalue query are each faster on
-// the tiled route at that shape and at every larger one, 2000 x 64 (at 256 x 32 the assembly is five times faster
-// but the two-launch PrepareStep and query cost 2 us more); twice, because the numbers are one box's on one day.
-constexpr long long kTiledLinearMinWork = 2ll * 2000 * 64 * 64;  // 16 384 000
-
-// Automatic mode (cxk_set_sparse_linear(ctx, -1)) sends a linear block to the sparse route when
-// R sum_r nnz_r^2 <= rows m^2: the sparse assembly forms about sum_r nnz_r^2 products one fma at a time, the dense
-// routes rows m^2 on the matrix pipe.  Measured (tools/linear_sparse_speed.py against the build before the sparse
-// route on its own choice): R is twice the smallest rows m^2 / sum_r nnz_r^2 among the measured
-// shapes at which assembly, PrepareStep and the eigenvalue query are each faster on the sparse route, 3.9 at the
-// half-full 2000 x 64; twice, because the numbers are one box's on one day.  A fully dense block (ratio 1) never moves.
-// CXK_SPARSE_LINEAR_MIN_RATIO moves R for comparison runs.  Two more conditions, both from shapes that lost:
-//  - a column's rows are one wavefront's dependent chain, 0.33 us per row (100 000 x 50 with one full column: 32.6 ms
-//    against 0.38 ms): no column longer than kSparseLinearMaxColumn, twice the longest measured to win (about 1050);
-//  - a thousand 20 x 10 blocks with 3 nonzeros per row are 20 % slower at every stage than on the LDS route's one
-//    launch per stage: nothing below the rows m^2 of the smallest measured shape that won, 2000 x 64, moves.
-constexpr double kSparseLinearMinRatio = 7.8;
-constexpr int kSparseLinearMaxColumn = 2048;
-constexpr long long kSparseLinearMinWork = 2000ll * 64 * 64;  // 8 192 000
-inline bool LinearSparsePays(double rows, double m, double sum_nnz_sq, int longest_column, double ratio) {
-  return ratio * sum_nnz_sq <= rows * m * m && rows * m * m >= (double)kSparseLinearMinWork &&
-         longest_column <= kSparseLinearMaxColumn;
-}
-
-// Automatic mode (cxk_set_sparse_soc(ctx, -1)) sends a second-order cone of dimension len = n + 1 over m variables to
-// the sparse route when it can run nowhere else (added by cxk_add_soc_csr, or len m beyond the int range), or when
-// R nnz <= len m and len m^2 >= kSparseSocMinWork: the sparse assembly reads the nnz nonzeros and moves the m x m
-// square twice, the dense routes stream len m entries (and the streamed one multiplies len m^2).  Measured
-// (tools/soc_sparse_speed.py --sweep against the streamed route): each constant is twice the smallest
-// value among the swept shapes at which assembly + query + PrepareStep + TakeStep are faster on the sparse route;
-// twice, because the numbers are one box's on one day.  The smallest winning len m / nnz is 2.02 (2048 x 64 half full:
-// 87.8 us against 129.7 us; the assembly gains 4.3x, the one-thread-per-row slack loses 0.63x); a fully dense 401 x 61
-// loses (87.6 us against 82.7 us) and never moves.  The smallest swept shape, 401 x 61 (len m^2 = 1 492 121), wins at
-// 3 nonzeros per row (51.4 us against 79.7 us); nothing smaller was measured, so nothing smaller moves.
-// CXK_SPARSE_SOC_MIN_RATIO moves R for comparison runs.  No default anywhere asks for this mode.
-constexpr double kSparseSocMinRatio = 4.04;
-constexpr long long kSparseSocMinWork = 2ll * 401 * 61 * 61;  // 2 984 242
-inline bool SocSparsePays(double len, double m, double nnz, double ratio) {
-  return ratio * nnz <= len * m && len * m * m >= (double)kSparseSocMinWork;
-}
-
-// Automatic mode (cxk_set_streamed_quadratic(ctx, -1)) sends a quadratic cone to the streamed route from this many
-// doubles streamed per pass, (Q ? n n : 0) + (n + 1) m, on.  Measured (tools/quad_stream_speed.py):
-// the smallest shape of the sweep, n = 32 with Q over m = 8 (32 * 32 + 33 * 8), where assembly + PrepareStep +
-// TakeStep already take 48 us on the streamed route against 333 us on the LDS route; every larger swept shape gains
-// more.  Nothing smaller was measured, so nothing smaller moves (the cones of a handful of doubles stay where they are).
-constexpr long long kQuadStreamMinWork = 32 * 32 + 33 * 8;  // 1288
+// (The thresholds of the automatic modes -- kLinearLdsMaxVars, kTiledLinearMinWork, kSparseLinear*, kSparseSoc*,
+// kQuadStreamMinWork -- and the rules LinearSparsePays / SocSparsePays are cone_route.h's, with the choice they feed.)
 
 // The environment switches of cxk_finalize, read once per call (FinalizeImpl).
 struct FinalizeSwitches {
+  // the modes of the routes as the environment has them (CXK_SPARSE_LMI, CXK_STREAMED_CONES, CXK_TILED_LINEAR,
+  // CXK_STREAMED_QUADRATIC, CXK_SPARSE_LINEAR, CXK_SPARSE_SOC and their _MIN_WORK / _MIN_RATIO: cone_route.h); what the
+  // context was told by a cxk_set_* goes in front (GroupConstraints)
+  RouteModes modes;
   bool quirks_off = false;      // CXK_REFERENCE_QUIRKS=0: the two corrections instead of the reference as written
   int chain_segments = -1;      // CXK_CHAIN_SEGMENTS: 0 keeps the reference's order, P asks for P segments
-  int sparse_lmi = -1;          // CXK_SPARSE_LMI=0 / 1 forces sparse evaluation never / always (tests)
   int gemm_min_n = 9;           // CXK_GEMM_MIN_N: smallest LDS-resident order on the batched-GEMM assembly
   bool schur_generic = false;   // CXK_LMI_SCHUR=generic: the LDS-resident literal kernel (comparison runs, tests)
   bool no_herm_fold = false;    // CXK_NO_HERM_FOLD
   bool no_packed_slack = false; // CXK_NO_PACKED_SLACK
   int gram_splits = 0;          // CXK_GRAM_SPLITS: K splits of the GEMM assembly (0: chosen by shape)
-  bool streamed_cones = false;  // CXK_STREAMED_CONES=1: second-order cones beyond LDS run from HBM (cxk_set_streamed_cones)
   int soc_stream_stages = 0;    // CXK_SOC_STREAM_STAGES=1 / 2: their assembly stops after that stage (timing runs: wrong results)
-  int tiled_linear = -1;        // CXK_TILED_LINEAR=0 / 1: linear blocks never / always on the tiled route (cxk_set_tiled_linear)
-  long long tiled_linear_min_work = kTiledLinearMinWork;  // CXK_TILED_LINEAR_MIN_WORK (comparison runs)
-  int streamed_quadratic = 0;   // CXK_STREAMED_QUADRATIC=0 / 1: quadratic cones never / always held in HBM (cxk_set_streamed_quadratic)
-  long long streamed_quadratic_min_work = kQuadStreamMinWork;  // CXK_STREAMED_QUADRATIC_MIN_WORK (comparison runs)
-  int sparse_linear = 0;        // CXK_SPARSE_LINEAR=0 / 1: linear blocks never / always on the sparse route (cxk_set_sparse_linear)
-  double sparse_linear_min_ratio = kSparseLinearMinRatio;  // CXK_SPARSE_LINEAR_MIN_RATIO (comparison runs)
-  int sparse_soc = 0;           // CXK_SPARSE_SOC=0 / 1: second-order cones never / always on the sparse route (cxk_set_sparse_soc)
-  double sparse_soc_min_ratio = kSparseSocMinRatio;  // CXK_SPARSE_SOC_MIN_RATIO (comparison runs)
 };
 
 // ---- kkt_context.hip

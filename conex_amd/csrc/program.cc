@@ -1051,6 +1051,8 @@ CONEX_STATUS CONEX_UpdateLinearOperator(void* x, int constraint, double value, i
     case kQuadCost:
     case kEquality:  // constraint.h:13-18 default: not supported
       CONEX_DEMAND(false, "Constraint does not support updates of linear operator.");
+    case kQuadCone:  // (as it has always been here: accepted, nothing updated)
+      break;
   }
   p->dirty = true;
   return CONEX_SUCCESS;
@@ -1101,6 +1103,8 @@ CONEX_STATUS CONEX_UpdateAffineTerm(void* x, int constraint, double value, int r
       break;
     case kEquality:  // constraint.h:20-24 default: not supported
       CONEX_DEMAND(false, "Constraint does not support updates of affine term.");
+    case kQuadCone:  // (as it has always been here: accepted, nothing updated)
+      break;
   }
   p->dirty = true;
   return CONEX_SUCCESS;

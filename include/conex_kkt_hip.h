@@ -162,7 +162,7 @@ int cxk_count_tiled_linear(const cxk_context* ctx);
  * route's bit for bit.  G comes out exactly symmetric.  Every output, getter and setter is that of any linear block.
  * cxk_set_sparse_linear, before cxk_finalize: mode 1 every linear block takes the sparse route; 0 none does; -1 a
  * block does when kSparseLinearMinRatio x sum_r nnz_r^2 <= rows x variables^2, rows x variables^2 is at least
- * kSparseLinearMinWork and no column has more than kSparseLinearMaxColumn rows (kkt_launch.h: 7.8, 8 192 000, 2048,
+ * kSparseLinearMinWork and no column has more than kSparseLinearMaxColumn rows (cone_route.h: 7.8, 8 192 000, 2048,
  * measured; CXK_SPARSE_LINEAR_MIN_RATIO moves the ratio for comparison runs) and neither cxk_set_tiled_linear
  * nor CXK_TILED_LINEAR made an explicit choice, which is a request for the dense kernels.  Without a call: the
  * environment's CXK_SPARSE_LINEAR = 0 | 1, else 0.  A sparse block may have more than 4096 variables whatever the
@@ -195,7 +195,7 @@ int cxk_add_linear_csr(cxk_context* ctx, int rows, int m, const int* rowptr /* r
  * cxk_set_sparse_soc, before cxk_finalize: mode 1 every second-order cone takes the sparse route; 0 none does; -1 a
  * cone does when it can run nowhere else (added by cxk_add_soc_csr, or (n + 1) x variables beyond the int range), or
  * when kSparseSocMinRatio x nnz <= (n + 1) x variables and (n + 1) x variables^2 is at least kSparseSocMinWork
- * (kkt_launch.h, measured; CXK_SPARSE_SOC_MIN_RATIO moves the ratio for comparison runs).  Without a call: the
+ * (cone_route.h, measured; CXK_SPARSE_SOC_MIN_RATIO moves the ratio for comparison runs).  Without a call: the
  * environment's CXK_SPARSE_SOC = 0 | 1, else 0.  A sparse cone needs neither cxk_set_streamed_cones nor LDS room.
  * Refused on the sparse route at cxk_finalize, by name: variables^2 beyond the int range; a group of equal-shaped
  * cones with more than 2^31 nonzeros, column chunks, row tiles or tiles of the Schur block.

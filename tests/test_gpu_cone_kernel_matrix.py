@@ -32,7 +32,7 @@ C_AFFINE = 32     # the linear cone's affine update
 C_TAKE = 256      # W after the step, from the device's own d
 POINTS = ("well", 1e6, 1e10)
 C_WEIGHT = 1.0
-K_LDS_LIMIT = 160 * 1024 - 512   # kLdsLimit (kkt_internal.h); 8 * 5104 * 4 = 8 * 88 * 58 * 4 = 163 328
+K_LDS_LIMIT = 160 * 1024 - 512   # kLdsLimit (cone_route.h); 8 * 5104 * 4 = 8 * 88 * 58 * 4 = 163 328
 
 # (id, kind, K, n, m, extra): soc / quad have dimension len = n + 1, lin has n rows, oct has order n;
 # extra: quad "Q" / None, static "eq" (the equality path: a non-zero constant AQc) / None

@@ -7,7 +7,7 @@ constraint_schur -> eigenvalue query -> PrepareStep -> TakeStep on a KktContext 
 set_streamed_quadratic(1).  test_quad_streamed_reference.py runs the same rows on the float64 oracle, which shows
 that correct float64 code meets the bounds at these sizes too.
 
-test_rows_sit_on_their_edges recomputes every edge with the launch site's arithmetic (GroupConstraints' three
+test_rows_sit_on_their_edges recomputes every edge with the launch site's arithmetic (cone_route.h's three
 demands, QuadStreamSplits, the row tile and the x chunk of quad_stream_qmv, the 256-entry blocks of the Schur
 block), so that a row cannot leave its edge unnoticed.
 """
@@ -59,7 +59,7 @@ class AutomaticQuad(KktContext):
 
 
 def lds_route(n, m):
-    """GroupConstraints' three demands on a quadratic cone, restated: True = the LDS kernels can hold it."""
+    """cone_route.h's three demands on a quadratic cone, restated: True = the LDS kernels can hold it."""
     return (8 * (m + 4 * (n + 1)) <= km.K_LDS_LIMIT and 8 * (2 * n + m + 4) <= km.K_LDS_LIMIT
             and 8 * 3 * (n + 1) <= km.K_LDS_LIMIT)
 

@@ -8,7 +8,7 @@ constructor calls set_streamed_cones().  test_soc_streamed_reference.py runs the
 float64 oracle, which shows that correct float64 code meets the bounds at these lengths too.
 
 Each row is the smallest shape at which its mechanism first engages; test_rows_sit_on_their_edges
-recomputes every edge with the launch site's arithmetic (GroupConstraints' three demands,
+recomputes every edge with the launch site's arithmetic (cone_route.h's three demands,
 SocStreamSplits, the row tile of soc_stream_slack), so that a row cannot leave its edge unnoticed.
 """
 import numpy as np
@@ -47,7 +47,7 @@ class StreamedContext(KktContext):
 
 
 def staged(n, m):
-    """GroupConstraints' three demands on a second-order cone, restated: True = it keeps the LDS kernels."""
+    """cone_route.h's three demands on a second-order cone, restated: True = it keeps the LDS kernels."""
     length = n + 1
     return (8 * length * (m + 2) <= km.K_LDS_LIMIT and 8 * 4 * length <= km.K_LDS_LIMIT
             and 8 * (m + 3 * length) <= km.K_LDS_LIMIT)
