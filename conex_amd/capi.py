@@ -71,6 +71,8 @@ def api():
                                                   C.POINTER(C.c_long), ci]),
         "CONEX_HIP_AddFactoredLMIConstraint": (ci, [vp, ci, c_double_p, ci, c_double_p, ip, ci, c_double_p,
                                                     C.POINTER(C.c_long)]),
+        "CONEX_HIP_AddFactoredHermitianConstraint": (ci, [vp, ci, ci, c_double_p, ci, c_double_p, ip, ci, c_double_p,
+                                                          C.POINTER(C.c_long)]),
         "CONEX_HIP_AddQuadraticCostEpigraph": (ci, [vp, c_double_p, ci, C.POINTER(C.c_long), C.c_long]),
         "CONEX_HIP_SetStreamedCones": (ci, [vp, ci]),
         "CONEX_HIP_SetTiledLinear": (ci, [vp, ci]),

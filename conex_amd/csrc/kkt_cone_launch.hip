@@ -452,10 +452,17 @@ static int AllocGemmAssembly(cxk_context* ctx, Group& g, const FinalizeSwitches&
   return CXK_SUCCESS;
 }
 
+int LmiLargeSpectrumMaxOrder() {
+  int n = 1;
+  while (LmiLargeSpectrumLds(n + 1) <= kLdsLimit) n++;
+  return n;
+}
+
 LmiFactoredGroup MakeLmiFactored(Group& g) {
   LmiFactoredGroup f{};
   const size_t cnt = g.ids.size(), nr = (size_t)g.n * g.f_R;
   f.R = g.f_R;
+  f.d = g.herm_d > 1 ? g.herm_d : 1;
   f.rank_one = g.f_rank_one;
   f.F = g.f_F.p;
   f.sigma = g.f_sigma.p;
@@ -464,24 +471,26 @@ LmiFactoredGroup MakeLmiFactored(Group& g) {
   f.Z = g.f_ws.p;  // (the layout UploadLmiFactored sizes: LmiFactoredWsDoubles)
   f.Y = f.Z + cnt * nr;
   f.Fs = f.Y + cnt * nr;
-  f.P = f.Fs + cnt * nr;
+  f.P = f.Fs + cnt * nr * f.d;
   f.part = g.ws_part.p;
   f.npart = kSparseCParts;
   return f;
 }
-size_t LmiFactoredWsDoubles(size_t cnt, size_t n, size_t R) { return cnt * (3 * n * R + R * R); }
+// (d: the column blocks of a Hermitian member's L(F); Z and Y keep R columns, Fs and P have d R)
+size_t LmiFactoredWsDoubles(size_t cnt, size_t n, size_t R, size_t d) { return cnt * ((2 + d) * n * R + d * R * R); }
 
 // A group of LMIs given by factors: every member's F, sigma, column pointers and column -> variable map, the work
 // space of the factored kernels and of the large-order step kernels behind them.
 static int UploadLmiFactored(cxk_context* ctx, Group& g) {
   const size_t cnt = g.ids.size(), n = (size_t)g.n, R = (size_t)g.f_R, m = (size_t)g.m;
+  const size_t d = g.herm_d > 1 ? (size_t)g.herm_d : 1;  // (a Hermitian member's f_F is L(F): n x dR)
   CXK_DEMAND(cnt <= 65535, "a group of more than 65535 equal-shaped factored LMIs is not supported");
-  std::vector<double> hF(cnt * n * R), hs(cnt * R);
+  std::vector<double> hF(cnt * n * R * d), hs(cnt * R);
   std::vector<int> hp(cnt * (m + 1)), hv(cnt * R);
   g.f_rank_one = true;
   for (size_t k = 0; k < cnt; k++) {
     const ConstraintRec& c = ctx->cons[g.ids[k]];
-    std::copy(c.f_F.begin(), c.f_F.end(), hF.begin() + k * n * R);
+    std::copy(c.f_F.begin(), c.f_F.end(), hF.begin() + k * n * R * d);
     std::copy(c.f_sigma.begin(), c.f_sigma.end(), hs.begin() + k * R);
     std::copy(c.f_ptr.begin(), c.f_ptr.end(), hp.begin() + k * (m + 1));
     for (size_t i = 0; i < m; i++) {
@@ -493,7 +502,7 @@ static int UploadLmiFactored(cxk_context* ctx, Group& g) {
   CXK_TRY(g.f_sigma.upload(hs));
   CXK_TRY(g.f_ptr.upload(hp));
   CXK_TRY(g.f_var.upload(hv));
-  CXK_TRY(g.f_ws.alloc(LmiFactoredWsDoubles(cnt, n, R)));
+  CXK_TRY(g.f_ws.alloc(LmiFactoredWsDoubles(cnt, n, R, d)));
   CXK_TRY(g.ws_main.alloc(cnt * 8 * n * n));  // step temporaries; C W and W C W during assembly
   CXK_TRY(g.ws_part.alloc(cnt * 2 * kSparseCParts));
   CXK_TRY(g.ws_piv.alloc(cnt * n));

@@ -210,7 +210,22 @@ static int AllocateSystemBuffers(cxk_context* ctx) {
 static int FinalizeImpl(cxk_context* ctx) {
   const FinalizeSwitches sw = ReadFinalizeSwitches();
   for (const ConstraintRec& c : ctx->cons)
-    if (c.factored) {  // the limit of LmiLargeLuSolve, and the int indexing of kernels_lmi_factored.hip.h
+    if (c.factored && c.herm_d) {
+      // Hermitian factors (order c.n = d x the hyper-complex order, f_F = L(F) of d R columns): the Taylor TakeStep
+      // has no LU; what bounds the order is the one-workgroup Lanczos of lmi_large_spectrum, then the int indexing
+      const int64_t N = c.n, R = c.f_R, d = c.herm_d;
+      if (c.n > LmiLargeSpectrumMaxOrder()) {
+        ctx->err = "a factored Hermitian constraint whose real representation has an order above " +
+                   std::to_string(LmiLargeSpectrumMaxOrder()) + " is not supported (the vectors of its Lanczos run exceed the " +
+                   std::to_string(kLdsLimit) + " B of LDS)";
+        fprintf(stderr, "%s line %d: %s\n", __FILE__, __LINE__, ctx->err.c_str());
+        return CXK_FAILURE;
+      }
+      CXK_DEMAND(N * R <= INT_MAX, "a factored Hermitian constraint whose N x R entries (N = d n) exceed the int range is not supported");
+      CXK_DEMAND(d * R * R <= INT_MAX, "a factored Hermitian constraint whose d x R x R entries exceed the int range is not supported");
+      CXK_DEMAND(N * d * R <= INT_MAX, "a factored Hermitian constraint whose N x dR entries (N = d n) exceed the int range is not supported");
+      CXK_DEMAND((int64_t)c.m * c.m <= INT_MAX, "a factored Hermitian constraint whose m x m entries exceed the int range is not supported");
+    } else if (c.factored) {  // the limit of LmiLargeLuSolve, and the int indexing of kernels_lmi_factored.hip.h
       CXK_DEMAND(c.n <= 1024, "a factored LMI of order above 1024 is not supported (one panel row per thread in the Pade LU)");
       CXK_DEMAND((int64_t)c.n * c.f_R <= INT_MAX && (int64_t)c.f_R * c.f_R <= INT_MAX && (int64_t)c.m * c.m <= INT_MAX,
                  "a factored LMI whose n x R, R x R or m x m entries exceed the int range is not supported");
@@ -352,16 +367,18 @@ int cxk_add_lmi_factored(cxk_context* ctx, int n, int m, const int* rank_ptr, co
 // Real representation L(X): block (k, j) = sign[k ^ j][j] X_{k ^ j}; L(XY) = L(X) L(Y),
 // L(X^*) = L(X)^T, tr L(X) = d Re tr X.
 const int kHcSign[4][4] = {{1, 1, 1, 1}, {1, -1, -1, 1}, {1, 1, -1, -1}, {1, -1, 1, -1}};
-void EmbedPlanes(int d, int n, const double* planes, double* out /* (d n)^2 col-major */) {
-  const size_t nn = (size_t)n * n, N = (size_t)d * n;
+// (also for rectangular arguments, planes of n x cols: L(X) is (d n) x (d cols), and stays multiplicative)
+void EmbedPlanesRect(int d, int n, int cols, const double* planes, double* out /* (d n) x (d cols) col-major */) {
+  const size_t nc = (size_t)n * cols, N = (size_t)d * n;
   for (int k = 0; k < d; k++)
     for (int j = 0; j < d; j++) {
-      const double* X = planes + (size_t)(k ^ j) * nn;
+      const double* X = planes + (size_t)(k ^ j) * nc;
       const double sg = kHcSign[k ^ j][j];
-      for (int c = 0; c < n; c++)
-        for (int r = 0; r < n; r++) out[((size_t)j * n + c) * N + (size_t)k * n + r] = sg * X[(size_t)c * n + r];
+      for (int c = 0; c < cols; c++)
+        for (int r = 0; r < n; r++) out[((size_t)j * cols + c) * N + (size_t)k * n + r] = sg * X[(size_t)c * n + r];
     }
 }
+void EmbedPlanes(int d, int n, const double* planes, double* out /* (d n)^2 col-major */) { EmbedPlanesRect(d, n, n, planes, out); }
 void ExtractPlanes(int d, int n, const double* emb, double* planes) {
   const size_t nn = (size_t)n * n, N = (size_t)d * n;
   for (int k = 0; k < d; k++)  // block (k, 0) = sign[k][0] X_k = X_k
@@ -401,6 +418,54 @@ int cxk_add_hermitian(cxk_context* ctx, int n, int d, int m, const double* A, co
   r.A.resize((size_t)m * NN);
   r.C.resize(NN);
   for (int i = 0; i < m; i++) EmbedPlanes(d, n, A + (size_t)i * d * nn, r.A.data() + (size_t)i * NN);
+  EmbedPlanes(d, n, C, r.C.data());
+  return AddConstraint(ctx, std::move(r), vars);
+}
+
+int cxk_add_hermitian_factored(cxk_context* ctx, int n, int d, int m, const int* rank_ptr, const double* F, const double* sigma,
+                               const double* C, const int* vars) {
+  if (!ctx) return -1;
+  auto refuse = [ctx](const char* msg) {
+    ctx->err = std::string("cxk_add_hermitian_factored: ") + msg;
+    return -1;
+  };
+  if (n < 1 || m < 0) return refuse("n is at least 1 and m at least 0");
+  if (d == 8) return refuse("hyper-complex dimension 8: the octonions have no real representation, factors are for d = 1, 2, 4");
+  if (d != 1 && d != 2 && d != 4) return refuse("the hyper-complex dimension is 1, 2 or 4");
+  if (!rank_ptr || !C) return refuse("rank_ptr or C is null");
+  if (rank_ptr[0] != 0) return refuse("rank_ptr[0] is not 0");
+  for (int i = 0; i < m; i++)
+    if (rank_ptr[i + 1] < rank_ptr[i]) return refuse("rank_ptr decreases");
+  const int R = rank_ptr[m];
+  if (R > 0 && !F) return refuse("F is null");
+  const size_t nr = (size_t)n * R, nn = (size_t)n * n;
+  for (size_t q = 0; q < d * nr; q++)
+    if (!std::isfinite(F[q])) return refuse("F holds a value that is not finite");
+  for (int k = 0; sigma && k < R; k++)
+    if (!std::isfinite(sigma[k])) return refuse("sigma holds a value that is not finite");
+  for (size_t q = 0; q < d * nn; q++)
+    if (!std::isfinite(C[q])) return refuse("C holds a value that is not finite");
+  for (int p = 0; p < d; p++)
+    for (int c = 0; c < n; c++)
+      for (int q = c; q < n; q++) {
+        const double lo = C[p * nn + q + (size_t)c * n], up = C[p * nn + c + (size_t)q * n];
+        if (p == 0 ? lo != up : lo != -up) return refuse("C is not Hermitian (plane 0 symmetric, the others skew)");
+      }
+  ConstraintRec r;
+  r.type = CXK_LMI;
+  r.herm_d = d;
+  r.n = d * n;
+  r.m = m;
+  r.factored = true;
+  r.f_R = R;
+  r.f_ptr.assign(rank_ptr, rank_ptr + m + 1);
+  r.f_F.resize((size_t)d * d * nr);  // L(F): (d n) x (d R); its first R columns are the stacked planes
+  if (R > 0) EmbedPlanesRect(d, n, R, F, r.f_F.data());
+  if (sigma)
+    r.f_sigma.assign(sigma, sigma + R);
+  else
+    r.f_sigma.assign((size_t)R, 1.0);
+  r.C.resize((size_t)r.n * r.n);
   EmbedPlanes(d, n, C, r.C.data());
   return AddConstraint(ctx, std::move(r), vars);
 }
@@ -1400,6 +1465,14 @@ int cxk_assembly_work(const cxk_context* ctx, double* bytes, double* flops) {
         const double ri = c.f_ptr[i + 1] - c.f_ptr[i];
         below += (int)ri;
         terms += ri * below;
+      }
+      if (c.herm_d > 1) {
+        // the folded Hermitian form (n = d x order): Z and Y from F0 alone, P = L(F)' Z (d planes of R x R, full),
+        // 2 d + 1 flops per term of G; bytes: F0 and L(F) read once each, P's d planes
+        const double d = c.herm_d;
+        F += 4 * n * n * R + 2 * n * d * R * R + 4 * n * n * n + 4 * n * n + (2 * d + 1) * terms + 2 * n * R + 2 * R;
+        B += 8.0 * (n * R + n * d * R + 2 * n * n + 4 * n * R + n * R + d * R * R + 4 * n * n + m * (m + 1) / 2 + 2 * m + R + m);
+        continue;
       }
       F += 4 * n * n * R + n * R * (R + 1) + 4 * n * n * n + 4 * n * n + 3 * terms + 2 * n * R + 2 * R;
       B += 8.0 * (n * R + 2 * n * n + 4 * n * R + n * R + R * (R + 1) / 2 + 4 * n * n + m * (m + 1) / 2 + 2 * m + R + m);

@@ -81,6 +81,8 @@ int FlushDeferred(cxk_context* ctx, bool keep_scalars = false, bool keep_y = fal
 
 // ---- kkt_cone_launch.hip
 CXK_LOCAL hipError_t RaiseConeLdsLimits();
+// the largest order whose one-workgroup Lanczos run (lmi_large_spectrum, LmiLargeSpectrumLds) fits kLdsLimit
+CXK_LOCAL int LmiLargeSpectrumMaxOrder();
 CXK_LOCAL int GroupConstraints(cxk_context* ctx, const FinalizeSwitches& sw);     // finalize: constraints of one shape form a group
 CXK_LOCAL int UploadGroup(cxk_context* ctx, Group& g, const FinalizeSwitches& sw);  // finalize: one group's data and work space
 bool ClockSample(cxk_context* ctx, int slot, hipEvent_t* e0, hipEvent_t* e1);

@@ -42,7 +42,8 @@ double ConstraintWork(const ConstraintRec& c) {
   const double n = c.n, m = c.m;
   switch (c.type) {
     case CXK_LMI:
-      if (c.factored) return 4 * n * n * c.f_R + 2 * n * (double)c.f_R * c.f_R + 4 * n * n * n;
+      // (a Hermitian factored record: n = d x order, P = L(F)' Z has d planes)
+      if (c.factored) return 4 * n * n * c.f_R + 2 * n * (double)c.f_R * c.f_R * std::max(c.herm_d, 1) + 4 * n * n * n;
       return 4 * n * n * n * (m + 1) + n * n * m * m;
     case CXK_LINEAR: return n * m * m;
     case CXK_SOC: return (n + 1) * m * m;

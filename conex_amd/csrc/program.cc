@@ -64,7 +64,8 @@ struct Cone {
   std::vector<double> c;
   std::vector<double> Q;  // kQuadCone: inner-product matrix (order x order), empty = identity
   // kLmi added by CONEX_HIP_AddFactoredLMIConstraint: A_v = sum_k sigma[k] f_k f_k', k in rank_ptr[v] .. rank_ptr[v + 1] - 1,
-  // f_k the columns of F (order x rank_ptr.back()); `mats` stays empty, `affine` holds C
+  // f_k the columns of F (order x rank_ptr.back()); `mats` stays empty, `affine` holds C.  Added by
+  // CONEX_HIP_AddFactoredHermitianConstraint (`hermitian` set): F and `affine` hold `hyper` planes
   bool factored = false;
   std::vector<double> F, sigma;
   std::vector<int> rank_ptr;
@@ -181,8 +182,10 @@ int BuildContext(Program* p) {
     switch (c.kind) {
       case kLmi: {  // (hyper is 1 for a DenseLMIConstraint)
         if (c.factored) {  // the factors go to the device as they are: the matrices are never formed
-          id = cxk_add_lmi_factored(p->ctx, c.order, m, c.rank_ptr.data(), c.F.data(), c.sigma.data(), c.affine.data(),
-                                    c.vars.data());
+          id = c.hermitian ? cxk_add_hermitian_factored(p->ctx, c.order, c.hyper, m, c.rank_ptr.data(), c.F.data(),
+                                                        c.sigma.data(), c.affine.data(), c.vars.data())
+                           : cxk_add_lmi_factored(p->ctx, c.order, m, c.rank_ptr.data(), c.F.data(), c.sigma.data(),
+                                                  c.affine.data(), c.vars.data());
           break;
         }
         const size_t sz = (size_t)c.order * c.order * c.hyper;
@@ -1283,6 +1286,57 @@ int CONEX_HIP_AddFactoredLMIConstraint(void* x, int n, const double* F, int R, c
     k.sigma.assign((size_t)R, 1.0);
   k.rank_ptr.assign(rank_ptr, rank_ptr + num_vars + 1);
   k.affine.assign(c, c + nn);
+  if (vars) {
+    for (int i = 0; i < num_vars; i++) {
+      if (vars[i] < 0 || vars[i] >= p->num_vars) return -1;
+      k.vars.push_back((int)vars[i]);
+    }
+  } else {
+    k.vars = AllVars(*p);
+  }
+  return AddCone(p, std::move(k));
+}
+
+/* not part of conex.h: a HermitianPsdConstraint over R / C / H (d = 1, 2, 4) whose matrices are low-rank and given by
+ * their factors,  A_v = sum_k sigma[k] f_k f_k^*,  k = rank_ptr[v] .. rank_ptr[v + 1] - 1,  v < num_vars,
+ * f_k the hyper-complex columns of F (d planes of n x R column-major, R = rank_ptr[num_vars]); sigma NULL = all +1; c
+ * the affine term, d planes of n x n (plane 0 symmetric, the others skew); vars as above.  The matrices are never
+ * formed (cxk_add_hermitian_factored).  CONEX_UpdateLinearOperator and CONEX_UpdateAffineTerm fail on such a
+ * constraint; CONEX_GetDualVariable gives the real plane, as for every Hermitian constraint.
+ * Returns the constraint id, -1 on invalid arguments. */
+int CONEX_HIP_AddFactoredHermitianConstraint(void* x, int n, int d, const double* F, int R, const double* sigma,
+                                             const int* rank_ptr, int num_vars, const double* c, const long* vars) {
+  Program* p = static_cast<Program*>(x);
+  if (!p || p->magic != 0xC0DEC0DEu || n < 1 || R < 0 || num_vars < 0 || !rank_ptr || !c || (R > 0 && !F)) return -1;
+  if (d != 1 && d != 2 && d != 4) return -1;
+  if (vars ? false : num_vars != p->num_vars) return -1;
+  if (rank_ptr[0] != 0 || rank_ptr[num_vars] != R) return -1;
+  for (int v = 0; v < num_vars; v++)
+    if (rank_ptr[v + 1] < rank_ptr[v]) return -1;
+  const size_t nn = (size_t)n * n, nr = (size_t)n * R;
+  for (size_t q = 0; q < d * nr; q++)
+    if (!std::isfinite(F[q])) return -1;
+  for (int k = 0; sigma && k < R; k++)
+    if (!std::isfinite(sigma[k])) return -1;
+  for (int pl = 0; pl < d; pl++)
+    for (int col = 0; col < n; col++)
+      for (int row = col; row < n; row++) {
+        const double lo = c[pl * nn + row + (size_t)col * n], up = c[pl * nn + col + (size_t)row * n];
+        if (!std::isfinite(lo) || (pl == 0 ? lo != up : lo != -up)) return -1;
+      }
+  Cone k;
+  k.kind = kLmi;
+  k.order = n;
+  k.hyper = d;
+  k.hermitian = true;
+  k.factored = true;
+  k.F.assign(F, F + d * nr);
+  if (sigma)
+    k.sigma.assign(sigma, sigma + R);
+  else
+    k.sigma.assign((size_t)R, 1.0);
+  k.rank_ptr.assign(rank_ptr, rank_ptr + num_vars + 1);
+  k.affine.assign(c, c + d * nn);
   if (vars) {
     for (int i = 0; i < num_vars; i++) {
       if (vars[i] < 0 || vars[i] >= p->num_vars) return -1;

@@ -35,6 +35,8 @@ _SIGNATURES = {
     "cxk_add_lmi": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_double_p, c_double_p, c_int_p]),
     "cxk_add_lmi_factored": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_int_p, c_double_p, c_double_p, c_double_p, c_int_p]),
     "cxk_count_factored_lmi": (C.c_int, [C.c_void_p]),
+    "cxk_add_hermitian_factored": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, c_int_p, c_double_p, c_double_p, c_double_p,
+                                             c_int_p]),
     "cxk_add_linear": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_double_p, c_double_p, c_int_p]),
     "cxk_add_soc": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_double_p, c_double_p, c_int_p]),
     "cxk_add_quadratic": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p, c_int_p]),
@@ -314,6 +316,28 @@ class KktContext:
         c = np.ascontiguousarray(np.swapaxes(np.asarray(Cm, dtype=np.float64), -1, -2)).ravel()
         keep, vp = self._vars(vars_)
         r = self.L.cxk_add_hermitian(self.h, n, d, m, _dp(a), _dp(c), vp)
+        if r >= 0:
+            self.cons.append(("herm", n, m, d))
+        return r
+
+    def add_hermitian_factored(self, F, rank_ptr, sigma, Cm, vars_=None):
+        """The constraint of add_hermitian with A_i = sum_k sigma[k] f_k f_k^*, k in rank_ptr[i]:rank_ptr[i + 1], f_k the
+        hyper-complex columns of F: F is (d, n, R) real planes, d in {1, 2, 4}, Cm (d, n, n), rank_ptr has m + 1 entries,
+        sigma R signs or weights (None: all +1).  Neither the A_i nor their real representations are formed."""
+        Cm = np.asarray(Cm, dtype=np.float64)
+        F = np.asarray(F, dtype=np.float64)
+        if Cm.ndim != 3 or Cm.shape[1] != Cm.shape[2] or F.ndim != 3 or F.shape[:2] != Cm.shape[:2]:
+            raise ValueError("add_hermitian_factored: F is (d, n, R) planes and Cm (d, n, n) planes of the same d and n")
+        d, n, R = F.shape
+        rp = np.ascontiguousarray(rank_ptr, dtype=np.int32)
+        sg = None if sigma is None else np.ascontiguousarray(np.asarray(sigma, dtype=np.float64).ravel())
+        if len(rp) < 1 or rp[-1] != R or (sg is not None and len(sg) != R):
+            raise ValueError("add_hermitian_factored: rank_ptr ends at the number of columns of F, which sigma has one entry for")
+        f = np.ascontiguousarray(np.swapaxes(F, -1, -2)).ravel()
+        c = np.ascontiguousarray(np.swapaxes(Cm, -1, -2)).ravel()
+        keep, vp = self._vars(vars_)
+        m = len(rp) - 1
+        r = self.L.cxk_add_hermitian_factored(self.h, n, d, m, _ip(rp), _dp(f), None if sg is None else _dp(sg), _dp(c), vp)
         if r >= 0:
             self.cons.append(("herm", n, m, d))
         return r
@@ -867,7 +891,8 @@ class KktContext:
         return self.L.cxk_count_sparse_soc(self.h)
 
     def count_factored_lmi(self):
-        """Constraints this context owns that were added by add_lmi_factored (kernels_lmi_factored.hip.h)."""
+        """Constraints this context owns that were added by add_lmi_factored or add_hermitian_factored
+        (kernels_lmi_factored.hip.h)."""
         return self.L.cxk_count_factored_lmi(self.h)
 
     def sparse_soc_setup_ms(self):

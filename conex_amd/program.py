@@ -236,6 +236,37 @@ class Conex:
         self.num_constraints += 1
         return cid
 
+    def AddFactoredHermitianMatrixInequality(self, F, rank_ptr, sigma, c, variables=None):
+        """c - sum_i y_i A_i positive semidefinite over R / C / H with low-rank Hermitian A_i = sum_k sigma[k] f_k f_k^*,
+        k in rank_ptr[i]:rank_ptr[i + 1], given by its factors and never expanded
+        (CONEX_HIP_AddFactoredHermitianConstraint, an extra next to the reference's surface).  F is (d, n, R) real planes
+        of the hyper-complex columns f_k, d in {1, 2, 4}; rank_ptr has one entry more than the constraint has variables
+        (len(variables), or all when None); sigma R entries or None (all +1); c is (d, n, n): plane 0 symmetric, the
+        others skew.  As for NewLinearMatrixInequality, the dual variable is the real plane and ComputeErrors does not
+        cover the constraint.  Returns the constraint id."""
+        c = np.asarray(c, dtype=np.float64)
+        F = np.asarray(F, dtype=np.float64)
+        if c.ndim != 3 or c.shape[1] != c.shape[2] or F.ndim != 3 or F.shape[:2] != c.shape[:2]:
+            raise ConexError("Invalid LMI")
+        d, n, R = F.shape
+        rp = np.ascontiguousarray(np.asarray(rank_ptr).ravel(), dtype=np.int32)
+        sg = np.ones(R) if sigma is None else _f64(np.asarray(sigma, dtype=np.float64).ravel())
+        if len(rp) < 1 or len(sg) != R:
+            raise ConexError("Invalid LMI")
+        v = None if variables is None else np.ascontiguousarray(np.asarray(variables).ravel(), dtype=np.int64)
+        if len(rp) - 1 != (self.m if v is None else len(v)):
+            raise ConexError("Invalid LMI")
+        Ff = np.ascontiguousarray(np.swapaxes(F, -1, -2)).ravel()
+        cf = np.ascontiguousarray(np.swapaxes(c, -1, -2)).ravel()
+        cid = self._L.CONEX_HIP_AddFactoredHermitianConstraint(
+            self.a, n, d, capi.dp(Ff), R, capi.dp(sg), rp.ctypes.data_as(C.POINTER(C.c_int)), len(rp) - 1, capi.dp(cf),
+            None if v is None else v.ctypes.data_as(C.POINTER(C.c_long)))
+        if cid < 0:
+            raise ConexError("Failed to add constraint.")
+        self.c.append(c[0].copy())
+        self.num_constraints += 1
+        return cid
+
     def AddQuadraticConstraint(self, Q, A, c, variables=None):
         """c - A y in {(x0, x1): x0 >= sqrt(x1' Q x1)}: the reference's QuadraticConstraint(Q, A, c), which it reaches
         through its C++ API only (an extra next to its Python surface, like CONEX_HIP_AddQuadraticConstraint itself).

@@ -111,6 +111,67 @@ def factored_lmi_problem(K=4, n=12, ranks=(1,) * 8, branching=2, overlap=2, seed
     return dict(F=Fs, rank_ptr=ptrs, sigma=sigs, A=A, C=Cm, cliques=cliques, num_vars=num_vars, b=b, n=n, m=m)
 
 
+def expand_hermitian_factors(F, rank_ptr, sigma):
+    """The planes of a factored Hermitian constraint: A_i = sum_k sigma[k] f_k f_k^*, k in rank_ptr[i]:rank_ptr[i + 1],
+    f_k the hyper-complex column k of F (d, n, R).  Returns (m, d, n, n): plane 0 symmetric, the others skew."""
+    F = np.asarray(F, dtype=np.float64)
+    d, n, m = F.shape[0], F.shape[1], len(rank_ptr) - 1
+    A = np.zeros((m, d, n, n))
+    for i in range(m):
+        for k in range(rank_ptr[i], rank_ptr[i + 1]):
+            f = F[:, :, k:k + 1]
+            fs = np.swapaxes(f, -1, -2).copy()  # f^*: the conjugate transpose
+            fs[1:] = -fs[1:]
+            A[i] += sigma[k] * hc_multiply(f, fs)
+        A[i, 0] = 0.5 * (A[i, 0] + A[i, 0].T)
+        for p in range(1, d):
+            A[i, p] = 0.5 * (A[i, p] - A[i, p].T)
+    return A
+
+
+def factored_hermitian_problem(K=4, n=5, d=2, ranks=(1,) * 6, branching=2, overlap=2, seed=SEED, signs="plus", factors=None):
+    """K low-rank Hermitian constraints of order n over R / C / H (d = 1, 2, 4) on the clique tree of lmi_problem, given
+    by factors and expanded: factored_lmi_problem with hyper-complex Gaussian vectors.  Member c has F[c] (d, n, R),
+    rank_ptr[c] (m + 1) and sigma[c] (R); signs and factors as there.  C is Hermitian positive definite and
+    b_i = sum_c <A_ci, X_c> for positive definite X_c.  Returns dict(F, rank_ptr, sigma, A (K, m, d, n, n), C (K, d, n, n),
+    cliques, num_vars, b, n, m, d)."""
+    rng = np.random.default_rng(seed)
+    per = [list(r) for r in ranks] if len(ranks) and np.ndim(ranks[0]) else [list(ranks)] * K
+    m = len(factors[0][1]) - 1 if factors is not None else len(per[0])
+    cliques, num_vars = tree_cliques(K, branching, m, min(overlap, m)) if m else ([[] for _ in range(K)], 0)
+    Fs, ptrs, sigs = [], [], []
+    for c in range(K):
+        if factors is not None:
+            F, ptr, sg = factors[c]
+            F = np.asarray(F, dtype=np.float64).reshape(d, n, -1)
+            ptr = np.asarray(ptr, dtype=np.int32)
+            sg = np.ones(F.shape[2]) if sg is None else np.asarray(sg, dtype=np.float64)
+        else:
+            ptr = np.concatenate([[0], np.cumsum(per[c])]).astype(np.int32)
+            R = int(ptr[-1])
+            F = rng.standard_normal((d, n, R))
+            if signs == "plus":
+                sg = np.ones(R)
+            elif signs == "matrix":
+                sg = np.repeat(rng.choice([-1.0, 1.0], m), per[c])
+            else:
+                sg = rng.choice([-1.0, 1.0], R)
+        Fs.append(F)
+        ptrs.append(ptr)
+        sigs.append(sg)
+    A = np.stack([expand_hermitian_factors(Fs[c], ptrs[c], sigs[c]) for c in range(K)]) if K else np.zeros((0, m, d, n, n))
+    Cm = np.zeros((K, d, n, n))
+    b = np.zeros(num_vars)
+    for c in range(K):
+        Cm[c] = 0.2 * random_hermitian(rng, d, n) / (2 * n)
+        Cm[c, 0] += np.eye(n)
+        X = random_hermitian(rng, d, n) / (2 * n)
+        X = hc_multiply(X, X)
+        X[0] += np.eye(n) / n
+        b[cliques[c]] += np.einsum("ipab,pab->i", A[c], X)
+    return dict(F=Fs, rank_ptr=ptrs, sigma=sigs, A=A, C=Cm, cliques=cliques, num_vars=num_vars, b=b, n=n, m=m, d=d)
+
+
 def sparsify(prob, density, seed=SEED + 7):
     """Zero all but about `density` of the entries of every A_i of an lmi_problem / hermitian_problem
     (symmetric pattern, the diagonal of the first plane kept with the same probability plus one
@@ -331,6 +392,10 @@ def build(ctx_cls, prob, kind="lmi", **kw):
         p = ctx_cls(prob["num_vars"], **kw)
         for c, cl in enumerate(prob["cliques"]):
             assert p.add_lmi_factored(prob["F"][c], prob["rank_ptr"][c], prob["sigma"][c], prob["C"][c], cl) == c
+    elif kind == "herm-factored":
+        p = ctx_cls(prob["num_vars"], **kw)
+        for c, cl in enumerate(prob["cliques"]):
+            assert p.add_hermitian_factored(prob["F"][c], prob["rank_ptr"][c], prob["sigma"][c], prob["C"][c], cl) == c
     elif kind == "herm":
         p = ctx_cls(prob["num_vars"], **kw)
         for c, cl in enumerate(prob["cliques"]):

@@ -241,6 +241,32 @@ int cxk_add_lmi_factored(cxk_context* ctx, int n, int m, const int* rank_ptr /* 
                          const double* sigma /* R, NULL = all +1 */, const double* C /* n x n */, const int* vars);
 int cxk_count_factored_lmi(const cxk_context* ctx);
 
+/* Low-rank Hermitian matrix inequalities over R / C / H given by their factors: cxk_add_hermitian_factored adds the
+ * constraint of cxk_add_hermitian(ctx, n, d, m, A, C, vars), d in {1, 2, 4}, with
+ *   A_i = sum_k sigma_k f_k f_k^*,  k = rank_ptr[i] .. rank_ptr[i + 1] - 1,
+ * f_k the hyper-complex columns of F (d planes of n x R, column-major, R = rank_ptr[m]); C is d planes of n x n as
+ * cxk_add_hermitian takes them.  Neither the A_i nor their real representations L(A_i) are formed.  The record is
+ * Hermitian (cxk_get_W / cxk_set_W / cxk_dual_size speak d planes) and factored (everything said of
+ * cxk_add_lmi_factored's constraint above holds, cxk_count_factored_lmi counts it).  With N = d n the device holds
+ * L(F) (N x dR: d times F; its first R columns F0 are the stacked planes), sigma, the pointers and L(C).  Only F0
+ * passes through W and C: Z = W F0, Y = C Z (N x R), P = L(F)' Z (d planes of R x R in one product), then
+ * G(i,j) = sum sigma_k sigma_l sum_p P_p(k,l)^2, AW(i) = sum sigma_k P_0(k,k), AQc(i) = sum sigma_k z_k' y_k, every
+ * contraction being tr / d as for cxk_add_hermitian; the slack is L(F) diag(sigma_k y_i(k)) L(F)' - k L(C): its first
+ * n columns from one N x n x dR product, the other block columns filled from them, so that it is exactly a real
+ * representation.  The assembly first replaces W by the real representation nearest to it (TakeStep leaves it one
+ * only to rounding, and the folded sums read W through one column block of L(F)); a W that is one keeps its bits.
+ * Behind the slack run the large-order route's Hermitian rules (Taylor-squaring exponential, random-start Lanczos).  Fixed summation orders, no atomics: two runs give the same bits.
+ * Returns the constraint id, or -1 (cxk_last_error names the reason, prefixed "cxk_add_hermitian_factored: ") for:
+ * n < 1, m < 0; d not 1, 2 or 4 (the octonions, d = 8, have no real representation); null rank_ptr, C or (R > 0) F;
+ * rank_ptr[0] != 0; a decreasing rank_ptr; a value of F, sigma or C that is not finite; a C that is not Hermitian
+ * (plane 0 symmetric, the others skew).
+ * Refused at cxk_finalize, by name: N R, d R R, N dR or m m beyond the int range; an order N above 2549, whose Lanczos
+ * vectors (lmi_large_spectrum) exceed LDS -- the Taylor TakeStep has no LU, so cxk_add_lmi_factored's limit of 1024
+ * does not apply. */
+int cxk_add_hermitian_factored(cxk_context* ctx, int n, int d, int m, const int* rank_ptr /* m + 1 */,
+                               const double* F /* d planes of n x R, column-major */, const double* sigma /* R or NULL */,
+                               const double* C /* d planes of n x n, as cxk_add_hermitian */, const int* vars);
+
 /* Quadratic cones { x0 >= sqrt(x1' Q x1) } of real size.  The LDS route (quad_schur, quad_prepare, quad_take_step)
  * gives a cone one workgroup and runs its maps, the products with Q among them, on one thread; a cone whose
  * variables + 4 (dimension + 1) doubles exceed LDS is refused at cxk_finalize.  The streamed route

@@ -5,6 +5,7 @@
   python tools/lmi_factored_speed.py --n 200 --m 200 --parent-lib /path/to/parent/libconex.so
   python tools/lmi_factored_speed.py --sweep                        # n in {64, 200, 500}, m in {n/4, n, 4n}
   python tools/lmi_factored_speed.py --n 1000 --m 4000 --factored   # a shape the dense form cannot hold
+  python tools/lmi_factored_speed.py --herm 2 --n 200 --m 200       # complex Hermitian: add_hermitian_factored against add_hermitian
 
 One constraint of order n over m variables, A_i = f_i f_i' with dense Gaussian f_i (--rank r: r columns each), C = I,
 W at the well-conditioned point of the LMI tests.  Times come from the library's kernel clocks (cxk_kernel_clock:
@@ -14,6 +15,9 @@ library (a build from before the factored route), each form in fresh processes, 
 medians are printed, then the medians over the pairs.  Prints one JSON line per shape: microseconds per stage and form,
 the speed-ups, the device bytes held for A and for F, and the route's own flop count (cxk_assembly_work).  A shape
 whose expanded form exceeds --dense-limit-gb (8) is measured in the factored form only, and says so.
+--herm d (2 or 4; 1 for the Hermitian rules over R): the f_i are hyper-complex, A_i = f_i f_i^*, the factored form is
+add_hermitian_factored and the expanded one add_hermitian on the d planes of every A_i; both hold their data in the real
+representation of order d n on the device (m (d n)^2 doubles against d n x d R).
 """
 import argparse
 import json
@@ -42,8 +46,30 @@ def load_other_library():
     kkt.LIB_PATH = path
 
 
-def dense_bytes(n, m):
-    return 8.0 * m * n * n
+def dense_bytes(n, m, d=1):
+    return 8.0 * m * (d * n) * (d * n)
+
+
+def hermitian_context(a, form):
+    from conex_amd import KktContext
+    from conex_amd import synthetic as syn
+    rng = np.random.default_rng(1)
+    n, m, d, R = a.n, a.m, a.herm, a.m * a.rank
+    F = rng.standard_normal((d, n, R)) / np.sqrt(d * n)
+    ptr = np.arange(0, R + 1, a.rank)
+    Cm = np.zeros((d, n, n))
+    Cm[0] = np.eye(n)
+    k = KktContext(m, device=0)
+    if form == "factored":
+        assert k.add_hermitian_factored(F, ptr, None, Cm) == 0
+    else:
+        A = syn.expand_hermitian_factors(F, ptr, np.ones(R))
+        assert k.add_hermitian(A, Cm) == 0
+        del A
+    k.initialize()
+    k.sync()
+    W = syn.hermitian_scaling_points(1, n, d, seed=2)[0]
+    return k, W, 8.0 * (d * n) * (d * R) if form == "factored" else dense_bytes(n, m, d)
 
 
 def context(a, form):
@@ -51,23 +77,27 @@ def context(a, form):
     from conex_amd import synthetic as syn
     rng = np.random.default_rng(1)
     n, m, R = a.n, a.m, a.m * a.rank
-    F = rng.standard_normal((n, R)) / np.sqrt(n)
-    ptr = np.arange(0, R + 1, a.rank)
-    k = KktContext(m, device=0)
-    if form == "factored":
-        assert k.add_lmi_factored(F, ptr, None, np.eye(n)) == 0
+    if a.herm:
+        k, W, held = hermitian_context(a, form)
     else:
-        A = np.einsum("aik,bik->iab", F.reshape(n, m, a.rank), F.reshape(n, m, a.rank))
-        assert k.add_lmi(A, np.eye(n)) == 0
-        del A
-    k.initialize()
-    k.sync()
-    W = syn.scaling_points(1, n, seed=2, scale=0.3)[0]
+        F = rng.standard_normal((n, R)) / np.sqrt(n)
+        ptr = np.arange(0, R + 1, a.rank)
+        k = KktContext(m, device=0)
+        if form == "factored":
+            assert k.add_lmi_factored(F, ptr, None, np.eye(n)) == 0
+        else:
+            A = np.einsum("aik,bik->iab", F.reshape(n, m, a.rank), F.reshape(n, m, a.rank))
+            assert k.add_lmi(A, np.eye(n)) == 0
+            del A
+        k.initialize()
+        k.sync()
+        W = syn.scaling_points(1, n, seed=2, scale=0.3)[0]
+        held = 8.0 * n * R if form == "factored" else dense_bytes(n, m)
     k.set_W(0, W)
     k.set_y(rng.uniform(-1, 1, k.N) * (0.25 / max(1, m)))
     k.enable_timing(True)
     byt, flops = k.assembly_work()
-    info = {"held_bytes": 8.0 * n * R if form == "factored" else dense_bytes(n, m), "work_flops": flops, "work_bytes": byt}
+    info = {"held_bytes": held, "work_flops": flops, "work_bytes": byt}
     if form == "factored":
         assert k.count_factored_lmi() == 1
     return k, W, info
@@ -96,9 +126,10 @@ def once(k, slot, call):
 
 
 def measure(a, forms):
-    out = {"n": a.n, "m": a.m, "rank": a.rank, "rounds": a.rounds}
-    if "dense" in forms and dense_bytes(a.n, a.m) > a.dense_limit_gb * 2.0 ** 30:
-        out["dense_skipped"] = f"the expanded form holds {dense_bytes(a.n, a.m) / 2.0 ** 30:.1f} GB (limit {a.dense_limit_gb:g})"
+    out = {"n": a.n, "m": a.m, "rank": a.rank, "herm": a.herm, "rounds": a.rounds}
+    held = dense_bytes(a.n, a.m, max(a.herm, 1))
+    if "dense" in forms and held > a.dense_limit_gb * 2.0 ** 30:
+        out["dense_skipped"] = f"the expanded form holds {held / 2.0 ** 30:.1f} GB (limit {a.dense_limit_gb:g})"
         forms = tuple(f for f in forms if f != "dense")
     built = {name: context(a, name) for name in forms}
     calls = {name: stage_calls(k, W) for name, (k, W, _) in built.items()}
@@ -126,7 +157,7 @@ def finish(out):
 
 
 def child(a, form, parent):
-    cmd = [sys.executable, os.path.abspath(__file__), "--n", str(a.n), "--m", str(a.m), "--rank", str(a.rank), "--" + form,
+    cmd = [sys.executable, os.path.abspath(__file__), "--n", str(a.n), "--m", str(a.m), "--rank", str(a.rank), "--herm", str(a.herm), "--" + form,
            "--rounds", str(a.rounds), "--warmup", str(a.warmup), "--dense-limit-gb", str(a.dense_limit_gb)]
     env = dict(os.environ)
     env.pop("CONEX_AMD_LIB", None)
@@ -164,6 +195,7 @@ def main():
     ap.add_argument("--n", type=int, default=200)
     ap.add_argument("--m", type=int, default=200)
     ap.add_argument("--rank", type=int, default=1)
+    ap.add_argument("--herm", type=int, default=0, choices=(0, 1, 2, 4), help="hyper-complex dimension d of the Hermitian mode (0: real LMI)")
     ap.add_argument("--dense", action="store_true", help="the expanded form only")
     ap.add_argument("--factored", action="store_true", help="the factored form only")
     ap.add_argument("--rounds", type=int, default=30)
