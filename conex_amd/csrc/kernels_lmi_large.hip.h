@@ -16,6 +16,7 @@
 #pragma once
 #include "kernels_gemm.hip.h"
 #include "kernels_lmi.hip.h"
+#include "kernels_lmi_wide.hip.h"
 
 namespace cxk {
 
@@ -31,6 +32,10 @@ struct LmiLargeWs {
   // `fold` columns of every [A_1 .. A_m C], side by side (count x n x fold (m+1), leading dimension n)
   int fold;
   const double* Aleft;
+  // not null: the group's Lanczos runs take the chip-wide kernels (kernels_lmi_wide.hip.h) in this work space,
+  // count x LmiWideDoubles(n, herm_d); null: lmi_large_spectrum on one workgroup per constraint
+  double* wide;
+  bool wide_reduce;  // its partials are summed by lmi_wide_reduce (orders from kWideReduceMinOrder on)
 };
 
 // ---- assembly ---------------------------------------------------------------------------
@@ -186,6 +191,7 @@ __global__ void __launch_bounds__(256) lmi_large_taylor_head(int n, const double
 // factored with pivoting inside one workgroup (panel in LDS), the row swaps and the triangular
 // solves run column-parallel, every O(n^3) update is the batched fp64 MFMA GEMM.
 constexpr int kLuNB = 32;
+constexpr int kLuPanelMaxRows = 1024;  // lu_panel: one row per thread; taller panels take lu_panel_tall
 
 // Panel factorization: rows k0..n-1, columns k0..k0+nb-1.  grid = constraints, one THREAD PER
 // ROW with the row's nb <= 32 panel entries in registers (static indices: the column loop is
@@ -282,6 +288,78 @@ __global__ void __launch_bounds__(1024) lu_panel(double* __restrict__ aug_all, i
   }
 }
 
+// The same panel for MORE rows than a workgroup has threads (n - k0 > 1024): the panel stays in memory (its
+// (n - k0) x 32 doubles are L2-resident) and one workgroup works it column by column, thread t on rows t, t + 1024, ..
+// Per column: every thread's first largest |entry| over its rows in ascending order, then the same butterfly and
+// wave-order comparison as lu_panel (ties go to the lower row: Eigen's first maximum), rows j and p trade places
+// across the panel while the new row j lands in LDS as the broadcast operand, then the rank-1 update.  No atomics,
+// one order for every comparison: the result depends on the data alone.  Four barriers per column.
+__global__ void __launch_bounds__(1024) lu_panel_tall(double* __restrict__ aug_all, int n, int k0, int nb,
+                                                      int* __restrict__ piv_all) {
+  __shared__ double urow[kLuNB];
+  __shared__ double s_val[16];
+  __shared__ int s_idx[16];
+  __shared__ int s_piv;
+  double* a = aug_all + (size_t)blockIdx.x * 2 * n * n + k0 + (size_t)k0 * n;  // panel entry (r, c) at a[r + c n]
+  int* piv = piv_all + (size_t)blockIdx.x * n;
+  const int rows = n - k0, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
+  for (int j = 0; j < nb; j++) {
+    const double* col = a + (size_t)j * n;
+    double best = -1.0;
+    int bi = j + tid < rows ? j + tid : INT_MAX;
+    for (int r = j + tid; r < rows; r += blockDim.x) {
+      const double v = fabs(col[r]);
+      if (v > best) {
+        best = v;
+        bi = r;
+      }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+      const double ov = __shfl_xor(best, off, 64);
+      const int oi = __shfl_xor(bi, off, 64);
+      if (ov > best || (ov == best && oi < bi)) {
+        best = ov;
+        bi = oi;
+      }
+    }
+    if (lane == 0) {
+      s_val[wave] = best;
+      s_idx[wave] = bi;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      double b = s_val[0];
+      int p = s_idx[0];
+      for (int w = 1; w < nw; w++)
+        if (s_val[w] > b || (s_val[w] == b && s_idx[w] < p)) {
+          b = s_val[w];
+          p = s_idx[w];
+        }
+      s_piv = p;
+      piv[k0 + j] = k0 + p;
+    }
+    __syncthreads();
+    const int p = s_piv;
+    if (tid < nb) {
+      double* c = a + (size_t)tid * n;
+      const double vp = c[p];
+      if (p != j) {
+        c[p] = c[j];
+        c[j] = vp;
+      }
+      urow[tid] = vp;
+    }
+    __syncthreads();
+    const double pivot = urow[j];
+    for (int r = j + 1 + tid; r < rows; r += blockDim.x) {
+      const double l = a[r + (size_t)j * n] / pivot;
+      a[r + (size_t)j * n] = l;
+      for (int c = j + 1; c < nb; c++) a[r + (size_t)c * n] -= l * urow[c];
+    }
+    __syncthreads();  // (the next column's search reads what this update wrote; urow and s_piv are free again)
+  }
+}
+
 // Columns outside the panel (0..k0-1 and k0+nb..2n-1): apply the panel's row swaps, then for the
 // columns to the right the unit-lower solve x <- L11^-1 x.  grid = (column blocks, constraints).
 // One thread per column; NB is the compile-time block size (registers with static indices; the
@@ -371,7 +449,6 @@ __global__ void __launch_bounds__(256) lu_backsolve_block(double* __restrict__ a
 }
 
 inline hipError_t LmiLargeLuSolve(int n, int count, double* aug, int* piv, hipStream_t st) {
-  if (n > 1024) return hipErrorNotSupported;  // one panel row per thread
   const int64_t an = 2 * (int64_t)n * n;
   hipError_t e;
   auto gemm = [&](int M, int N, int K, const double* A, const double* B, double* C) {
@@ -396,7 +473,9 @@ inline hipError_t LmiLargeLuSolve(int n, int count, double* aug, int* piv, hipSt
   };
   for (int k0 = 0; k0 < n; k0 += kLuNB) {
     const int nb = std::min(kLuNB, n - k0), below = n - k0 - nb;
-    {
+    if (n - k0 > kLuPanelMaxRows) {  // (such a panel is always 32 columns wide)
+      lu_panel_tall<<<count, 1024, 0, st>>>(aug, n, k0, nb, piv);
+    } else {
       const int threads = std::min(1024, ((n - k0 + 63) / 64) * 64);
       lu_panel<kLuNB><<<count, threads, 0, st>>>(aug, n, k0, nb, piv);
     }
@@ -816,6 +895,7 @@ inline hipError_t LmiLargeAfterSlack(const LmiGroup& g, const StepArgs& sa, cons
     lmi_large_affine<<<ElemGrid(n, g.count), 256, 0, st>>>(n, sa.e_weight, T, g.W);
     return hipGetLastError();
   }
+  if (ws.wide) return LmiWideSpectrum(g, sa, WS, S, ws.wide, ws.wide_reduce, mode, st);
   if (mode == 0)
     lmi_large_spectrum<0><<<g.count, 512, LmiLargeSpectrumLds(n), st>>>(g, sa, WS, S);
   else

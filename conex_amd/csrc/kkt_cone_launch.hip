@@ -431,6 +431,8 @@ LmiLargeWs MakeLargeWs(Group& g) {
   w.splits = g.splits;
   w.fold = g.Aleft.n ? g.n / g.herm_d : 0;
   w.Aleft = g.Aleft.p;
+  w.wide = g.ws_wide.n ? g.ws_wide.p : nullptr;
+  w.wide_reduce = g.wide_reduce;
   return w;
 }
 
@@ -1267,6 +1269,10 @@ int UploadGroup(cxk_context* ctx, Group& g, const FinalizeSwitches& sw) {
                                                   sw.schur_generic, sw.gemm_min_n);
     g.large = a.large;
     g.assembly = a.assembly;
+    const int wide = WideSpectrumMode(ctx, sw);
+    if (g.large && (wide == 1 || (wide == -1 && g.n > LmiLargeSpectrumMaxOrder())))
+      CXK_TRY(g.ws_wide.alloc(cnt * LmiWideDoubles(g.n, g.herm_d)));
+    g.wide_reduce = g.n >= (sw.wide_reduce_min_order >= 0 ? sw.wide_reduce_min_order : kWideReduceMinOrder);
   }
   // the routes that hold their data as nonzeros or factors keep no dense copy of A on the device
   const bool dense_a = g.route != ConeRoute::kLmiSparse && g.route != ConeRoute::kLmiFactored &&

@@ -109,6 +109,8 @@ static FinalizeSwitches ReadFinalizeSwitches() {
   if ((v = getenv("CXK_TILED_LINEAR_MIN_WORK")) && v[0] != '\0') sw.modes.tiled_linear_min_work = std::max(0ll, atoll(v));
   if ((v = getenv("CXK_SPARSE_SOC")) && v[0] != '\0') sw.modes.sparse_soc = atoi(v) != 0;
   if ((v = getenv("CXK_SPARSE_SOC_MIN_RATIO")) && v[0] != '\0') sw.modes.sparse_soc_min_ratio = std::max(0.0, atof(v));
+  if ((v = getenv("CXK_WIDE_SPECTRUM")) && v[0] != '\0') sw.wide_spectrum = std::max(-1, std::min(1, atoi(v)));
+  if ((v = getenv("CXK_WIDE_REDUCE_MIN_ORDER")) && v[0] != '\0') sw.wide_reduce_min_order = std::max(0, atoi(v));
   return sw;
 }
 
@@ -230,6 +232,19 @@ static int FinalizeImpl(cxk_context* ctx) {
       CXK_DEMAND((int64_t)c.n * c.f_R <= INT_MAX && (int64_t)c.f_R * c.f_R <= INT_MAX && (int64_t)c.m * c.m <= INT_MAX,
                  "a factored LMI whose n x R, R x R or m x m entries exceed the int range is not supported");
     }
+  // matrix inequalities given by their matrices: any order whose n x n entries the kernels can index; beyond the
+  // one-workgroup Lanczos run (lmi_large_spectrum) only with the chip-wide one (cxk_set_wide_spectrum)
+  for (const ConstraintRec& c : ctx->cons)
+    if (c.type == CXK_LMI && !c.factored) {
+      CXK_DEMAND((int64_t)c.n * c.n <= INT_MAX,
+                 "a matrix inequality of order above 46340 is not supported (the kernels index its n x n entries with ints)");
+      if (c.n > LmiLargeSpectrumMaxOrder() && WideSpectrumMode(ctx, sw) == 0) {
+        ctx->err = "a matrix inequality whose (real representation's) order is above " + std::to_string(LmiLargeSpectrumMaxOrder()) +
+                   " needs the chip-wide Lanczos run (cxk_set_wide_spectrum / CXK_WIDE_SPECTRUM, which is 0)";
+        fprintf(stderr, "%s line %d: %s\n", __FILE__, __LINE__, ctx->err.c_str());
+        return CXK_FAILURE;
+      }
+    }
   if (ChooseEliminationStructure(ctx, sw)) return CXK_FAILURE;
   ctx->finalized = true;
   if (ctx->device < 0) return CXK_SUCCESS;  // symbolic-only context
@@ -310,6 +325,8 @@ int cxk_add_lmi(cxk_context* ctx, int n, int m, const double* A, const double* C
   r.type = CXK_LMI;
   r.n = n;
   r.m = m;
+  // (an order whose n x n entries no int indexes is refused by cxk_finalize, by name: its 17 GB and more are not copied)
+  if ((int64_t)n * n > INT_MAX) return AddConstraint(ctx, std::move(r), vars);
   r.A.assign(A, A + (size_t)m * n * n);
   r.C.assign(C, C + (size_t)n * n);
   auto symmetric = [n](const double* X) {
@@ -672,6 +689,21 @@ int cxk_set_sparse_soc(cxk_context* ctx, int mode) {
 int cxk_count_sparse_soc(const cxk_context* ctx) { return CountOnRoute(ctx, ConeRoute::kSocSparse); }
 
 double cxk_sparse_soc_setup_ms(const cxk_context* ctx) { return ctx && ctx->finalized ? ctx->sparse_soc_setup_ms : 0.0; }
+
+int cxk_set_wide_spectrum(cxk_context* ctx, int mode) {
+  if (!ctx) return CXK_FAILURE;
+  CXK_DEMAND(!ctx->finalized, "cxk_set_wide_spectrum: the context is finalized (the choice is made by cxk_finalize)");
+  CXK_DEMAND(mode >= -1 && mode <= 1, "cxk_set_wide_spectrum: the mode is -1 (automatic), 0 (never) or 1 (every large-order matrix inequality)");
+  ctx->wide_spectrum = mode;
+  return CXK_SUCCESS;
+}
+int cxk_count_wide_spectrum(const cxk_context* ctx) {
+  if (!ctx || !ctx->finalized) return -1;
+  int k = 0;
+  for (const Group& g : ctx->groups)
+    if (g.ws_wide.n) k += (int)g.ids.size();
+  return k;
+}
 
 int cxk_set_streamed_quadratic(cxk_context* ctx, int mode) {
   if (!ctx) return CXK_FAILURE;

@@ -121,6 +121,10 @@ struct Group {
   bool literal = false;  // non-symmetric data: literal kernels only
   // orders beyond the LDS-resident kernels: HBM-resident matrices + MFMA GEMM pipeline
   bool large = false;
+  // a `large` group whose Lanczos runs take the chip-wide kernels (kernels_lmi_wide.hip.h, cxk_set_wide_spectrum):
+  // their per-constraint work space; empty: lmi_large_spectrum on one workgroup per constraint
+  DevBuf<double> ws_wide;
+  bool wide_reduce = false;  // ... with lmi_wide_reduce between pass and step (orders from kWideReduceMinOrder on)
   DevBuf<double> ws_main, ws_gf, ws_part;
   DevBuf<int> ws_piv;
   int splits = 1;
@@ -200,6 +204,9 @@ struct cxk_context {
   // cxk_set_sparse_soc: -2 the environment's CXK_SPARSE_SOC (else never), -1 by pattern, 0 never, 1 every second-order cone
   int sparse_soc = -2;
   double sparse_soc_setup_ms = 0;  // device time the last cxk_finalize spent on their constants (cxk_sparse_soc_setup_ms)
+  // cxk_set_wide_spectrum: -2 the environment's CXK_WIDE_SPECTRUM (else automatic), -1 automatic (large-order groups
+  // above LmiLargeSpectrumMaxOrder()), 0 never (such orders are refused), 1 every large-order group
+  int wide_spectrum = -2;
   std::vector<Group> groups;
   std::vector<int64_t> g_off, r_off;
   std::vector<unsigned char> owned;      // constraint i assembled/updated by this rank

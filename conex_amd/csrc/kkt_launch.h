@@ -72,6 +72,8 @@ struct FinalizeSwitches {
   bool no_packed_slack = false; // CXK_NO_PACKED_SLACK
   int gram_splits = 0;          // CXK_GRAM_SPLITS: K splits of the GEMM assembly (0: chosen by shape)
   int soc_stream_stages = 0;    // CXK_SOC_STREAM_STAGES=1 / 2: their assembly stops after that stage (timing runs: wrong results)
+  int wide_spectrum = -1;       // CXK_WIDE_SPECTRUM: -1 large-order LMI groups beyond the one-workgroup Lanczos run, 0 never, 1 all
+  int wide_reduce_min_order = -1;    // CXK_WIDE_REDUCE_MIN_ORDER instead of kWideReduceMinOrder (kernels_lmi_wide.hip.h; tests)
 };
 
 // ---- kkt_context.hip
@@ -83,6 +85,10 @@ int FlushDeferred(cxk_context* ctx, bool keep_scalars = false, bool keep_y = fal
 CXK_LOCAL hipError_t RaiseConeLdsLimits();
 // the largest order whose one-workgroup Lanczos run (lmi_large_spectrum, LmiLargeSpectrumLds) fits kLdsLimit
 CXK_LOCAL int LmiLargeSpectrumMaxOrder();
+// cxk_set_wide_spectrum's word, else the environment's (kernels_lmi_wide.hip.h: the Lanczos run spread over the chip)
+inline int WideSpectrumMode(const cxk_context* ctx, const FinalizeSwitches& sw) {
+  return ctx->wide_spectrum != -2 ? ctx->wide_spectrum : sw.wide_spectrum;
+}
 CXK_LOCAL int GroupConstraints(cxk_context* ctx, const FinalizeSwitches& sw);     // finalize: constraints of one shape form a group
 CXK_LOCAL int UploadGroup(cxk_context* ctx, Group& g, const FinalizeSwitches& sw);  // finalize: one group's data and work space
 bool ClockSample(cxk_context* ctx, int slot, hipEvent_t* e0, hipEvent_t* e1);

@@ -142,6 +142,8 @@ _SIGNATURES = {
     "cxk_set_sparse_soc": (C.c_int, [C.c_void_p, C.c_int]),
     "cxk_count_sparse_soc": (C.c_int, [C.c_void_p]),
     "cxk_sparse_soc_setup_ms": (C.c_double, [C.c_void_p]),
+    "cxk_set_wide_spectrum": (C.c_int, [C.c_void_p, C.c_int]),
+    "cxk_count_wide_spectrum": (C.c_int, [C.c_void_p]),
     "cxk_add_soc_csr": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_int_p, c_int_p, c_double_p, c_double_p, c_int_p]),
     "cxk_count_tiled_linear": (C.c_int, [C.c_void_p]),
     "cxk_fused_tree_timed_out": (C.c_int, [C.c_void_p]),
@@ -889,6 +891,16 @@ class KktContext:
     def count_sparse_soc(self):
         """Constraints this context owns that run on the sparse second-order-cone kernels."""
         return self.L.cxk_count_sparse_soc(self.h)
+
+    def set_wide_spectrum(self, mode=1):
+        """The Lanczos run of large-order matrix inequalities spread over the chip: 1 every large-order group, 0 none
+        (orders above 2549 are then refused), -1 only the orders the one-workgroup run cannot hold (before initialize;
+        default: CXK_WIDE_SPECTRUM in the environment, else -1)."""
+        self._check(self.L.cxk_set_wide_spectrum(self.h, int(mode)), "cxk_set_wide_spectrum")
+
+    def count_wide_spectrum(self):
+        """Constraints this context owns whose Lanczos runs take the chip-wide kernels."""
+        return self.L.cxk_count_wide_spectrum(self.h)
 
     def count_factored_lmi(self):
         """Constraints this context owns that were added by add_lmi_factored or add_hermitian_factored

@@ -216,6 +216,23 @@ double cxk_sparse_soc_setup_ms(const cxk_context* ctx);
 int cxk_add_soc_csr(cxk_context* ctx, int n, int m, const int* rowptr /* n + 2 */, const int* col, const double* val,
                     const double* c /* n + 1 */, const int* vars);
 
+/* Matrix inequalities of any order (kernels_lmi_large.hip.h, kernels_lmi_wide.hip.h).  A real symmetric LMI beyond
+ * order 1024 factors its Pade system with a panel kernel whose row count no workgroup bounds (lu_panel_tall; the
+ * orders up to 1024 keep their kernel and bits).  The two-sided Lanczos run behind PrepareStep and the eigenvalue
+ * query keeps its vectors in the LDS of one workgroup up to a real-representation order of 2549; the chip-wide run
+ * keeps them in HBM and spreads every matrix pass over 64 x 64 tiles: the same recurrence, start vector, break rule
+ * and outputs, other summation orders (fixed ones, no atomics: two runs give the same bits).
+ * cxk_set_wide_spectrum, before cxk_finalize: mode -1 (the default) a large-order group (order above 60) takes the
+ * chip-wide run only above order 2549, so that no shape that ran before changes its kernels or bits; 0 never: an order
+ * above 2549 is then refused by cxk_finalize, by name; 1 every large-order group.  Without a call: the environment's
+ * CXK_WIDE_SPECTRUM = -1 | 0 | 1.  cxk_finalize also refuses, by name, an order above 46340 (the kernels index the
+ * n x n entries with ints).  The factored routes (cxk_add_lmi_factored, cxk_add_hermitian_factored) keep their limits
+ * of 1024 and 2549.
+ * cxk_count_wide_spectrum: constraints this context owns whose groups take the chip-wide run (-1 before cxk_finalize; 0
+ * on a host-only context). */
+int cxk_set_wide_spectrum(cxk_context* ctx, int mode);
+int cxk_count_wide_spectrum(const cxk_context* ctx);
+
 /* Low-rank matrix inequalities given by their factors (kernels_lmi_factored.hip.h).  cxk_add_lmi_factored adds the
  * constraint of cxk_add_lmi (DenseLMIConstraint semantics, real symmetric) with
  *   A_i = sum_k sigma_k f_k f_k',  k = rank_ptr[i] .. rank_ptr[i + 1] - 1,
