@@ -1,0 +1,255 @@
+// Quadratic cones on their two routes (kQuadLds, kQuadStreamed): the views, the stages of cxk_finalize and every
+// launch.  Owns the kernels of kernels_quad / _quad_stream; the slack of the streamed route is the second-order
+// cones' kernel (cone_soc.hip: LaunchSocStreamSlack), the scaling point's identity the vector cones' (cone_linear.hip).
+#include "cone_units.h"
+#include "kernels_gemm.hip.h"
+#include "kernels_quad.hip.h"
+#include "kernels_quad_stream.hip.h"
+
+namespace cxk_host {
+
+// ---- The views the kernels take of a group, each beside the stage of cxk_finalize that allocates what it lays out,
+// so that a layout and its size are read together.  What those stages call further down:
+int QuadStreamConstants(cxk_context* ctx, Group& g);
+
+QuadGroup MakeQuad(Group& g) {
+  QuadGroup d;
+  d.n = g.n;
+  d.m = g.m;
+  d.count = static_cast<int>(g.ids.size());
+  d.A = g.A.p;
+  d.c = g.C.p;
+  d.Q = g.has_q ? g.qQ.p : nullptr;
+  d.Agram = g.qGram.p;
+  d.W = g.W.p;
+  d.D = g.T1.p;
+  d.S = g.qS.p;
+  d.ids = g.dids.p;
+  return d;
+}
+// A_gram = A1' (Q A1) of a group of quadratic cones on the LDS route, made once on the host
+// (QuadraticConstraintBase::Initialize, quadratic_cone_constraint.cc:216-219), Q, and the state S.
+int UploadQuadGram(cxk_context* ctx, Group& g) {
+  const size_t cnt = g.ids.size();
+  const int n = g.n, m = g.m, len = n + 1;
+  std::vector<double> hQ(g.has_q ? (size_t)n * n * cnt : 0), hG((size_t)m * m * cnt, 0.0), qa((size_t)n);
+  for (size_t k = 0; k < cnt; k++) {
+    const ConstraintRec& c = ctx->cons[g.ids[k]];
+    if (g.has_q) std::copy(c.Q.begin(), c.Q.end(), hQ.begin() + k * (size_t)n * n);
+    for (int j = 0; j < m; j++) {
+      const double* aj = c.A.data() + (size_t)j * len + 1;
+      for (int i = 0; i < n; i++) {
+        double s2 = g.has_q ? 0.0 : aj[i];
+        if (g.has_q)
+          for (int q2 = 0; q2 < n; q2++) s2 += c.Q[(size_t)q2 * n + i] * aj[q2];
+        qa[(size_t)i] = s2;
+      }
+      for (int i = 0; i < m; i++) {
+        const double* ai = c.A.data() + (size_t)i * len + 1;
+        double s2 = 0;
+        for (int q2 = 0; q2 < n; q2++) s2 += ai[q2] * qa[(size_t)q2];
+        hG[k * (size_t)m * m + (size_t)j * m + i] = s2;
+      }
+    }
+  }
+  CXK_TRY(g.qQ.upload(hQ));
+  CXK_TRY(g.qGram.upload(hG));
+  CXK_TRY(g.qS.alloc((size_t)len * cnt));
+  return CXK_SUCCESS;
+}
+QuadStreamGroup MakeQuadStream(Group& g) {
+  QuadStreamGroup d;
+  const size_t cnt = g.ids.size(), n = (size_t)g.n, m = (size_t)g.m;
+  d.n = g.n;
+  d.m = g.m;
+  d.count = static_cast<int>(cnt);
+  d.splits = g.splits;
+  d.A = g.A.p;
+  d.c = g.C.p;
+  d.Q = g.has_q ? g.qQ.p : nullptr;
+  d.Agram = g.qGram.p;
+  d.W = g.W.p;
+  d.D = g.T1.p;
+  d.S = g.qS.p;
+  d.ids = g.dids.p;
+  d.part = g.ws_part.p;
+  double* p = g.st_vec.p;  // (the layout UploadQuadStream sizes: QuadStreamVecDoubles)
+  d.qc1 = p;
+  d.qw = (p += cnt * n);
+  d.dv = (p += cnt * n);
+  d.qd = (p += cnt * n);
+  d.ms = (p += cnt * n);
+  d.v = (p += cnt * (n + 1));
+  d.u = (p += cnt * m);
+  d.scal = (p += cnt * m);
+  d.cqc = (p += cnt * 8);
+  return d;
+}
+size_t QuadStreamVecDoubles(size_t cnt, size_t n, size_t m) { return cnt * (4 * n + (n + 1) + 2 * m + 8 + 1); }
+// A group of streamed quadratic cones: Q as it is, the work space, and the constants (Q c1, c1' Q c1, A_gram) on the
+// device (QuadStreamConstants).
+int UploadQuadStream(cxk_context* ctx, Group& g, const FinalizeSwitches& sw) {
+  const size_t cnt = g.ids.size();
+  const size_t n = (size_t)g.n, m = (size_t)g.m, tiles = (n + kQuadStreamRowTile - 1) / kQuadStreamRowTile;
+  g.splits = g.has_q ? QuadStreamSplits(g.n, (long long)cnt) : 1;
+  if (g.has_q && sw.gram_splits > 0) g.splits = sw.gram_splits;  // (comparison runs)
+  CXK_DEMAND(cnt * std::max<size_t>(std::max<size_t>(m, (m * m + kQuadStreamBlock - 1) / kQuadStreamBlock),
+                                    std::max<size_t>(tiles * (size_t)g.splits, (n + 1 + kSocStreamRowTile - 1) / kSocStreamRowTile)) <=
+                 (size_t)INT_MAX,
+             "a group of streamed quadratic cones with more than 2^31 columns, row tiles or blocks is not supported");
+  std::vector<double> hQ(g.has_q ? n * n * cnt : 0);
+  if (g.has_q)
+    for (size_t k = 0; k < cnt; k++) std::copy(ctx->cons[g.ids[k]].Q.begin(), ctx->cons[g.ids[k]].Q.end(), hQ.begin() + k * n * n);
+  CXK_TRY(g.qQ.upload(hQ));
+  CXK_TRY(g.qGram.alloc(m * m * cnt));
+  CXK_TRY(g.qS.alloc((n + 1) * cnt));
+  CXK_TRY(g.st_vec.alloc(QuadStreamVecDoubles(cnt, n, m)));
+  CXK_TRY(g.ws_part.alloc(g.has_q ? cnt * (size_t)g.splits * 2 * n : 0));
+  return QuadStreamConstants(ctx, g);
+}
+// soc_stream_slack serves the streamed quadratic cone as it is (same layout, same formula): what it reads of the group.
+SocStreamGroup QuadStreamSlackView(Group& g, const QuadStreamGroup& d) {
+  SocStreamGroup s{};
+  s.v = MakeVec(g);
+  s.ms = d.ms;
+  return s;
+}
+
+// Kernels of this unit that may be launched with more than the default 64 KB of dynamic LDS.
+hipError_t RaiseQuadLdsLimits() {
+  return RaiseDynamicLds({
+    reinterpret_cast<const void*>(&quad_schur),
+    reinterpret_cast<const void*>(&quad_prepare<0>),
+    reinterpret_cast<const void*>(&quad_prepare<1>),
+    reinterpret_cast<const void*>(&quad_take_step),
+  });
+}
+
+// One pass over Q of a group of streamed quadratic cones: out_r = Q x_r for the R vectors of `x` (partials per
+// column split; QuadStreamQx adds them).  Nothing to do where Q is the identity.
+template <int R>
+hipError_t LaunchQuadStreamQmv(const QuadStreamGroup& d, const QuadStreamVecs& x, hipStream_t st) {
+  if (!d.Q) return hipSuccess;
+  const int tiles = (d.n + kQuadStreamRowTile - 1) / kQuadStreamRowTile;
+  quad_stream_qmv<R><<<(unsigned)((size_t)d.count * tiles * d.splits), kQuadStreamBlock, 0, st>>>(d, x, tiles);
+  return hipGetLastError();
+}
+QuadStreamVecs QuadStreamOne(const double* p, size_t stride) {
+  QuadStreamVecs x;
+  x.p[0] = x.p[1] = p;
+  x.stride[0] = x.stride[1] = stride;
+  return x;
+}
+
+// The Schur complement of a group of quadratic cones on the LDS route: one workgroup per cone.
+void LaunchQuadLdsSchur(Group& g, const Arena& ar, hipStream_t st) {
+  quad_schur<<<(int)g.ids.size(), 64, QuadSchurLds(g.n, g.m), st>>>(MakeQuad(g), ar);
+}
+
+// The Schur complement of a group of streamed quadratic cones: Q w1, the scalars, the columns, the block.
+hipError_t LaunchQuadStreamSchur(Group& g, const Arena& ar, hipStream_t st) {
+  const QuadStreamGroup d = MakeQuadStream(g);
+  const int cnt = d.count, m = d.m;
+  hipError_t e = LaunchQuadStreamQmv<1>(d, QuadStreamOne(d.W + 1, (size_t)d.n + 1), st);
+  if (e != hipSuccess) return e;
+  quad_stream_schur_vectors<<<cnt, kQuadStreamBlock, 0, st>>>(d);
+  if (m > 0) quad_stream_schur_columns<<<(unsigned)((size_t)cnt * m), kQuadStreamBlock, 0, st>>>(d);
+  const int blocks = (int)std::max<size_t>(1, ((size_t)m * m + kQuadStreamBlock - 1) / kQuadStreamBlock);
+  quad_stream_schur_finish<<<(unsigned)((size_t)cnt * blocks), kQuadStreamBlock, 0, st>>>(d, ar, blocks);
+  return hipGetLastError();
+}
+
+// The constants of a group of streamed quadratic cones, once at cxk_finalize, on the device: Qc1 = Q c1 and
+// c1' Q c1 by the pass kernel, A_gram = A1' (Q A1) as two batched GEMMs (A1 = A + 1 with leading dimension
+// n + 1; T = Q A1 in a buffer that lives for this call only).
+int QuadStreamConstants(cxk_context* ctx, Group& g) {
+  const QuadStreamGroup d = MakeQuadStream(g);
+  const int cnt = d.count, n = d.n, m = d.m, len = n + 1;
+  CXK_TRY(LaunchQuadStreamQmv<1>(d, QuadStreamOne(d.c + 1, (size_t)len), ctx->stream));
+  quad_stream_constants<<<cnt, kQuadStreamBlock, 0, ctx->stream>>>(d);
+  CXK_TRY(hipGetLastError());
+  DevBuf<double> T;
+  if (g.has_q && m > 0) CXK_TRY(T.alloc((size_t)cnt * n * m));
+  constexpr int kMaxBatch = 65535;  // gridDim.z
+  for (int b0 = 0; b0 < cnt && m > 0; b0 += kMaxBatch) {
+    const int nb = std::min(kMaxBatch, cnt - b0);
+    const double* A1 = g.A.p + (size_t)b0 * len * m + 1;
+    GemmArgs a{};
+    a.inner = 1;
+    a.alpha = 1.0;
+    a.beta = 0.0;
+    a.splits = 1;
+    if (g.has_q) {  // T = Q A1
+      a.M = n;
+      a.N = m;
+      a.K = n;
+      a.A = g.qQ.p + (size_t)b0 * n * n;
+      a.lda = n;
+      a.sA1 = (int64_t)n * n;
+      a.B = A1;
+      a.ldb = len;
+      a.sB1 = (int64_t)len * m;
+      a.C = T.p + (size_t)b0 * n * m;
+      a.ldc = n;
+      a.sC1 = (int64_t)n * m;
+      CXK_TRY(LaunchGemm(a, false, false, nb, ctx->stream));
+    }
+    // A_gram = A1' T (A1' A1 where Q is the identity)
+    a.M = a.N = m;
+    a.K = n;
+    a.A = A1;
+    a.lda = len;
+    a.sA1 = (int64_t)len * m;
+    a.B = g.has_q ? T.p + (size_t)b0 * n * m : A1;
+    a.ldb = g.has_q ? n : len;
+    a.sB1 = g.has_q ? (int64_t)n * m : (int64_t)len * m;
+    a.C = g.qGram.p + (size_t)b0 * m * m;
+    a.ldc = m;
+    a.sC1 = (int64_t)m * m;
+    CXK_TRY(LaunchGemm(a, true, false, nb, ctx->stream));
+  }
+  CXK_TRY(hipStreamSynchronize(ctx->stream));  // (T is released on return)
+  return CXK_SUCCESS;
+}
+
+// PrepareStep (MODE 0) or the eigenvalue query (MODE 1) of one group.
+namespace {
+template <int MODE>
+int QuadPrepare(cxk_context* ctx, Group& g, const StepArgs& sa) {
+  const int cnt = (int)g.ids.size();
+  switch (g.route) {
+    case ConeRoute::kQuadLds: quad_prepare<MODE><<<cnt, 64, QuadPrepareLds(g.n, g.m), ctx->stream>>>(MakeQuad(g), sa); break;
+    case ConeRoute::kQuadStreamed: {
+      const QuadStreamGroup d = MakeQuadStream(g);
+      LaunchSocStreamSlack(QuadStreamSlackView(g, d), sa, ctx->stream);
+      QuadStreamVecs x;  // Q [w1, ms1] in one pass
+      x.p[0] = d.W + 1;
+      x.p[1] = d.ms + 1;
+      x.stride[0] = x.stride[1] = (size_t)g.n + 1;
+      CXK_TRY(LaunchQuadStreamQmv<2>(d, x, ctx->stream));
+      quad_stream_prepare_mid<MODE><<<cnt, kQuadStreamBlock, 0, ctx->stream>>>(d, sa);
+      CXK_TRY(LaunchQuadStreamQmv<1>(d, QuadStreamOne(d.dv, (size_t)g.n), ctx->stream));
+      quad_stream_prepare_finish<MODE><<<cnt, kQuadStreamBlock, 0, ctx->stream>>>(d, sa);
+      break;
+    }
+    default: CXK_DEMAND(false, "internal error: not a route of the quadratic cones");
+  }
+  return CXK_SUCCESS;
+}
+}  // namespace
+
+int LaunchQuadPrepare(cxk_context* ctx, Group& g, int mode, const StepArgs& sa) {
+  return mode == 0 ? QuadPrepare<0>(ctx, g, sa) : QuadPrepare<1>(ctx, g, sa);
+}
+
+int LaunchQuadTakeStep(cxk_context* ctx, Group& g, const StepArgs& sa) {
+  const int cnt = (int)g.ids.size();
+  switch (g.route) {
+    case ConeRoute::kQuadLds: quad_take_step<<<cnt, 64, QuadTakeLds(g.n), ctx->stream>>>(MakeQuad(g), sa); break;
+    case ConeRoute::kQuadStreamed: quad_stream_take_step<<<cnt, kQuadStreamBlock, 0, ctx->stream>>>(MakeQuadStream(g), sa); break;
+    default: CXK_DEMAND(false, "internal error: not a route of the quadratic cones");
+  }
+  return CXK_SUCCESS;
+}
+
+}  // namespace cxk_host

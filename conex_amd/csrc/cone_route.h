@@ -5,7 +5,8 @@
 // LDS-resident kernel, and the thresholds of the automatic modes.
 //
 // GroupConstraints (kkt_cone_launch.hip) measures a constraint, asks Choose, and raises the refusal or stores the
-// route; every stage of the cxk_* path then switches on Group::route with a case for every enumerator.
+// route; every stage of the cxk_* path then switches on Group::route with a case for every enumerator, and each case
+// calls the unit that owns the route's kernels (cone_units.h: cone_linear / _soc / _quad / _lmi .hip).
 #pragma once
 #include <climits>
 #include <cstddef>
@@ -19,10 +20,10 @@ constexpr size_t kLdsLimit = 160 * 1024 - 512;
 
 // One enumerator per set of kernels.
 enum class ConeRoute {
-  kLinearLds,     // one workgroup per block (kernels_cone.hip.h)
+  kLinearLds,     // one workgroup per block (kernels_linear.hip.h)
   kLinearTiled,   // kernels_linear_tiled.hip.h
   kLinearSparse,  // from the nonzeros (kernels_linear_sparse.hip.h)
-  kSocLds,        // one wavefront per cone, its image in LDS (kernels_cone.hip.h)
+  kSocLds,        // one wavefront per cone, its image in LDS (kernels_soc.hip.h)
   kSocStreamed,   // held in HBM (kernels_soc_stream.hip.h)
   kSocSparse,     // from the nonzeros (kernels_soc_sparse.hip.h)
   kQuadLds,       // one workgroup per cone (kernels_quad.hip.h)

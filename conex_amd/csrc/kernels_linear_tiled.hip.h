@@ -1,6 +1,6 @@
 // Linear-inequality blocks on the tiled route (cxk_set_tiled_linear): the block's work is spread over the chip
 // instead of sitting on the one workgroup of linear_schur / linear_prepare / linear_line_search
-// (kernels_cone.hip.h; reference linear_constraint.cc:48-205).  The O(rows m) passes run on a grid of columns
+// (kernels_linear.hip.h; reference linear_constraint.cc:48-205).  The O(rows m) passes run on a grid of columns
 // (assembly) or of row tiles (slack, line search), and the one dense contraction, G = WA^T WA with
 // WA = diag(w) A, on the batched fp64 MFMA GEMM (gemm_mfma.hip).  linear_take_step and vec_set_identity are
 // grid-wide already and serve both routes.
@@ -14,7 +14,7 @@
 // Work space per group (LinTiledGroup): WA (rows x m per block), the GEMM's lower triangle Gf (m x m per block),
 // four doubles per row tile.
 #pragma once
-#include "kernels_soc_stream.hip.h"  // SocStreamSplits: the split rule of the Gram product is the streamed cones'
+#include "kernels_linear.hip.h"  // (the split rule of the Gram product is the streamed cones': SocStreamSplits, cone_types.h)
 
 namespace cxk {
 

@@ -17,7 +17,7 @@
 // rounding (tests/test_gpu_parity.py, <= 1e-11).
 #pragma once
 #include "dense_elim.hip.h"  // DppOperandFence
-#include "kernels_cone.hip.h"
+#include "cone_tail.hip.h"  // StepTail's device side: PrepareTailBlock, DirectionBlock, AgentStore
 #include "kernels_lmi.hip.h"
 
 namespace cxk {

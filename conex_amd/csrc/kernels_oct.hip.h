@@ -13,7 +13,8 @@
 // entries of 8 n multiply-adds each).  These cones are a few hundred doubles: nothing here is priced
 // against a roofline.
 #pragma once
-#include "kernels_lmi.hip.h"
+#include "device_utils.h"
+#include "lmi_types.h"
 
 namespace cxk {
 

@@ -11,7 +11,8 @@
 // One 64-thread workgroup per cone; the maps run on one thread in the order the oracle restates
 // (these cones are a handful of doubles each: an epigraph of a stage cost in solver_failures.cc).
 #pragma once
-#include "kernels_lmi.hip.h"
+#include "device_utils.h"
+#include "lmi_types.h"
 
 namespace cxk {
 

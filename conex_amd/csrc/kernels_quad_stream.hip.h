@@ -20,7 +20,6 @@
 // TakeStep 0: Q(step f d1) = step f (Q d1), and Q d1 is what PrepareStep's second pass left behind.
 #pragma once
 #include "kernels_quad.hip.h"
-#include "kernels_soc_stream.hip.h"
 
 namespace cxk {
 

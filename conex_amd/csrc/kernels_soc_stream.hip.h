@@ -1,6 +1,6 @@
 // Second-order cones whose data does not fit LDS (cxk_set_streamed_cones): the cone stays in HBM and
 // every stage is a few launches ordered by the stream alone.  Semantics are those of soc_schur /
-// soc_prepare / soc_take_step (kernels_cone.hip.h; reference soc_constraint.cc:14-191, 200-303); what
+// soc_prepare / soc_take_step (kernels_soc.hip.h; reference soc_constraint.cc:14-191, 200-303); what
 // differs is who does the work: the O(len) maps run on one 256-thread workgroup per cone that strides
 // over the cone, the O(len m) passes on a grid of column / row tiles, and the one dense contraction,
 // G = 2 WA^T WA, on the batched fp64 MFMA GEMM (gemm_mfma.hip).
@@ -11,34 +11,14 @@
 //
 // Work space per cone (SocStreamGroup): WA (len x m), s = w^{1/2}, wc = Q(s) c, ms (each len), det(s).
 #pragma once
-#include "kernels_cone.hip.h"
+#include "kernels_soc.hip.h"
 
 namespace cxk {
 
+// (SocStreamGroup, kSocStreamRowTile and the split rule of the Gram product, SocStreamSplits / kSocStreamMinSplitK, are
+// cone_types.h's: the units of the quadratic cones and the linear blocks read them too)
 constexpr int kSocStreamBlock = 256;     // threads of every kernel here
-constexpr int kSocStreamRowTile = 256;   // rows of the slack one workgroup forms (one per thread)
 constexpr int kSocStreamYChunk = 2048;   // entries of y staged in LDS at a time (16 KB)
-constexpr int kSocStreamMinSplitK = 1024;  // the Gram product is split along len only into pieces at least this long
-
-struct SocStreamGroup {
-  VecGroup v;    // len, m, count, A, c, W, T1 (d), ids as the staged kernels read them
-  double* WA;    // count x (len x m)   Q(s) a_i, column by column
-  double* s;     // count x len         w^{1/2}
-  double* wc;    // count x len         Q(s) c
-  double* ms;    // count x len         minus the slack; TakeStep keeps exp(d) here
-  double* dets;  // count               det(s)
-  double* Gf;    // count x (m x m)     2 WA^T WA, lower triangle (the GEMM's output)
-};
-
-// K splits of the Gram product of `count` cones: enough workgroups to fill the chip, none shorter than
-// kSocStreamMinSplitK (below that the ordered reduction of the partials costs more than it hides).
-__host__ __device__ inline int SocStreamSplits(int len, int m, long long count) {
-  const long long tiles = (long long)((m + 63) / 64) * ((m + 63) / 64) * (count > 0 ? count : 1);
-  const long long by_len = len / kSocStreamMinSplitK;
-  const long long by_fill = (512 + tiles - 1) / tiles;
-  const long long s = by_len < by_fill ? by_len : by_fill;
-  return s < 1 ? 1 : (int)s;
-}
 
 // s = w^{1/2} of one cone by the whole workgroup (SocSpectral's expressions): s written to `s`, returns
 // det(s) = s_0^2 - |s_1|^2 and (optionally) <s, other> to every thread.

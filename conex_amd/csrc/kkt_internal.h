@@ -1,6 +1,7 @@
 // Shared by the translation units of the cxk_* path: the context, its host-side types and the
 // functions that cross between them.  kkt_plans.hip builds the symbolic plans (tree structure,
-// partition, index tables: host code only); the launches and the C-ABI are the units kkt_launch.h lists.
+// partition, index tables: host code only); the launches and the C-ABI are the units kkt_launch.h lists (the per-cone
+// stages and the units of the cone families behind them: cone_units.h).
 // Which kernels a constraint runs on is ONE field of its record and of its group (ConeRoute, chosen by the pure
 // function of cone_route.h); what is a property of the data (symmetric, csr_only, factored, literal, has_q) stays a flag.
 #pragma once
@@ -434,7 +435,7 @@ struct cxk_context {
   double* pin_y = nullptr;  // pinned staging of y for cxk_get_y
   long long seq = 0, mb_seen = -1, factor_seq = -1, scal_seq = -1;
   // cxk_step_scalars_async leaves its launch to the tail workgroup of the PrepareStep that normally
-  // follows (StepTail, kernels_cone.hip.h); any other entry point runs it first (FlushDeferred)
+  // follows (StepTail, cone_types.h / cone_tail.hip.h); any other entry point runs it first (FlushDeferred)
   bool scal_deferred = false;
   bool no_step_tail = false;  // CXK_NO_STEP_TAIL / CXK_PREPARE_LDS in the environment at cxk_create
   bool no_device_mu = false;  // CXK_NO_DEVICE_MU likewise

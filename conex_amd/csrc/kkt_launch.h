@@ -1,7 +1,11 @@
 // What the translation units of the cxk_* path call in one another.  Every kernel is compiled in
 // exactly one unit; a unit that needs a kernel it does not own goes through a host function of the owner:
 //   kkt_cone_launch.hip  the per-cone stages (Schur, PrepareStep, eigenvalue query, TakeStep), each an exhaustive
-//                        switch over Group::route (cone_route.h); the per-group stages of cxk_finalize; the mailbox
+//                        switch over Group::route (cone_route.h); route choice and grouping; the mailbox, the step tail
+//   cone_linear.hip      the linear blocks' views, finalize stages and launches (what the arms of those switches call:
+//   cone_soc.hip         the second-order cones'                                 cone_units.h declares it)
+//   cone_quad.hip        the quadratic cones'
+//   cone_lmi.hip         the matrix inequalities', and the list of LMI kernel instances with its choosers
 //   kkt_tree_launch.hip  assembly gather, right-hand sides, the elimination-tree sweeps, the exchange kernels
 //   kkt_shard.hip        sharded sweeps, collectives, communicator and exchange entry points
 //   kkt_qr.hip           the host QR mode
@@ -11,7 +15,7 @@
 #include "kkt_internal.h"
 
 namespace cxk {
-struct MuRuleArgs;  // kernels_cone.hip.h
+struct MuRuleArgs;  // cone_types.h
 }
 
 namespace cxk_host {
@@ -81,7 +85,7 @@ int GridFor(size_t work, int block);
 int CheckReady(cxk_context* ctx);
 int FlushDeferred(cxk_context* ctx, bool keep_scalars = false, bool keep_y = false);
 
-// ---- kkt_cone_launch.hip
+// ---- kkt_cone_launch.hip (LmiLargeSpectrumMaxOrder: cone_lmi.hip)
 CXK_LOCAL hipError_t RaiseConeLdsLimits();
 // the largest order whose one-workgroup Lanczos run (lmi_large_spectrum, LmiLargeSpectrumLds) fits kLdsLimit
 CXK_LOCAL int LmiLargeSpectrumMaxOrder();

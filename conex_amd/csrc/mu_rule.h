@@ -1,5 +1,5 @@
 // The barrier-parameter rule of conex::Solve, ONE source for the host loop (program.cc) and for the
-// device (the tail workgroup of the eigenvalue query, kernels_cone.hip.h): compiled twice, the same
+// device (the tail workgroup of the eigenvalue query, cone_tail.hip.h): compiled twice, the same
 // IEEE operations in the same order (no contraction: -ffp-contract=off on the device, no fused
 // multiply-add on the host's baseline ISA), so both sides get the same bits.
 //   conex/divergence.cc:17-110        DivergenceUpperBoundInverse and helpers

@@ -1,5 +1,5 @@
 """The kernels of the cones that are not matrices -- linear, second-order, quadratic, octonion, constant
-block, line search (kernels_cone / _quad / _oct .hip.h) -- at their launch edges, against the
+block, line search (kernels_linear / _soc / _quad / _oct / _stage .hip.h) -- at their launch edges, against the
 extended-precision reference of cone_reference.py.
 
 Each row of ROWS is a handful of equal cones in a chain of cliques.  It runs at three scaling points

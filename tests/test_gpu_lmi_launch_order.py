@@ -1,5 +1,5 @@
 """lmi_schur_mfma walks each workgroup's constraints first to last in one launch of a group and last to
-first in the next (kkt_cone_launch.hip, LaunchSchur; CXK_LMI_ORDER=forward keeps the one order).  The order
+first in the next (cone_lmi.hip, LaunchLmiDenseSchur; CXK_LMI_ORDER=forward keeps the one order).  The order
 may change nothing but the time: every constraint's G, AW, AQc and scalars are the same bits in both.
 
 Each case runs four consecutive assemblies on one context (orders forward, backward, forward, backward), at a

@@ -1,4 +1,4 @@
-"""The tail workgroup of the PrepareStep / eigenvalue-query launch (StepTail, kernels_cone.hip.h).
+"""The tail workgroup of the PrepareStep / eigenvalue-query launch (StepTail, cone_tail.hip.h).
 
 When every constraint of a program goes through lmi_prepare_rows on one GPU, the reduction of the
 per-constraint step outputs (cone_program.cc:417-418 reads their sum and maximum), the by / cx

@@ -1,5 +1,5 @@
 """csrc/mu_rule.h -- the barrier-parameter rule that the host loop (program.cc) and the tail workgroup
-of the eigenvalue query (kernels_cone.hip.h) both compile -- against the oracle's restatement of
+of the eigenvalue query (cone_tail.hip.h) both compile -- against the oracle's restatement of
 divergence.cc / cone_program.cc:166-224, :386-392, on the CPU: the header is built into a small
 shared object with g++ and driven over random and hand-made inputs that reach every branch
 (bound branch of either end, MinimizeNormInf, the quadratic fall-back, no selection -> half the
