@@ -198,7 +198,7 @@ int UploadLmiFactored(cxk_context* ctx, Group& g) {
 
 // What Choose (cone_route.h) asks about an LMI added with its dense matrices.
 void MeasureLmi(const ConstraintRec& c, ConeShape* s) {
-  double nnz = 0;
+  double nnz = c.csr_only ? (double)c.e_ptr[c.m] : 0;  // (held by its nonzeros: A is empty)
   for (double v : c.A) nnz += (v != 0.0);
   s->mfma_supports = LmiMfmaSupports(c.n, c.m, c.herm_d);
   s->sparse_pays = LmiSparsePays(c.n, c.m, nnz, LmiLdsResident(c.n, c.m), s->mfma_supports);
@@ -308,9 +308,15 @@ const char* const kLmiKernelNames[kLmiKernelCount] = {
 #undef CXK_LMI_NAME
 };
 
+// An instance that runs only where it was asked for (cxk_set_sparse_affine, cxk_add_lmi_coo) and is no row of the
+// kernel matrix that [0, cxk_lmi_kernel_count()) lists: its code lies behind that range (kLmiKernelCount itself stays
+// "not an instance"), and cxk_lmi_kernel_name knows it.  lmi_schur_sparse behind lmi_affine_wc / _x / _scalars.
+constexpr LmiKernel kSchurSparseAffine = (LmiKernel)(kLmiKernelCount + 1);
+constexpr const char* kSchurSparseAffineName = "lmi_schur_sparse hbm sparse-C";
+
 bool IsSchurMfma(LmiKernel k) { return k >= kSchurMfma8 && k <= kSchurMfma24FoldedSingle; }
 bool IsSchurGemm(LmiKernel k) { return k >= kSchurGemm && k <= kSchurGemmFoldedLargeSplit; }
-bool IsSchurSparse(LmiKernel k) { return k >= kSchurSparseSmall && k <= kSchurSparseDenseC; }
+bool IsSchurSparse(LmiKernel k) { return (k >= kSchurSparseSmall && k <= kSchurSparseDenseC) || k == kSchurSparseAffine; }
 bool IsPrepareRows(LmiKernel k) {
   return (k >= kPrepareRowsPacked && k <= kPrepareRowsEven) || (k >= kQueryRowsPacked && k <= kQueryRowsEven);
 }
@@ -320,6 +326,7 @@ LmiKernel LmiSchurKernel(const Group& g) {
   // not one of the instances: a code outside the reported range, which no Is*() test accepts and
   // cxk_lmi_kernel_name has no name for (LaunchSchur switches on the route first, cxk_lmi_kernels refuses the constraint)
   if (g.route == ConeRoute::kLmiFactored) return kLmiKernelCount;
+  if (g.route == ConeRoute::kLmiSparse && g.sp_affine) return kSchurSparseAffine;
   if (g.route == ConeRoute::kLmiSparse) return (LmiKernel)((g.sp_small ? kSchurSparseSmall : kSchurSparse) + (g.sp_cdense ? 1 : 0));
   if (g.assembly == LmiAssembly::kGemm) {  // (fold and split counts as LmiLargeSchur reads them: MakeLargeWs, LmiFoldedSplits)
     const bool fold = g.Aleft.n != 0;
@@ -380,47 +387,142 @@ hipError_t RaiseLmiLdsLimits() {
   });
 }
 
-// Entry lists of a sparse LMI group (kernels_lmi_sparse.hip.h) from the dense host matrices.
+// The m + 1 entry lists of a constraint on the sparse route, both triangles, by column then row: as cxk_add_lmi_coo
+// left them, or read off the dense matrices in that order (list m is C; ptr has m + 2 entries).
+struct LmiLists {
+  const int *ptr = nullptr, *rc = nullptr;
+  const double* val = nullptr;
+  std::vector<int> own_ptr, own_rc;
+  std::vector<double> own_val;
+  bool too_many = false;  // 2^31 nonzeros and more: no int points at them
+};
+static void ReadLmiLists(const ConstraintRec& c, LmiLists* L) {
+  if (c.csr_only) {
+    L->ptr = c.e_ptr.data(), L->rc = c.e_rc.data(), L->val = c.e_val.data();
+    return;
+  }
+  const int n = c.n, m = c.m;
+  const size_t nn = (size_t)n * n;
+  L->own_ptr.assign((size_t)m + 2, 0);
+  for (int i = 0; i <= m; i++) {
+    const double* M = i < m ? c.A.data() + (size_t)i * nn : c.C.data();
+    for (int col = 0; col < n; col++)
+      for (int row = 0; row < n; row++) {
+        const double v = M[row + (size_t)col * n];
+        if (v != 0.0) {
+          L->own_rc.push_back(row | (col << 16));
+          L->own_val.push_back(v);
+        }
+      }
+    L->too_many = L->too_many || L->own_val.size() > (size_t)INT_MAX;
+    L->own_ptr[(size_t)i + 1] = L->too_many ? L->own_ptr[i] : (int)L->own_val.size();
+  }
+  L->ptr = L->own_ptr.data(), L->rc = L->own_rc.data(), L->val = L->own_val.data();
+}
+
+// GroupConstraints: a constraint on kLmiSparse takes its affine term by C's nonzeros -- beyond the LDS-resident orders,
+// with more than 64 of them (fewer ride in the pair sums as list m), when the mode says so.
+bool LmiTakesSparseAffine(const ConstraintRec& c, int mode, double min_ratio) {
+  if (mode == 0 || LmiLdsResident(c.n, c.m)) return false;
+  size_t nnz_c = 0;
+  if (c.csr_only)
+    nnz_c = (size_t)(c.e_ptr[c.m + 1] - c.e_ptr[c.m]);
+  else
+    for (double v : c.C) nnz_c += (v != 0.0);
+  if (nnz_c <= (size_t)kSparseAffineMinNnz) return false;
+  if (mode == 1) return true;
+  LmiLists L;
+  ReadLmiLists(c, &L);
+  if (L.too_many) return false;
+  std::vector<int> pos(L.rc, L.rc + L.ptr[c.m + 1]);
+  std::sort(pos.begin(), pos.end());
+  const size_t npos = (size_t)(std::unique(pos.begin(), pos.end()) - pos.begin());
+  return LmiSparseAffinePays(c.n, (double)nnz_c, (double)npos, min_ratio);
+}
+
+// What the kernels of the affine term by its nonzeros read (kernels_lmi_sparse.hip.h: SparseAffine): every member's C
+// by columns, the positions P, and the slot there of every entry of the A_i and of C.  `erc` holds the group's A lists.
+static int UploadSparseAffine(cxk_context* ctx, Group& g, const std::vector<LmiLists>& lists, const std::vector<int>& eptr) {
+  const size_t cnt = g.ids.size();
+  const int n = g.n, m = g.m, m1 = m + 1;
+  CXK_DEMAND(cnt <= 65535, "a group of more than 65535 equal-shaped sparse LMIs with an affine term by its nonzeros is not supported");
+  std::vector<int> cptr(cnt * ((size_t)n + 1), 0), crc, cslot, pptr(cnt + 1, 0), prc, eslot((size_t)eptr[cnt * m1], 0);
+  std::vector<double> cval;
+  g.sa_pmax = 0;
+  for (size_t k = 0; k < cnt; k++) {
+    const LmiLists& L = lists[k];
+    std::vector<int> pos(L.rc, L.rc + L.ptr[m1]);
+    std::sort(pos.begin(), pos.end());
+    pos.erase(std::unique(pos.begin(), pos.end()), pos.end());
+    auto slot = [&pos](int rc) { return (int)(std::lower_bound(pos.begin(), pos.end(), rc) - pos.begin()); };
+    for (int e = 0; e < L.ptr[m]; e++) eslot[(size_t)eptr[k * m1] + e] = slot(L.rc[e]);
+    int* cp = cptr.data() + k * ((size_t)n + 1);
+    int col = 0;
+    cp[0] = (int)crc.size();
+    for (int e = L.ptr[m]; e < L.ptr[m1]; e++) {  // (by column then row already)
+      for (; col < (L.rc[e] >> 16); col++) cp[col + 1] = (int)crc.size();
+      crc.push_back(L.rc[e]);
+      cval.push_back(L.val[e]);
+      cslot.push_back(slot(L.rc[e]));
+    }
+    for (; col < n; col++) cp[col + 1] = (int)crc.size();
+    prc.insert(prc.end(), pos.begin(), pos.end());
+    CXK_DEMAND(prc.size() < ((size_t)1 << 31) && crc.size() < ((size_t)1 << 31), "sparse LMI group: too many nonzeros");
+    pptr[k + 1] = (int)prc.size();
+    g.sa_pmax = std::max(g.sa_pmax, (int)pos.size());
+  }
+  CXK_TRY(g.sa_cptr.upload(cptr));
+  CXK_TRY(g.sa_crc.upload(crc));
+  CXK_TRY(g.sa_cslot.upload(cslot));
+  CXK_TRY(g.sa_cval.upload(cval));
+  CXK_TRY(g.sa_pptr.upload(pptr));
+  CXK_TRY(g.sa_prc.upload(prc));
+  CXK_TRY(g.sa_eslot.upload(eslot));
+  return CXK_SUCCESS;
+}
+
+// Entry lists of a sparse LMI group (kernels_lmi_sparse.hip.h): matrix-major for the sums, position-major for the slack.
 int UploadSparseLmi(cxk_context* ctx, Group& g) {
   const size_t cnt = g.ids.size(), nn = (size_t)g.n * g.n;
   const int n = g.n, m = g.m, m1 = m + 1;
+  std::vector<LmiLists> lists(cnt);
+  for (size_t k = 0; k < cnt; k++) {
+    ReadLmiLists(ctx->cons[g.ids[k]], &lists[k]);
+    CXK_DEMAND(!lists[k].too_many, "sparse LMI group: too many nonzeros");
+  }
   // a dense affine term stays out of the pair sums (X = W C W is formed instead)
   g.sp_cdense = false;
-  for (size_t k = 0; k < cnt; k++) {
-    size_t nz = 0;
-    for (double v : ctx->cons[g.ids[k]].C) nz += (v != 0.0);
-    if (nz > 64) g.sp_cdense = true;  // (C, C) alone would be nz^2 terms on one wavefront
-  }
+  for (size_t k = 0; k < cnt; k++)
+    if (lists[k].ptr[m1] - lists[k].ptr[m] > 64) g.sp_cdense = true;  // (C, C) alone would be nz^2 terms on one wavefront
   std::vector<int> eptr(cnt * m1 + 1, 0), erc, pptr(cnt * nn + 1, 0), pvar;
   std::vector<double> eval, pval;
   g.sp_emax = 0;
   for (size_t k = 0; k < cnt; k++) {
-    const ConstraintRec& c = ctx->cons[g.ids[k]];
+    const LmiLists& L = lists[k];
     for (int i = 0; i < m1; i++) {
-      const double* M = i < m ? c.A.data() + (size_t)i * nn : c.C.data();
-      if (i < m || !g.sp_cdense)
-        for (int col = 0; col < n; col++)
-          for (int row = 0; row < n; row++) {
-            const double v = M[row + (size_t)col * n];
-            if (v != 0.0) {
-              erc.push_back(row | (col << 16));
-              eval.push_back(v);
-            }
-          }
+      if (i < m || !g.sp_cdense) {
+        erc.insert(erc.end(), L.rc + L.ptr[i], L.rc + L.ptr[i + 1]);
+        eval.insert(eval.end(), L.val + L.ptr[i], L.val + L.ptr[i + 1]);
+      }
       CXK_DEMAND(eval.size() < ((size_t)1 << 31), "sparse LMI group: too many nonzeros");
       eptr[k * m1 + i + 1] = (int)eval.size();
     }
     g.sp_emax = std::max(g.sp_emax, eptr[k * m1 + m1] - eptr[k * m1]);
-    for (size_t q = 0; q < nn; q++) {
-      for (int i = 0; i < m; i++) {
-        const double v = c.A[(size_t)i * nn + q];
-        if (v != 0.0) {
-          pvar.push_back(i);
-          pval.push_back(v);
-        }
+    // position-major: the variables of a position in ascending order (the reference's order of i in sum_i y_i A_i)
+    int* pp = pptr.data() + k * nn;
+    const int base = (int)pval.size();
+    for (int e = 0; e < L.ptr[m]; e++) pp[(size_t)(L.rc[e] & 0xffff) + (size_t)(L.rc[e] >> 16) * n + 1]++;
+    pp[0] = base;
+    for (size_t q = 0; q < nn; q++) pp[q + 1] += pp[q];
+    pvar.resize(pval.size() + (size_t)L.ptr[m]);
+    pval.resize(pvar.size());
+    std::vector<int> fill(pp, pp + nn);
+    for (int i = 0; i < m; i++)
+      for (int e = L.ptr[i]; e < L.ptr[i + 1]; e++) {
+        const int at = fill[(size_t)(L.rc[e] & 0xffff) + (size_t)(L.rc[e] >> 16) * n]++;
+        pvar[at] = i;
+        pval[at] = L.val[e];
       }
-      pptr[k * nn + q + 1] = (int)pval.size();
-    }
   }
   g.sp_small = !g.large && LmiSparseLds(n, m, true, g.sp_cdense, 0) <= kLdsLimit;
   // work split: lanes per pair from the average number of terms of a pair (each lane takes four
@@ -446,46 +548,55 @@ int UploadSparseLmi(cxk_context* ctx, Group& g) {
   CXK_TRY(g.sp_pptr.upload(pptr));
   CXK_TRY(g.sp_pvar.upload(pvar));
   CXK_TRY(g.sp_pval.upload(pval));
+  if (g.sp_affine) {
+    CXK_DEMAND(g.sp_cdense && !g.sp_small, "internal error: a sparse LMI group takes its affine term by nonzeros only beyond the LDS-resident orders");
+    return UploadSparseAffine(ctx, g, lists, eptr);
+  }
   return CXK_SUCCESS;
 }
 
 // Sparse LMI group: the nonzero sums; a dense C first needs X = W C W (LDS for small orders, two
 // GEMMs otherwise).
 
-template <bool SMALL, int LPP>
+template <bool SMALL, int LPP, bool AFF>
 hipError_t LaunchLmiSparseKernelL(Group& g, const LmiGroup& d, const Arena& ar, const double* X, hipStream_t st) {
   const dim3 grid(d.count, g.sp_chunks);
   const int emax = (g.sp_emax + 1) & ~1;  // keeps the arrays behind it 8-byte aligned
   const bool stage = LmiSparseLds(g.n, g.m, SMALL, g.sp_cdense, emax) <= kLdsLimit;
   const size_t lds = LmiSparseLds(g.n, g.m, SMALL, g.sp_cdense, stage ? emax : 0);
-  SparseLaunch L;
+  SparseLaunchOf<AFF> L;
   L.Xg = X;
   L.part = g.ws_part.p;
   L.npart = kSparseCParts;
   L.emax = stage ? emax : 0;
   L.cdense = g.sp_cdense;
+  if constexpr (AFF) {
+    L.Xp = g.ws_main.p + (size_t)d.count * g.n * g.n;
+    L.eslot = g.sa_eslot.p;
+    L.ppos = g.sa_pptr.p;
+  }
   auto raise = [&](const void* k) -> hipError_t {  // dynamic LDS beyond 64 KB needs the attribute
     return lds > 64 * 1024 ? hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit)
                            : hipSuccess;
   };
   hipError_t e;
   if (stage) {
-    if ((e = raise(reinterpret_cast<const void*>(&lmi_schur_sparse<SMALL, LPP, true>))) != hipSuccess) return e;
-    lmi_schur_sparse<SMALL, LPP, true><<<grid, 256, lds, st>>>(d, ar, L);
+    if ((e = raise(reinterpret_cast<const void*>(&lmi_schur_sparse<SMALL, LPP, true, AFF>))) != hipSuccess) return e;
+    lmi_schur_sparse<SMALL, LPP, true, AFF><<<grid, 256, lds, st>>>(d, ar, L);
   } else {
-    if ((e = raise(reinterpret_cast<const void*>(&lmi_schur_sparse<SMALL, LPP, false>))) != hipSuccess) return e;
-    lmi_schur_sparse<SMALL, LPP, false><<<grid, 256, lds, st>>>(d, ar, L);
+    if ((e = raise(reinterpret_cast<const void*>(&lmi_schur_sparse<SMALL, LPP, false, AFF>))) != hipSuccess) return e;
+    lmi_schur_sparse<SMALL, LPP, false, AFF><<<grid, 256, lds, st>>>(d, ar, L);
   }
   return hipGetLastError();
 }
 
-template <bool SMALL>
+template <bool SMALL, bool AFF = false>
 hipError_t LaunchLmiSparseKernel(Group& g, const LmiGroup& d, const Arena& ar, const double* X, hipStream_t st) {
   switch (g.sp_lpp) {
-    case 1: return LaunchLmiSparseKernelL<SMALL, 1>(g, d, ar, X, st);
-    case 4: return LaunchLmiSparseKernelL<SMALL, 4>(g, d, ar, X, st);
-    case 16: return LaunchLmiSparseKernelL<SMALL, 16>(g, d, ar, X, st);
-    default: return LaunchLmiSparseKernelL<SMALL, 64>(g, d, ar, X, st);
+    case 1: return LaunchLmiSparseKernelL<SMALL, 1, AFF>(g, d, ar, X, st);
+    case 4: return LaunchLmiSparseKernelL<SMALL, 4, AFF>(g, d, ar, X, st);
+    case 16: return LaunchLmiSparseKernelL<SMALL, 16, AFF>(g, d, ar, X, st);
+    default: return LaunchLmiSparseKernelL<SMALL, 64, AFF>(g, d, ar, X, st);
   }
 }
 
@@ -494,7 +605,22 @@ hipError_t LaunchLmiSchurSparse(Group& g, LmiKernel kern, const Arena& ar, hipSt
   const int n = g.n;
   if (kern == kSchurSparseSmall || kern == kSchurSparseSmallDenseC) return LaunchLmiSparseKernel<true>(g, d, ar, nullptr, st);
   double* X = nullptr;
-  if (g.sp_cdense) {
+  if (kern == kSchurSparseAffine) {
+    SparseAffine a;
+    a.cptr = g.sa_cptr.p;
+    a.crc = g.sa_crc.p;
+    a.cslot = g.sa_cslot.p;
+    a.cval = g.sa_cval.p;
+    a.pptr = g.sa_pptr.p;
+    a.prc = g.sa_prc.p;
+    a.U = g.ws_main.p;                               // count x n^2
+    a.Xp = g.ws_main.p + (size_t)d.count * n * n;    // at most count x n^2 positions
+    const int tiles = (n + 63) / 64;
+    lmi_affine_wc<<<dim3(tiles, tiles, d.count), 256, 0, st>>>(d, a);
+    lmi_affine_x<<<dim3((g.sa_pmax + 3) / 4, d.count), 256, 0, st>>>(d, a);
+    lmi_affine_scalars<<<dim3(kSparseCParts, d.count), 256, 0, st>>>(d, a, g.ws_part.p);
+    return LaunchLmiSparseKernel<false, true>(g, d, ar, nullptr, st);
+  } else if (g.sp_cdense) {
     const int64_t nn = (int64_t)n * n;
     double* CW = g.ws_main.p;                  // count x nn
     X = g.ws_main.p + (size_t)d.count * nn;    // count x nn
@@ -648,6 +774,7 @@ int cxk_lmi_kernels(const cxk_context* ctx, int constraint, int out[5]) {
 }
 
 const char* cxk_lmi_kernel_name(int code) {
+  if (code == kSchurSparseAffine) return kSchurSparseAffineName;
   return code >= 0 && code < kLmiKernelCount ? kLmiKernelNames[code] : nullptr;
 }
 

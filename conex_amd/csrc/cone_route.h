@@ -95,6 +95,26 @@ inline bool SocSparsePays(double len, double m, double nnz, double ratio) {
 // more.  Nothing smaller was measured, so nothing smaller moves (the cones of a handful of doubles stay where they are).
 constexpr long long kQuadStreamMinWork = 32 * 32 + 33 * 8;  // 1288
 
+// Automatic mode (cxk_set_sparse_affine(ctx, -1)) evaluates the affine term C of a sparse matrix inequality beyond
+// the LDS-resident orders from C's nonzeros (kernels_lmi_sparse.hip.h: lmi_affine_wc, lmi_affine_x) when
+// R (nnz_c + npos) <= 4 n^2: the two kernels make n nnz_c + n npos multiply-adds (npos: the distinct positions of
+// W C W that an entry of some A_i or of C names), the two GEMMs they replace 4 n^3 flops on the matrix pipe.  Measured
+// (tools/lmi_entries_speed.py): R is twice the smallest 4 n^2 / (nnz_c + npos) among the measured
+// shapes at which the assembly is faster on the new kernels, 30.6 at order 256 with 8 sub-diagonals (42.8 us against
+// 54.6 us); every measured shape with a larger ratio wins too (max-cut at 500 / 2000: 143 / 572), every one at 20 and
+// below loses (a tenth of C's entries at order 256 / 1024: 58.1 us against 54.2 us, 274 us against 151 us); twice,
+// because the numbers are one box's on one day.  CXK_SPARSE_AFFINE_MIN_RATIO moves R for comparison runs.  An affine
+// term of at most kSparseAffineMinNnz nonzeros never asks: it rides in the pair sums as list number m.
+constexpr double kSparseAffineMinRatio = 61.2;
+constexpr int kSparseAffineMinNnz = 64;
+inline bool LmiSparseAffinePays(double n, double nnz_c, double npos, double ratio = kSparseAffineMinRatio) {
+  return nnz_c > kSparseAffineMinNnz && ratio * (nnz_c + npos) <= 4.0 * n * n;
+}
+// The packed tables of the sparse-LMI route (erc = row | col << 16, the pair table i | j << 16) go into ints that the
+// kernels unpack with `& 0xffff` and a signed `>> 16`: the shifted half must stay below 2^15.  cxk_add_lmi_coo
+// refuses a larger order or variable count by this name.
+constexpr int kSparseLmiMaxIndex = 32767;
+
 // Dynamic LDS of the LDS-resident kernels: what the launch sites ask for and what Choose admits a constraint by,
 // so that an admitted constraint can be launched at every stage.  Every product is taken in size_t.
 inline size_t LmiGenericLds(int n) { return sizeof(double) * 4 * (size_t)n * (size_t)n; }
@@ -138,6 +158,11 @@ struct RouteModes {
   long long streamed_quadratic_min_work = kQuadStreamMinWork;       // CXK_STREAMED_QUADRATIC_MIN_WORK (comparison runs)
   double sparse_linear_min_ratio = kSparseLinearMinRatio;           // CXK_SPARSE_LINEAR_MIN_RATIO (comparison runs)
   double sparse_soc_min_ratio = kSparseSocMinRatio;                 // CXK_SPARSE_SOC_MIN_RATIO (comparison runs)
+  // CXK_SPARSE_AFFINE: how a sparse LMI group beyond the LDS-resident orders evaluates an affine term of more than 64
+  // nonzeros: -1 from C's nonzeros when LmiSparseAffinePays, 0 by the two GEMMs, 1 always from the nonzeros; -2: nobody
+  // said, each constraint keeps the default of its entry point (cxk_add_lmi 0, cxk_add_lmi_coo -1).  No route hangs on it.
+  int sparse_affine = -2;
+  double sparse_affine_min_ratio = kSparseAffineMinRatio;           // CXK_SPARSE_AFFINE_MIN_RATIO (comparison runs)
 };
 
 // The route, or why there is none (`refusal` is the message cxk_finalize fails with; null with a route).
@@ -251,6 +276,13 @@ inline RouteChoice ChooseLmi(const ConeShape& s, const RouteModes& md) {
   // held by its factors in front of the large-order route (cxk_finalize has checked the order and the int indexing
   // of the kernels)
   if (s.factored) return Take(ConeRoute::kLmiFactored);
+  // held by its nonzeros (symmetric by construction, order and variables within kSparseLmiMaxIndex: cxk_add_lmi_coo)
+  if (s.csr_only) {
+    if (md.sparse_lmi == 0)
+      return Refuse("a matrix inequality added by cxk_add_lmi_coo has no dense matrices and can only take the sparse route "
+                    "(CXK_SPARSE_LMI, which is 0)");
+    return Take(ConeRoute::kLmiSparse);
+  }
   // The reference accepts non-symmetric matrices and evaluates <W A_i W, A_j> as written; only the literal LDS
   // kernels do the same.
   if (!s.symmetric && !LmiLdsResident(s.n, s.m))

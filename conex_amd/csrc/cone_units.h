@@ -83,6 +83,8 @@ CXK_LOCAL int LaunchQuadTakeStep(cxk_context* ctx, Group& g, const StepArgs& sa)
 CXK_LOCAL hipError_t RaiseLmiLdsLimits();
 // GroupConstraints: what Choose asks about a dense-added LMI (mfma_supports, sparse_pays)
 CXK_LOCAL void MeasureLmi(const ConstraintRec& c, ConeShape* s);
+// a constraint on kLmiSparse evaluates its affine term from C's nonzeros under `mode` (-1 / 0 / 1: cxk_set_sparse_affine)
+CXK_LOCAL bool LmiTakesSparseAffine(const ConstraintRec& c, int mode, double min_ratio);
 // UploadGroup: the group's assembly, whether it is `large`, and the work space of the chip-wide Lanczos run
 CXK_LOCAL int PlanLmiGroup(cxk_context* ctx, Group& g, const FinalizeSwitches& sw);
 CXK_LOCAL int UploadLmiDense(cxk_context* ctx, Group& g, const FinalizeSwitches& sw);

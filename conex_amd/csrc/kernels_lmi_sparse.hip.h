@@ -14,6 +14,8 @@
 // (the dense A is never uploaded).  A dense affine term C (more than 64 nonzeros) does not join
 // the pair sums: X = W C W is formed densely instead (LDS for small orders, two GEMM launches
 // otherwise) and AQc(i) = sum a X[c,r], <c,Qc> = sum C o X, <w,c> = sum C o W.
+// Beyond the LDS-resident orders such a C can instead be taken by its nonzeros (cxk_set_sparse_affine; the kernels
+// lmi_affine_wc / _x / _scalars below): W C W is then formed only at the positions that an entry of some A_i or of C reads.
 // Values equal the dense path's up to summation order (tolerance parity,
 // tests/test_gpu_sparse.py); every sum has a fixed order: bit-reproducible.
 //
@@ -24,6 +26,8 @@
 // (kernels_lmi.hip.h / kernels_lmi_large.hip.h: sp_pptr / sp_pvar / sp_pval) so that every
 // entry of sum_i y_i A_i is accumulated by one thread in the reference's order of i.
 #pragma once
+#include <type_traits>
+
 #include "kernels_lmi.hip.h"
 
 namespace cxk {
@@ -53,6 +57,16 @@ struct SparseLaunch {
   int emax;            // entries reserved in LDS per workgroup (STAGE)
   int cdense;          // C takes the dense route
 };
+// ... of the instances behind the affine term by its nonzeros (AFF; SparseAffine below): W C W at the group's positions,
+// member mem's from ppos[mem] on, and the slot there of every entry of the A_i.  The other instances take the plain
+// struct: their code is what it was.
+struct SparseLaunchAffine : SparseLaunch {
+  const double* Xp;
+  const int* eslot;
+  const int* ppos;
+};
+template <bool AFF>
+using SparseLaunchOf = typename std::conditional<AFF, SparseLaunchAffine, SparseLaunch>::type;
 
 // Dense C beyond LDS-resident orders: partial sums of <w,c> = sum C o W and <c,Qc> = sum C o X over
 // slices of the n^2 positions; grid (npart, count).  The sparse kernel adds them in block order.
@@ -70,6 +84,102 @@ __global__ void __launch_bounds__(256) lmi_dense_c_scalars(LmiGroup g, const dou
     const double c = Cm[q];
     wc = fma(c, Wg[q], wc);
     cq = fma(c, X[q], cq);
+  }
+  wc = BlockSum(wc, red);
+  cq = BlockSum(cq, red + 8);
+  if (threadIdx.x == 0) {
+    part[((size_t)mem * gridDim.x + blockIdx.x) * 2] = wc;
+    part[((size_t)mem * gridDim.x + blockIdx.x) * 2 + 1] = cq;
+  }
+}
+
+// ---- The affine term of a group beyond the LDS-resident orders from C's nonzeros (cxk_set_sparse_affine): instead of
+// X = W C W by two n^3 GEMMs and sums over all n^2 positions,
+//   U = (W C)':  U[p,c] = sum_{q in column p of C} C[q,p] W[c,q]          (lmi_affine_wc:  n nnz(C) multiply-adds)
+//   X[c,r] = sum_p U[p,c] W[p,r]  at the positions (c,r) of P only        (lmi_affine_x:   n |P| multiply-adds)
+//   <w,c> = sum_{(q,p) in C} C[q,p] W[p,q],  <c,Qc> = sum C[q,p] X[p,q]   (lmi_affine_scalars, slices as lmi_dense_c_scalars)
+//   AQc(i) = sum_{(r,c,a) in A_i} a X[c,r]                                (lmi_schur_sparse, through SparseLaunch::eslot)
+// P: the distinct positions that an entry of some A_i or of C names.  W is read as stored: nothing but the symmetry of
+// C, which cxk_add_lmi_coo makes and the route demands, is used.  The product is kept transposed so that both W and U
+// are read down their columns: lmi_affine_wc reads W with the lanes along a column and turns its 64 x 64 tile in LDS,
+// lmi_affine_x multiplies two columns.  Every sum has a fixed order; no atomics.
+struct SparseAffine {
+  const int* cptr;    // (n + 1) per member: column p of its C is [cptr[p], cptr[p + 1]) of crc / cval / cslot
+  const int* crc;     // row | col << 16, rows ascending within a column
+  const int* cslot;   // the slot in P of position (col, row)
+  const double* cval;
+  const int* pptr;    // count + 1: member mem's positions are [pptr[mem], pptr[mem + 1]) of prc and of Xp
+  const int* prc;     // r | c << 16 of position (c, r), ascending: a run of positions shares the column c of U
+  double* U;          // count x n^2
+  double* Xp;
+};
+
+// grid (tiles of 64 c, tiles of 64 p, count).  A wavefront takes 16 of the tile's columns p with its lanes along c:
+// every load of W is one contiguous run of a column; the bounds and entries of column p are wavefront-uniform.
+__global__ void __launch_bounds__(256) lmi_affine_wc(LmiGroup g, SparseAffine a) {
+  __shared__ double tile[64 * 65];
+  const int n = g.n, mem = blockIdx.z, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int c0 = blockIdx.x * 64, p0 = blockIdx.y * 64, c = c0 + lane;
+  const double* W = g.W + (size_t)mem * n * n;
+  const int* cp = a.cptr + (size_t)mem * (n + 1);
+  for (int pl = wave; pl < 64; pl += 4) {
+    const int p = p0 + pl;
+    double s = 0;
+    if (p < n && c < n) {
+      const int e1 = cp[p + 1];
+#pragma unroll 4
+      for (int e = cp[p]; e < e1; e++) s = fma(a.cval[e], W[c + (size_t)(a.crc[e] & 0xffff) * n], s);
+    }
+    tile[lane * 65 + pl] = s;
+  }
+  __syncthreads();
+  double* U = a.U + (size_t)mem * n * n;
+  const int p = p0 + lane;
+  for (int cl = wave; cl < 64; cl += 4)
+    if (p < n && c0 + cl < n) U[p + (size_t)(c0 + cl) * n] = tile[cl * 65 + lane];
+}
+
+// grid (positions / 4, count): a wavefront per position, its lanes down the two columns, four independent partial
+// sums per lane, then the fixed butterfly over the lanes.
+__global__ void __launch_bounds__(256) lmi_affine_x(LmiGroup g, SparseAffine a) {
+  const int n = g.n, mem = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int b = a.pptr[mem], k = blockIdx.x * 4 + wave;
+  if (k >= a.pptr[mem + 1] - b) return;
+  const int rc = a.prc[b + k], r = rc & 0xffff, c = rc >> 16;
+  const double* Uc = a.U + (size_t)mem * n * n + (size_t)c * n;
+  const double* Wr = g.W + (size_t)mem * n * n + (size_t)r * n;
+  double s0 = 0, s1 = 0, s2 = 0, s3 = 0;
+  int q = lane;
+  for (; q + 192 < n; q += 256) {
+    s0 = fma(Uc[q], Wr[q], s0);
+    s1 = fma(Uc[q + 64], Wr[q + 64], s1);
+    s2 = fma(Uc[q + 128], Wr[q + 128], s2);
+    s3 = fma(Uc[q + 192], Wr[q + 192], s3);
+  }
+  for (; q < n; q += 64) s0 = fma(Uc[q], Wr[q], s0);
+  double s = (s0 + s1) + (s2 + s3);
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, 64);
+  if (lane == 0) a.Xp[b + k] = s;
+}
+
+// Partial sums of <w,c> and <c,Qc> over slices of C's nonzeros, in the layout of lmi_dense_c_scalars (lmi_schur_sparse
+// adds them in block order); grid (npart, count).
+__global__ void __launch_bounds__(256) lmi_affine_scalars(LmiGroup g, SparseAffine a, double* __restrict__ part) {
+  __shared__ double red[16];
+  const int n = g.n, mem = blockIdx.y;
+  const double* Wg = g.W + (size_t)mem * n * n;
+  const double* Xp = a.Xp + a.pptr[mem];
+  const int* cp = a.cptr + (size_t)mem * (n + 1);
+  const int b = cp[0], nz = cp[n] - b;
+  const int per = (nz + gridDim.x - 1) / gridDim.x;
+  const int e0 = b + per * blockIdx.x, e1 = e0 + per < b + nz ? e0 + per : b + nz;
+  double wc = 0, cq = 0;
+  for (int e = e0 + threadIdx.x; e < e1; e += blockDim.x) {
+    const int rc = a.crc[e], row = rc & 0xffff, col = rc >> 16;
+    const double v = a.cval[e];
+    wc = fma(v, Wg[col + (size_t)row * n], wc);
+    cq = fma(v, Xp[a.cslot[e]], cq);
   }
   wc = BlockSum(wc, red);
   cq = BlockSum(cq, red + 8);
@@ -155,8 +265,9 @@ __device__ __forceinline__ double PairSum(const int* erc, const double* eval, co
 // the W elements it names), so the terms of a lane are issued four at a time.  STAGE: the
 // constraint's entry list is copied to LDS first: a sweep reads entries at unrelated addresses,
 // which costs a cache line per lane from L1/L2 but only bank conflicts from LDS.
-template <bool SMALL, int LPP, bool STAGE>
-__global__ void __launch_bounds__(256) lmi_schur_sparse(LmiGroup g, Arena ar, SparseLaunch L) {
+// AFF (never with SMALL): AQc gathers W C W from the values at the positions.
+template <bool SMALL, int LPP, bool STAGE, bool AFF = false>
+__global__ void __launch_bounds__(256) lmi_schur_sparse(LmiGroup g, Arena ar, SparseLaunchOf<AFF> L) {
   extern __shared__ double lds[];
   const int n = g.n, m = g.m, m1 = m + 1, nn = n * n;
   const int mem = blockIdx.x, id = g.ids[mem];
@@ -195,6 +306,12 @@ __global__ void __launch_bounds__(256) lmi_schur_sparse(LmiGroup g, Arena ar, Sp
   SPSTAMP(1);
   // dense C: X = W C W (LDS product here for small orders, GEMM launches before this kernel otherwise)
   const double* X = (cdense && L.Xg) ? L.Xg + (size_t)mem * nn : nullptr;
+  const double* Xp = nullptr;  // (AFF: W C W at the positions, and an entry's slot beside the entry in the unstaged list)
+  const int* eslot = nullptr;
+  if constexpr (AFF) {
+    Xp = L.Xp + L.ppos[mem];
+    eslot = L.eslot + (STAGE ? e0 : 0);
+  }
   if (cdense && SMALL) {
     double* sC = sW + nn;
     double* sP = sC + nn;
@@ -243,7 +360,11 @@ __global__ void __launch_bounds__(256) lmi_schur_sparse(LmiGroup g, Arena ar, Sp
         const int rc = erc[e], r = rc & 0xffff, c = rc >> 16;
         const double a = eval[e];
         aw = fma(a, W[c + (size_t)r * n], aw);
-        if (cdense) aq = fma(a, X[c + (size_t)r * n], aq);
+        if constexpr (AFF) {
+          aq = fma(a, Xp[eslot[e]], aq);
+        } else {
+          if (cdense) aq = fma(a, X[c + (size_t)r * n], aq);
+        }
       }
       aw = GroupSum<LPV>(aw);
       if (cdense) aq = GroupSum<LPV>(aq);

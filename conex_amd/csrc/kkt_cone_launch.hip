@@ -186,7 +186,7 @@ static void MeasureNonzeros(ConstraintRec* c, ConeShape* s) {
 // cxk_finalize fails with); constraints of one shape on one route form a group, numbered by first appearance.
 int GroupConstraints(cxk_context* ctx, const FinalizeSwitches& sw) {
   const int K = (int)ctx->cons.size();
-  std::map<std::tuple<int, int, int, int, ConeRoute, bool, bool, int>, int> gmap;
+  std::map<std::tuple<int, int, int, int, ConeRoute, bool, bool, int, bool>, int> gmap;
   ctx->groups.clear();
   ctx->sparse_soc_setup_ms = 0;
   // what the context was told (-1 / -2: nothing) goes in front of the environment's word
@@ -196,9 +196,11 @@ int GroupConstraints(cxk_context* ctx, const FinalizeSwitches& sw) {
   if (ctx->streamed_quadratic != -2) modes.streamed_quadratic = ctx->streamed_quadratic;
   if (ctx->sparse_linear != -2) modes.sparse_linear = ctx->sparse_linear;
   if (ctx->sparse_soc != -2) modes.sparse_soc = ctx->sparse_soc;
+  if (ctx->sparse_affine != -2) modes.sparse_affine = ctx->sparse_affine;
   for (int i = 0; i < K; i++) {
     ConstraintRec& c = ctx->cons[i];
     c.route = ConeRoute::kStatic;
+    c.sparse_affine = false;
     if (!ctx->owned[i]) continue;
     ConeShape s{c.type, c.n, c.m, c.herm_d, c.symmetric, c.csr_only, c.factored, c.type == CXK_QUAD && !c.Q.empty()};
     const int sparse_mode = c.type == CXK_LINEAR ? modes.sparse_linear : c.type == CXK_SOC ? modes.sparse_soc : 0;
@@ -209,7 +211,11 @@ int GroupConstraints(cxk_context* ctx, const FinalizeSwitches& sw) {
     c.route = choice.route;
     const bool literal = c.type == CXK_LMI && !c.symmetric;
     const int f_R = c.factored ? c.f_R : 0;
-    const auto key = std::make_tuple(c.type, c.n, c.m, c.herm_d, c.route, literal, s.has_q, f_R);
+    // (nobody said: the default of the entry point the constraint came through; a group mixes no modes)
+    if (c.route == ConeRoute::kLmiSparse)
+      c.sparse_affine = LmiTakesSparseAffine(c, modes.sparse_affine != -2 ? modes.sparse_affine : c.affine_default,
+                                             modes.sparse_affine_min_ratio);
+    const auto key = std::make_tuple(c.type, c.n, c.m, c.herm_d, c.route, literal, s.has_q, f_R, c.sparse_affine);
     auto it = gmap.find(key);
     if (it == gmap.end()) {
       it = gmap.emplace(key, (int)ctx->groups.size()).first;
@@ -222,6 +228,7 @@ int GroupConstraints(cxk_context* ctx, const FinalizeSwitches& sw) {
       g.literal = literal;
       g.has_q = s.has_q;
       g.f_R = f_R;
+      g.sp_affine = c.sparse_affine;
     }
     c.group = it->second;
     c.member = (int)ctx->groups[it->second].ids.size();

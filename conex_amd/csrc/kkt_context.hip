@@ -109,6 +109,8 @@ static FinalizeSwitches ReadFinalizeSwitches() {
   if ((v = getenv("CXK_TILED_LINEAR_MIN_WORK")) && v[0] != '\0') sw.modes.tiled_linear_min_work = std::max(0ll, atoll(v));
   if ((v = getenv("CXK_SPARSE_SOC")) && v[0] != '\0') sw.modes.sparse_soc = atoi(v) != 0;
   if ((v = getenv("CXK_SPARSE_SOC_MIN_RATIO")) && v[0] != '\0') sw.modes.sparse_soc_min_ratio = std::max(0.0, atof(v));
+  if ((v = getenv("CXK_SPARSE_AFFINE")) && v[0] != '\0') sw.modes.sparse_affine = std::max(-1, std::min(1, atoi(v)));
+  if ((v = getenv("CXK_SPARSE_AFFINE_MIN_RATIO")) && v[0] != '\0') sw.modes.sparse_affine_min_ratio = std::max(0.0, atof(v));
   if ((v = getenv("CXK_WIDE_SPECTRUM")) && v[0] != '\0') sw.wide_spectrum = std::max(-1, std::min(1, atoi(v)));
   if ((v = getenv("CXK_WIDE_REDUCE_MIN_ORDER")) && v[0] != '\0') sw.wide_reduce_min_order = std::max(0, atoi(v));
   return sw;
@@ -245,6 +247,14 @@ static int FinalizeImpl(cxk_context* ctx) {
         return CXK_FAILURE;
       }
     }
+  // a matrix inequality held by its nonzeros has one route (a host-only context says so too: cone_route.h has the words)
+  for (const ConstraintRec& c : ctx->cons)
+    if (c.type == CXK_LMI && c.csr_only) {
+      ConeShape s;
+      s.type = c.type, s.n = c.n, s.m = c.m, s.csr_only = true;
+      const RouteChoice choice = Choose(s, sw.modes);
+      CXK_DEMAND(!choice.refusal, choice.refusal);
+    }
   if (ChooseEliminationStructure(ctx, sw)) return CXK_FAILURE;
   ctx->finalized = true;
   if (ctx->device < 0) return CXK_SUCCESS;  // symbolic-only context
@@ -377,6 +387,59 @@ int cxk_add_lmi_factored(cxk_context* ctx, int n, int m, const int* rank_ptr, co
   else
     r.f_sigma.assign((size_t)R, 1.0);
   r.C.assign(C, C + nn);
+  return AddConstraint(ctx, std::move(r), vars);
+}
+
+int cxk_add_lmi_coo(cxk_context* ctx, int n, int m, const int* ptr, const int* row, const int* col, const double* val,
+                    const int* vars) {
+  if (!ctx) return -1;
+  auto refuse = [ctx](const std::string& msg) {
+    ctx->err = "cxk_add_lmi_coo: " + msg;
+    return -1;
+  };
+  if (n < 1 || m < 0) return refuse("n is at least 1 and m at least 0");
+  if (!ptr) return refuse("ptr is null");
+  // (before anything of size n x n is touched)
+  if (n > kSparseLmiMaxIndex || m > kSparseLmiMaxIndex)
+    return refuse("n or m is above " + std::to_string(kSparseLmiMaxIndex) +
+                  " (the entry table packs row | col << 16 and the pair table i | j << 16 into ints that the kernels "
+                  "unpack with signed shifts)");
+  if (ptr[0] != 0) return refuse("ptr[0] is not 0");
+  for (int i = 0; i <= m; i++)
+    if (ptr[i + 1] < ptr[i]) return refuse("ptr decreases");
+  if (ptr[m + 1] > 0 && (!row || !col || !val)) return refuse("row, col or val is null");
+  ConstraintRec r;
+  r.type = CXK_LMI;
+  r.n = n;
+  r.m = m;
+  r.csr_only = true;
+  r.affine_default = -1;
+  r.e_ptr.assign((size_t)m + 2, 0);
+  std::vector<std::pair<int, double>> list;  // (row | col << 16, value): both triangles of one matrix
+  for (int i = 0; i <= m; i++) {
+    list.clear();
+    for (int s = ptr[i]; s < ptr[i + 1]; s++) {
+      if (row[s] < 0 || row[s] >= n || col[s] < 0 || col[s] >= n) return refuse("an index is outside [0, n)");
+      if (row[s] < col[s]) return refuse("an entry lies above the diagonal (row < col): the lower triangle is given");
+      if (!std::isfinite(val[s])) return refuse("a value is not finite");
+      list.emplace_back(row[s] | (col[s] << 16), val[s]);
+      if (row[s] != col[s]) list.emplace_back(col[s] | (row[s] << 16), val[s]);
+    }
+    // by column, then row: the packed word orders exactly so
+    std::sort(list.begin(), list.end(), [](const std::pair<int, double>& a, const std::pair<int, double>& b) { return a.first < b.first; });
+    for (size_t s = 1; s < list.size(); s++)
+      if (list[s].first == list[s - 1].first) return refuse("a list names a position twice");
+    for (const auto& e : list)
+      if (e.second != 0.0) {  // explicit zeros are dropped
+        r.e_rc.push_back(e.first);
+        r.e_val.push_back(e.second);
+      }
+    if (r.e_rc.size() > (size_t)INT_MAX) return refuse("more than 2^31 nonzeros");
+    r.e_ptr[(size_t)i + 1] = (int)r.e_rc.size();
+  }
+  r.C.assign((size_t)n * n, 0.0);
+  for (int e = r.e_ptr[m]; e < r.e_ptr[m + 1]; e++)
+    r.C[(size_t)(r.e_rc[e] & 0xffff) + (size_t)(r.e_rc[e] >> 16) * n] = r.e_val[e];
   return AddConstraint(ctx, std::move(r), vars);
 }
 
@@ -689,6 +752,20 @@ int cxk_set_sparse_soc(cxk_context* ctx, int mode) {
 int cxk_count_sparse_soc(const cxk_context* ctx) { return CountOnRoute(ctx, ConeRoute::kSocSparse); }
 
 double cxk_sparse_soc_setup_ms(const cxk_context* ctx) { return ctx && ctx->finalized ? ctx->sparse_soc_setup_ms : 0.0; }
+
+int cxk_set_sparse_affine(cxk_context* ctx, int mode) {
+  if (!ctx) return CXK_FAILURE;
+  CXK_DEMAND(!ctx->finalized, "cxk_set_sparse_affine: the context is finalized (the choice is made by cxk_finalize)");
+  CXK_DEMAND(mode >= -1 && mode <= 1, "cxk_set_sparse_affine: the mode is -1 (automatic), 0 (never) or 1 (every eligible sparse matrix inequality)");
+  ctx->sparse_affine = mode;
+  return CXK_SUCCESS;
+}
+int cxk_count_sparse_affine(const cxk_context* ctx) {
+  if (!ctx || !ctx->finalized) return -1;
+  int k = 0;
+  for (size_t i = 0; i < ctx->cons.size(); i++) k += ctx->owned[i] && ctx->cons[i].route == ConeRoute::kLmiSparse && ctx->cons[i].sparse_affine;
+  return k;
+}
 
 int cxk_set_wide_spectrum(cxk_context* ctx, int mode) {
   if (!ctx) return CXK_FAILURE;

@@ -60,6 +60,16 @@ struct ConstraintRec {
   int f_R = 0;
   std::vector<int> f_ptr;
   std::vector<double> f_F, f_sigma;
+  // CXK_LMI given by its nonzeros (cxk_add_lmi_coo; csr_only is set and A stays empty, C is the n x n square the slack
+  // kernels read): list i < m holds A_i, list m holds C, both triangles of each, sorted by column then row -- the order
+  // in which UploadSparseLmi scans a dense matrix -- as e_rc = row | col << 16 and e_val from e_ptr[i] on (m + 2 pointers)
+  std::vector<int> e_ptr, e_rc;
+  std::vector<double> e_val;
+  // how a sparse group beyond the LDS-resident orders evaluates this constraint's affine term when nobody says
+  // (cxk_set_sparse_affine, CXK_SPARSE_AFFINE): 0 the two GEMMs, -1 from C's nonzeros when that pays; and what
+  // GroupConstraints made of it (members of one group agree)
+  int affine_default = 0;
+  bool sparse_affine = false;
 };
 
 template <typename T>
@@ -136,6 +146,16 @@ struct Group {
   bool sp_small = false;           // W (and X) of a constraint fit in LDS
   DevBuf<int> sp_eptr, sp_erc, sp_pptr, sp_pvar, sp_pairs;
   DevBuf<double> sp_eval, sp_pval;
+  // ... whose dense-route affine term is evaluated from C's nonzeros (cxk_set_sparse_affine; kernels_lmi_sparse.hip.h:
+  // lmi_affine_wc / _x / _scalars): every member's C by columns (sa_cptr: n + 1 pointers per member into sa_crc = row | col << 16
+  // and sa_cval), the distinct positions of W C W that an entry of some A_i or of C names (sa_pptr: count + 1 pointers
+  // into sa_prc = row | col << 16, ascending), and the slot in that list of every entry of the A_i (sa_eslot, beside
+  // sp_erc) and of C (sa_cslot, beside sa_crc).  (W C)' in the first half of ws_main, the values at the positions in
+  // the second.
+  bool sp_affine = false;
+  int sa_pmax = 0;  // most positions in one member
+  DevBuf<int> sa_cptr, sa_crc, sa_cslot, sa_pptr, sa_prc, sa_eslot;
+  DevBuf<double> sa_cval;
   // second-order cones beyond LDS (kSocStreamed, cxk_set_streamed_cones): the kernels of kernels_soc_stream.hip.h; WA in ws_main,
   // the Gram product's output in ws_gf and its split partials in ws_part (`splits` of them)
   DevBuf<double> st_vec;   // s, Q(s) c, the slack: three vectors per cone
@@ -208,6 +228,9 @@ struct cxk_context {
   // cxk_set_wide_spectrum: -2 the environment's CXK_WIDE_SPECTRUM (else automatic), -1 automatic (large-order groups
   // above LmiLargeSpectrumMaxOrder()), 0 never (such orders are refused), 1 every large-order group
   int wide_spectrum = -2;
+  // cxk_set_sparse_affine: -2 the environment's CXK_SPARSE_AFFINE (else every constraint's own default: 0 for
+  // cxk_add_lmi / cxk_add_hermitian, -1 for cxk_add_lmi_coo), -1 when it pays, 0 never, 1 every eligible group
+  int sparse_affine = -2;
   std::vector<Group> groups;
   std::vector<int64_t> g_off, r_off;
   std::vector<unsigned char> owned;      // constraint i assembled/updated by this rank

@@ -69,6 +69,11 @@ struct Cone {
   bool factored = false;
   std::vector<double> F, sigma;
   std::vector<int> rank_ptr;
+  // kLmi added by CONEX_HIP_AddLMIConstraintFromEntries: the lower triangles of A_v (list v) and of the affine term
+  // (list vars.size()) as e_ptr / e_row / e_col / e_val; `mats` and `affine` stay empty: the matrices are never formed
+  bool from_entries = false;
+  std::vector<int> e_ptr, e_row, e_col;
+  std::vector<double> e_val;
 };
 
 struct Program {
@@ -87,6 +92,7 @@ struct Program {
   int tiled_linear = -1;        // linear blocks on the tiled kernels: -1 by size; see CONEX_HIP_SetTiledLinear
   int sparse_linear = -1;       // linear blocks from their nonzeros: -1 by pattern; see CONEX_HIP_SetSparseLinear
   int sparse_soc = 0;           // second-order cones from their nonzeros: 0 none; see CONEX_HIP_SetSparseSoc
+  int sparse_affine = -2;       // affine terms of sparse LMIs from their nonzeros: -2 nothing said; see CONEX_HIP_SetSparseAffine
   int streamed_quadratic = -1;  // quadratic cones held in HBM: -1 beyond LDS or by size; see CONEX_HIP_SetStreamedQuadratic
   // multi-GPU (one process per GPU, every rank builds the same program): see CONEX_HIP_SetCommunicator
   int shard_rank = 0, shard_world = 1;
@@ -163,6 +169,8 @@ int BuildContext(Program* p) {
   cxk_set_sparse_linear(p->ctx, p->sparse_linear);
   // (never, as the cxk_* interface defaults: every program keeps its route and its bits unless asked)
   cxk_set_sparse_soc(p->ctx, p->sparse_soc);
+  // (nothing said: every constraint keeps the default of the entry point it comes through)
+  if (p->sparse_affine != -2) cxk_set_sparse_affine(p->ctx, p->sparse_affine);
   // (likewise no quadratic cone is refused for its size: automatic, where the cxk_* interface defaults to never)
   cxk_set_streamed_quadratic(p->ctx, p->streamed_quadratic);
   if (p->shard_world > 1) {
@@ -186,6 +194,11 @@ int BuildContext(Program* p) {
                                                         c.sigma.data(), c.affine.data(), c.vars.data())
                            : cxk_add_lmi_factored(p->ctx, c.order, m, c.rank_ptr.data(), c.F.data(), c.sigma.data(),
                                                   c.affine.data(), c.vars.data());
+          break;
+        }
+        if (c.from_entries) {  // the lists go to the device as they are: nothing of size m n^2 is formed
+          id = cxk_add_lmi_coo(p->ctx, c.order, m, c.e_ptr.data(), c.e_row.data(), c.e_col.data(), c.e_val.data(), c.vars.data());
+          CONEX_DEMAND(id >= 0, cxk_last_error(p->ctx));
           break;
         }
         const size_t sz = (size_t)c.order * c.order * c.hyper;
@@ -1013,6 +1026,7 @@ CONEX_STATUS CONEX_UpdateLinearOperator(void* x, int constraint, double value, i
   switch (k.kind) {
     case kLmi: {  // hermitian_psd.cc:249-275
       CONEX_DEMAND(!k.factored, "A constraint given by factors does not support updates of linear operator.");
+      CONEX_DEMAND(!k.from_entries, "A constraint given by entries does not support updates of linear operator.");
       CONEX_DEMAND(dim >= 0 && dim < k.hyper, "Complex dimension out of bounds.");
       CONEX_DEMAND(row >= 0 && col >= 0 && row < k.order && col < k.order,
                    "Matrix dimension out of bounds.");
@@ -1070,6 +1084,7 @@ CONEX_STATUS CONEX_UpdateAffineTerm(void* x, int constraint, double value, int r
   switch (k.kind) {
     case kLmi: {  // hermitian_psd.cc:286-313
       CONEX_DEMAND(!k.factored, "A constraint given by factors does not support updates of affine term.");
+      CONEX_DEMAND(!k.from_entries, "A constraint given by entries does not support updates of affine term.");
       CONEX_DEMAND(dim >= 0 && dim < k.hyper, "Complex dimension out of bounds.");
       CONEX_DEMAND(row >= 0 && col >= 0 && row < k.order && col < k.order,
                    "Matrix dimension out of bounds.");
@@ -1297,6 +1312,45 @@ int CONEX_HIP_AddFactoredLMIConstraint(void* x, int n, const double* F, int R, c
   return AddCone(p, std::move(k));
 }
 
+/* not part of conex.h: a DenseLMIConstraint whose matrices are sparse and given by their entries: list v < num_vars,
+ * ptr[v] .. ptr[v + 1] - 1, holds A_v and list num_vars the affine term, as (row, col, val) with row >= col (the lower
+ * triangle; the matrices are its symmetric completion; entries in any order, explicit zeros dropped, an empty list is
+ * the zero matrix); vars: num_vars variable ids (NULL: all variables in order).  The matrices are never formed
+ * (cxk_add_lmi_coo): a program with an LMI of order n over m variables holds its nonzeros and one n x n square, not
+ * m n^2 doubles.  CONEX_UpdateLinearOperator and CONEX_UpdateAffineTerm fail on such a constraint;
+ * CONEX_GetDualVariable works as for any LMI.  Returns the constraint id, -1 on invalid arguments (a position named
+ * twice in a list is found when the program is initialized). */
+int CONEX_HIP_AddLMIConstraintFromEntries(void* x, int n, const int* ptr, const int* row, const int* col, const double* val,
+                                          int num_vars, const long* vars) {
+  Program* p = static_cast<Program*>(x);
+  if (!p || p->magic != 0xC0DEC0DEu || n < 1 || n > 32767 || num_vars < 0 || num_vars > 32767 || !ptr) return -1;
+  if (vars ? false : num_vars != p->num_vars) return -1;
+  if (ptr[0] != 0) return -1;
+  for (int v = 0; v <= num_vars; v++)
+    if (ptr[v + 1] < ptr[v]) return -1;
+  const int nz = ptr[num_vars + 1];
+  if (nz > 0 && (!row || !col || !val)) return -1;
+  for (int e = 0; e < nz; e++)
+    if (col[e] < 0 || row[e] < col[e] || row[e] >= n || !std::isfinite(val[e])) return -1;
+  Cone k;
+  k.kind = kLmi;
+  k.order = n;
+  k.from_entries = true;
+  k.e_ptr.assign(ptr, ptr + num_vars + 2);
+  k.e_row.assign(row, row + nz);
+  k.e_col.assign(col, col + nz);
+  k.e_val.assign(val, val + nz);
+  if (vars) {
+    for (int i = 0; i < num_vars; i++) {
+      if (vars[i] < 0 || vars[i] >= p->num_vars) return -1;
+      k.vars.push_back((int)vars[i]);
+    }
+  } else {
+    k.vars = AllVars(*p);
+  }
+  return AddCone(p, std::move(k));
+}
+
 /* not part of conex.h: a HermitianPsdConstraint over R / C / H (d = 1, 2, 4) whose matrices are low-rank and given by
  * their factors,  A_v = sum_k sigma[k] f_k f_k^*,  k = rank_ptr[v] .. rank_ptr[v + 1] - 1,  v < num_vars,
  * f_k the hyper-complex columns of F (d planes of n x R column-major, R = rank_ptr[num_vars]); sigma NULL = all +1; c
@@ -1467,6 +1521,22 @@ int CONEX_HIP_SetSparseSoc(void* x, int mode) {
 int CONEX_HIP_CountSparseSoc(void* x) {
   Program* p = static_cast<Program*>(x);
   return p && p->ctx ? cxk_count_sparse_soc(p->ctx) : -1;
+}
+
+/* not part of conex.h: how sparse matrix inequalities of order 64 and up evaluate an affine term of more than 64
+ * nonzeros (conex_kkt_hip.h, cxk_set_sparse_affine): 1 from its nonzeros, 0 by two n^3 GEMMs, -1 from its nonzeros when
+ * that pays.  Without a call a constraint added by CONEX_HIP_AddLMIConstraintFromEntries takes -1 and every other one 0. */
+int CONEX_HIP_SetSparseAffine(void* x, int mode) {
+  Program* p = static_cast<Program*>(x);
+  if (!p || mode < -1 || mode > 1) return CONEX_FAILURE;
+  p->sparse_affine = mode;
+  p->dirty = true;
+  return CONEX_SUCCESS;
+}
+/* matrix inequalities of the program's device context on those kernels (cxk_count_sparse_affine); -1 before a first solve */
+int CONEX_HIP_CountSparseAffine(void* x) {
+  Program* p = static_cast<Program*>(x);
+  return p && p->ctx ? cxk_count_sparse_affine(p->ctx) : -1;
 }
 
 /* not part of conex.h: which quadratic cones are held in HBM and run on the streamed kernels (conex_kkt_hip.h,

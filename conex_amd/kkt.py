@@ -145,6 +145,9 @@ _SIGNATURES = {
     "cxk_set_wide_spectrum": (C.c_int, [C.c_void_p, C.c_int]),
     "cxk_count_wide_spectrum": (C.c_int, [C.c_void_p]),
     "cxk_add_soc_csr": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_int_p, c_int_p, c_double_p, c_double_p, c_int_p]),
+    "cxk_add_lmi_coo": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, c_double_p, c_int_p]),
+    "cxk_set_sparse_affine": (C.c_int, [C.c_void_p, C.c_int]),
+    "cxk_count_sparse_affine": (C.c_int, [C.c_void_p]),
     "cxk_count_tiled_linear": (C.c_int, [C.c_void_p]),
     "cxk_fused_tree_timed_out": (C.c_int, [C.c_void_p]),
     "cxk_debug_force_fused_timeout": (C.c_int, [C.c_void_p]),
@@ -261,6 +264,24 @@ class KktContext:
         r = self.L.cxk_add_lmi_factored(self.h, n, m, _ip(rp), _dp(f), None if sg is None else _dp(sg), _dp(c), vp)
         if r >= 0:
             self.cons.append(("lmi", n, m))
+        return r
+
+    def add_lmi_coo(self, n, ptr, row, col, val, vars_=None):
+        """The constraint of add_lmi, of order n, by the entries of the lower triangles: list i, row / col / val
+        [ptr[i]:ptr[i + 1]] with row >= col, holds A_i and the last list holds C; ptr has m + 2 entries, m = len(vars_)
+        or the context's variables.  Entries of a list in any order; explicit zeros are dropped.  The matrices are never
+        formed, and the constraint takes the sparse route only."""
+        pt = np.ascontiguousarray(ptr, dtype=np.int32)
+        rw = np.ascontiguousarray(row, dtype=np.int32)
+        cl = np.ascontiguousarray(col, dtype=np.int32)
+        vl = np.ascontiguousarray(val, dtype=np.float64)
+        keep, vp = self._vars(vars_)
+        m = self.num_vars if vars_ is None else len(keep)
+        if len(pt) != m + 2 or not (len(rw) == len(cl) == len(vl)) or pt[-1] > len(vl):
+            raise ValueError("add_lmi_coo: ptr has m + 2 entries and points into row / col / val of equal length")
+        r = self.L.cxk_add_lmi_coo(self.h, int(n), m, _ip(pt), _ip(rw), _ip(cl), _dp(vl), vp)
+        if r >= 0:
+            self.cons.append(("lmi", int(n), m))
         return r
 
     def add_linear(self, A, c, vars_=None):
@@ -891,6 +912,16 @@ class KktContext:
     def count_sparse_soc(self):
         """Constraints this context owns that run on the sparse second-order-cone kernels."""
         return self.L.cxk_count_sparse_soc(self.h)
+
+    def set_sparse_affine(self, mode=1):
+        """The affine term of sparse matrix inequalities of order 64 and up, when it has more than 64 nonzeros: 1 from
+        its nonzeros, 0 by two dense products, -1 from its nonzeros when that pays (before initialize; default:
+        CXK_SPARSE_AFFINE in the environment, else 0 for add_lmi / add_hermitian and -1 for add_lmi_coo)."""
+        self._check(self.L.cxk_set_sparse_affine(self.h, int(mode)), "cxk_set_sparse_affine")
+
+    def count_sparse_affine(self):
+        """Constraints this context owns whose affine term is evaluated from its nonzeros."""
+        return self.L.cxk_count_sparse_affine(self.h)
 
     def set_wide_spectrum(self, mode=1):
         """The Lanczos run of large-order matrix inequalities spread over the chip: 1 every large-order group, 0 none

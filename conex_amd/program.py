@@ -102,6 +102,34 @@ class _FactoredLMIOperator:
         return out
 
 
+class _EntriesLMIOperator:
+    """y -> sum_i y_i A_i and its adjoint for matrices given by the entries of their lower triangles (never formed
+    one by one; apply returns the n x n sum)."""
+
+    def __init__(self, n, ptr, row, col, val, num_vars, variables):
+        m = len(ptr) - 2
+        self.n, self.m = n, num_vars
+        self.row, self.col, self.val = row[:ptr[m]], col[:ptr[m]], val[:ptr[m]]
+        self.var = np.repeat(np.arange(m), np.diff(ptr[:m + 1]))
+        self.variables = np.arange(m) if variables is None else np.asarray(variables, dtype=np.int64)
+
+    def apply(self, y):
+        y = np.asarray(y, dtype=np.float64).ravel()[self.variables]
+        out = np.zeros((self.n, self.n))
+        w = self.val * y[self.var]
+        np.add.at(out, (self.row, self.col), w)
+        off = self.row != self.col
+        np.add.at(out, (self.col[off], self.row[off]), w[off])
+        return out
+
+    def adjoint(self, X):
+        X = np.asarray(X)
+        t = self.val * np.where(self.row == self.col, X[self.row, self.col], X[self.row, self.col] + X[self.col, self.row])
+        out = np.zeros(self.m)
+        np.add.at(out, self.variables[self.var], t)
+        return out
+
+
 def _f64(a):
     return np.ascontiguousarray(np.asarray(a, dtype=np.float64))
 
@@ -235,6 +263,41 @@ class Conex:
         self.c.append(c.copy())
         self.num_constraints += 1
         return cid
+
+    def AddLinearMatrixInequalityFromEntries(self, n, ptr, row, col, val, variables=None):
+        """c - sum_i y_i A_i positive semidefinite of order n with sparse symmetric A_i and c given by the entries of
+        their lower triangles and never expanded (CONEX_HIP_AddLMIConstraintFromEntries, an extra next to the reference's
+        surface): list i, ptr[i]:ptr[i + 1] of row / col / val with row >= col, holds A_i, the last list holds c; ptr has
+        two entries more than the constraint has variables (len(variables), or all when None).  Entries of a list come
+        in any order, explicit zeros are dropped, an empty list is the zero matrix.  UpdateLinearOperator and
+        UpdateAffineTerm fail on such a constraint.  Returns the constraint id."""
+        pt = np.ascontiguousarray(np.asarray(ptr).ravel(), dtype=np.int32)
+        rw = np.ascontiguousarray(np.asarray(row).ravel(), dtype=np.int32)
+        cl = np.ascontiguousarray(np.asarray(col).ravel(), dtype=np.int32)
+        vl = _f64(np.asarray(val, dtype=np.float64).ravel())
+        v = None if variables is None else np.ascontiguousarray(np.asarray(variables).ravel(), dtype=np.int64)
+        m = self.m if v is None else len(v)
+        if n < 1 or len(pt) != m + 2 or not (len(rw) == len(cl) == len(vl)) or pt[-1] > len(vl) or np.any(np.diff(pt) < 0):
+            raise ConexError("Invalid LMI")
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+        cid = self._L.CONEX_HIP_AddLMIConstraintFromEntries(
+            self.a, int(n), ip(pt), ip(rw), ip(cl), capi.dp(vl), m, None if v is None else v.ctypes.data_as(C.POINTER(C.c_long)))
+        if cid < 0:
+            raise ConexError("Failed to add constraint.")
+        self.A.append(_EntriesLMIOperator(int(n), pt, rw, cl, vl, self.m, v))
+        c = np.zeros((int(n), int(n)))
+        cs = slice(pt[m], pt[m + 1])
+        c[rw[cs], cl[cs]] = vl[cs]
+        c[cl[cs], rw[cs]] = vl[cs]
+        self.c.append(c)
+        self.num_constraints += 1
+        return cid
+
+    def SetSparseAffine(self, mode):
+        """How sparse matrix inequalities of order 64 and up evaluate an affine term of more than 64 nonzeros: 1 from
+        its nonzeros, 0 by two dense products, -1 from its nonzeros when that pays (CONEX_HIP_SetSparseAffine)."""
+        if self._L.CONEX_HIP_SetSparseAffine(self.a, int(mode)) != 0:
+            raise ConexError("Invalid mode.")
 
     def AddFactoredHermitianMatrixInequality(self, F, rank_ptr, sigma, c, variables=None):
         """c - sum_i y_i A_i positive semidefinite over R / C / H with low-rank Hermitian A_i = sum_k sigma[k] f_k f_k^*,

@@ -219,6 +219,38 @@ def maxcut_problem(n, edges_per_node=3, seed=SEED + 9):
     return dict(A=A, C=-Q[None], cliques=[list(range(n))], num_vars=n, b=-np.ones(n), n=n, m=n, Q=Q)
 
 
+def maxcut_entries(n, edges_per_node=3, seed=SEED + 9):
+    """The problem of maxcut_problem(n), from the same random stream, as the entry lists of KktContext.add_lmi_coo /
+    Conex.AddLinearMatrixInequalityFromEntries: list i < n holds A_i = -e_i e_i^T, list n the lower triangle of C = -Q.
+    Nothing of size n^3 (or n^2) is formed."""
+    rng = np.random.default_rng(seed)
+    w = {}
+    for _ in range(edges_per_node * n):
+        i, j = (int(t) for t in rng.integers(n, size=2))
+        if i != j:
+            w[(max(i, j), min(i, j))] = rng.uniform(0.2, 1.0)  # (a repeated edge keeps its last weight, as Q[i, j] = does)
+    # the degree sums in the order Q.sum(axis=1) adds a row: np.add.reduce over a contiguous row is pairwise, so the
+    # same routine does it here (a dense row per vertex, one at a time)
+    nbr = [[] for _ in range(n)]
+    for (i, j), v in w.items():
+        nbr[i].append((j, v))
+        nbr[j].append((i, v))
+    deg = np.zeros(n)
+    line = np.zeros(n)
+    for i in range(n):
+        line[:] = 0.0
+        for j, v in nbr[i]:
+            line[j] = v
+        deg[i] = line.sum()
+    keys = sorted(w)
+    row = np.r_[np.arange(n), np.arange(n), [k[0] for k in keys]].astype(np.int32)
+    col = np.r_[np.arange(n), np.arange(n), [k[1] for k in keys]].astype(np.int32)
+    # C = -Q, Q = 0.25 (diag(deg) - weights)
+    val = np.r_[-np.ones(n), -(0.25 * deg), -(0.25 * -np.array([w[k] for k in keys], dtype=np.float64))]
+    ptr = np.r_[np.arange(n + 1), 2 * n + len(keys)].astype(np.int32)
+    return dict(n=n, m=n, ptr=ptr, row=row, col=col, val=val, cliques=[list(range(n))], num_vars=n, b=-np.ones(n))
+
+
 def scaling_points(K, n, seed=SEED + 1, scale=0.3):
     """W_c = expm(scale * sym(R)): symmetric positive definite, W != I."""
     rng = np.random.default_rng(seed)

@@ -233,6 +233,35 @@ int cxk_add_soc_csr(cxk_context* ctx, int n, int m, const int* rowptr /* n + 2 *
 int cxk_set_wide_spectrum(cxk_context* ctx, int mode);
 int cxk_count_wide_spectrum(const cxk_context* ctx);
 
+/* Matrix inequalities given by their nonzeros (kernels_lmi_sparse.hip.h).  cxk_add_lmi_coo adds the constraint of
+ * cxk_add_lmi (DenseLMIConstraint semantics, real symmetric): list i < m, ptr[i] .. ptr[i + 1], holds the entries of
+ * A_i, list m those of C, as (row, col, val) with row >= col: the caller gives the lower triangle and the library
+ * mirrors it, so the data is symmetric by construction.  Entries of a list come in any order, explicit zeros are
+ * dropped, an empty list is the zero matrix.  Each mirrored list is sorted by column, then row -- the order in which a
+ * dense matrix given to cxk_add_lmi is scanned -- so the same data gives the same device lists and the same bits as
+ * cxk_add_lmi on the sparse route.  The record keeps the lists and the n x n square of C (the size of W); nothing of
+ * size m n^2 is allocated on the host or the device.  Returns -1 (cxk_last_error names the reason, prefixed
+ * "cxk_add_lmi_coo: ") for n < 1, m < 0, null pointers, ptr[0] != 0, a decreasing ptr, an index outside [0, n),
+ * row < col, a position named twice in a list, a value that is not finite, and n or m above 32767 (the entry table
+ * packs row | col << 16 and the pair table i | j << 16 into ints that the kernels unpack with signed shifts).  Such a
+ * constraint can only take the sparse route (cxk_count_sparse_lmi counts it) whatever LmiSparsePays says: with
+ * CXK_SPARSE_LMI=0 in force cxk_finalize refuses it by name.  Every getter, setter and output is that of an LMI.
+ * The affine term of a sparse LMI beyond the LDS-resident orders (order 64 and up) with more than 64 nonzeros is by
+ * default multiplied out, X = W C W, by two n^3 GEMMs.  cxk_set_sparse_affine, before cxk_finalize: mode 1 every such
+ * group instead forms (W C)' from C's nonzeros (n nnz(C) multiply-adds) and X only at the positions that an entry of
+ * some A_i or of C names (n multiply-adds each), then AQc, <c,Qc> and <w,c> from those; 0 none does (the GEMMs: the
+ * bits of before); -1 a constraint does when LmiSparseAffinePays(n, nnz(C), positions) (cone_route.h, measured).
+ * Without a call: the environment's CXK_SPARSE_AFFINE = -1 | 0 | 1, else 0 for a constraint added by cxk_add_lmi or
+ * cxk_add_hermitian (nothing that ran before changes its kernels or bits) and -1 for one added by cxk_add_lmi_coo.
+ * Constraints that differ in the outcome do not share a group.  Fixed summation orders, no atomics: two runs give the
+ * same bits; the values differ from the GEMM path's by rounding only.
+ * cxk_count_sparse_affine: constraints this context owns on those kernels (-1 before cxk_finalize; 0 on a host-only
+ * context); cxk_lmi_kernels reports "lmi_schur_sparse hbm sparse-C" for them. */
+int cxk_add_lmi_coo(cxk_context* ctx, int n, int m, const int* ptr /* m + 2 */, const int* row, const int* col,
+                    const double* val, const int* vars);
+int cxk_set_sparse_affine(cxk_context* ctx, int mode);
+int cxk_count_sparse_affine(const cxk_context* ctx);
+
 /* Low-rank matrix inequalities given by their factors (kernels_lmi_factored.hip.h).  cxk_add_lmi_factored adds the
  * constraint of cxk_add_lmi (DenseLMIConstraint semantics, real symmetric) with
  *   A_i = sum_k sigma_k f_k f_k',  k = rank_ptr[i] .. rank_ptr[i + 1] - 1,
@@ -581,7 +610,9 @@ int cxk_count_lmi_kernel(const cxk_context* ctx, int which);
 /* The kernel instance each per-constraint stage of LMI / Hermitian constraint `constraint` runs, as
  * codes 0 .. cxk_lmi_kernel_count() - 1 in out[stage] (stages below).  The launches choose through
  * the same functions.  Fails for a constraint of another type, one not owned by this rank, or before
- * initialize. */
+ * initialize.  One instance is no row of that list because it runs only where it was asked for: the Schur stage of
+ * a sparse LMI whose affine term is evaluated from its nonzeros (cxk_set_sparse_affine) reports the code
+ * cxk_lmi_kernel_count() + 1, which cxk_lmi_kernel_name names "lmi_schur_sparse hbm sparse-C". */
 enum {
   CXK_LMI_STAGE_SCHUR = 0,   /* Schur complement assembly */
   CXK_LMI_STAGE_PREPARE = 1, /* PrepareStep */
