@@ -1,6 +1,7 @@
 // Linear-inequality blocks on their three routes (kLinearLds, kLinearTiled, kLinearSparse): the views, the stages of
 // cxk_finalize and every launch.  Owns the kernels of kernels_linear / _linear_tiled / _linear_sparse; the other
-// vector cones reach vec_set_identity, the Gram product and the nonzero lists through the host functions here.
+// vector cones reach vec_set_identity, the Gram product and the nonzero lists through the host functions here, which
+// work on the GramWs / NonzeroLists they are handed.  The family's state is Group::lin (cone_state.h).
 #include "cone_units.h"
 #include "kernels_gemm.hip.h"
 #include "kernels_linear.hip.h"
@@ -20,56 +21,62 @@ VecGroup MakeVec(Group& g) {
   d.c = g.C.p;
   d.W = g.W.p;
   d.T1 = g.T1.p;
-  d.T2 = g.T2.p;
+  d.T2 = g.lin.T2.p;
   d.ids = g.dids.p;
   return d;
 }
-// The work space of the Gram product of LaunchGramLower, for streamed second-order cones (len = n + 1) and tiled
-// linear blocks (len = n) alike: the scaled copy of A in ws_main, the products in ws_gf, the split partials in ws_part.
-int AllocGramWorkspace(cxk_context* ctx, Group& g, size_t len, const FinalizeSwitches& sw) {
-  const size_t cnt = g.ids.size(), m = (size_t)g.m;
-  g.splits = SocStreamSplits((int)len, g.m, (long long)cnt);
-  if (sw.gram_splits > 0) g.splits = sw.gram_splits;  // (comparison runs)
-  CXK_TRY(g.ws_main.alloc(cnt * len * m));
-  CXK_TRY(g.ws_gf.alloc(cnt * m * m));
-  CXK_TRY(g.ws_part.alloc(g.splits > 1 ? (size_t)g.splits * std::min<size_t>(cnt, 65535) * m * m : 0));
+// The second temporary of the linear blocks' kernels, for every CXK_LINEAR group whatever its route (any other group
+// keeps the one element of an empty buffer: MakeVec hands the pointer on).
+int AllocLinearT2(cxk_context* ctx, Group& g) {
+  CXK_TRY(g.lin.T2.alloc(g.type == CXK_LINEAR ? (size_t)g.n * g.ids.size() : 0));
+  return CXK_SUCCESS;
+}
+// The work space of the Gram product of LaunchGramLower, for `cnt` streamed second-order cones (len = n + 1) or tiled
+// linear blocks (len = n) alike: the scaled copy of A, the products, the split partials.
+int AllocGramWorkspace(cxk_context* ctx, GramWs& w, size_t cnt, size_t len, size_t m, const FinalizeSwitches& sw) {
+  w.splits = SocStreamSplits((int)len, (int)m, (long long)cnt);
+  if (sw.gram_splits > 0) w.splits = sw.gram_splits;  // (comparison runs)
+  CXK_TRY(w.WA.alloc(cnt * len * m));
+  CXK_TRY(w.Gf.alloc(cnt * m * m));
+  CXK_TRY(w.part.alloc(w.splits > 1 ? (size_t)w.splits * std::min<size_t>(cnt, 65535) * m * m : 0));
   return CXK_SUCCESS;
 }
 LinTiledGroup MakeLinTiled(Group& g) {
   LinTiledGroup d;
   d.v = MakeVec(g);
-  d.WA = g.ws_main.p;
-  d.Gf = g.ws_gf.p;
-  d.part = g.lt_part.p;
+  d.WA = g.lin.gram.WA.p;
+  d.Gf = g.lin.gram.Gf.p;
+  d.part = g.lin.tile_part.p;
   return d;
 }
 int UploadLinearTiled(cxk_context* ctx, Group& g, const FinalizeSwitches& sw) {
   const size_t cnt = g.ids.size(), len = (size_t)g.n, m = (size_t)g.m, tiles = (len + kLinTiledRowTile - 1) / kLinTiledRowTile;
   CXK_DEMAND(cnt * std::max(m, tiles) <= (size_t)INT_MAX,
              "a group of tiled linear blocks with more than 2^31 columns or row tiles is not supported");
-  if (AllocGramWorkspace(ctx, g, len, sw)) return CXK_FAILURE;
-  CXK_TRY(g.lt_part.alloc(cnt * tiles * 4));
+  if (AllocGramWorkspace(ctx, g.lin.gram, cnt, len, m, sw)) return CXK_FAILURE;
+  CXK_TRY(g.lin.tile_part.alloc(cnt * tiles * 4));
   return CXK_SUCCESS;
 }
 LinSparseGroup MakeLinSparse(Group& g) {
   LinSparseGroup d;
   d.t = MakeLinTiled(g);  // (A is null, WA and Gf unused: the scalars and finish kernels read v and part only)
-  d.eptr = g.ls_eptr.p;
-  d.rowptr = g.ls_rowptr.p;
-  d.col = g.ls_col.p;
-  d.val = g.ls_val.p;
-  d.colptr = g.ls_colptr.p;
-  d.crow = g.ls_crow.p;
-  d.cval = g.ls_cval.p;
+  const NonzeroLists& nz = g.lin.nz;
+  d.eptr = nz.eptr.p;
+  d.rowptr = nz.rowptr.p;
+  d.col = nz.col.p;
+  d.val = nz.val.p;
+  d.colptr = nz.colptr.p;
+  d.crow = nz.crow.p;
+  d.cval = nz.cval.p;
   return d;
 }
 int UploadLinearSparse(cxk_context* ctx, Group& g) {
   const size_t cnt = g.ids.size(), len = (size_t)g.n, m = (size_t)g.m, tiles = (len + kLinTiledRowTile - 1) / kLinTiledRowTile;
   const size_t chunks = m <= (size_t)kLinSparseWaveCols ? 1 : (m + kLinSparseColChunk - 1) / kLinSparseColChunk;
-  if (UploadSparseNonzeros(ctx, g)) return CXK_FAILURE;
+  if (UploadSparseNonzeros(ctx, g, g.lin.nz)) return CXK_FAILURE;
   CXK_DEMAND(cnt * std::max(m * chunks, tiles) <= (size_t)INT_MAX,
              "a group of sparse linear blocks with more than 2^31 column chunks or row tiles is not supported");
-  CXK_TRY(g.lt_part.alloc(cnt * tiles * 4));
+  CXK_TRY(g.lin.tile_part.alloc(cnt * tiles * 4));
   return CXK_SUCCESS;
 }
 
@@ -77,65 +84,66 @@ int UploadLinearSparse(cxk_context* ctx, Group& g) {
 // columns ascending.
 void LinearNonzeros(ConstraintRec* c) {
   const size_t rows = (size_t)c->n + (c->type == CXK_SOC ? 1 : 0);
-  c->sp_rowptr.assign(rows + 1, 0);
+  ConstraintRec::RowNonzeros& nz = c->rows;
+  nz.ptr.assign(rows + 1, 0);
   for (int j = 0; j < c->m; j++)
-    for (size_t r = 0; r < rows; r++) c->sp_rowptr[r + 1] += c->A[r + (size_t)j * rows] != 0.0;
-  for (size_t r = 0; r < rows; r++) c->sp_rowptr[r + 1] += c->sp_rowptr[r];
-  c->sp_col.resize((size_t)c->sp_rowptr[rows]);
-  c->sp_val.resize((size_t)c->sp_rowptr[rows]);
-  std::vector<int> next(c->sp_rowptr.begin(), c->sp_rowptr.end() - 1);
+    for (size_t r = 0; r < rows; r++) nz.ptr[r + 1] += c->A[r + (size_t)j * rows] != 0.0;
+  for (size_t r = 0; r < rows; r++) nz.ptr[r + 1] += nz.ptr[r];
+  nz.col.resize((size_t)nz.ptr[rows]);
+  nz.val.resize((size_t)nz.ptr[rows]);
+  std::vector<int> next(nz.ptr.begin(), nz.ptr.end() - 1);
   for (int j = 0; j < c->m; j++)
     for (size_t r = 0; r < rows; r++) {
       const double v = c->A[r + (size_t)j * rows];
       if (v != 0.0) {
-        c->sp_col[(size_t)next[r]] = j;
-        c->sp_val[(size_t)next[r]++] = v;
+        nz.col[(size_t)next[r]] = j;
+        nz.val[(size_t)next[r]++] = v;
       }
     }
 }
 
 // The device copy of a group of linear blocks (rows = n) or second-order cones (rows = n + 1) on the sparse route:
-// every member's nonzeros by rows and by columns.
-int UploadSparseNonzeros(cxk_context* ctx, Group& g) {
+// every member's nonzeros by rows and by columns, into its family's lists.
+int UploadSparseNonzeros(cxk_context* ctx, const Group& g, NonzeroLists& nz) {
   const size_t cnt = g.ids.size(), rows = (size_t)g.n + (g.type == CXK_SOC ? 1 : 0), m = (size_t)g.m;
   size_t total = 0;
-  for (size_t k = 0; k < cnt; k++) total += ctx->cons[g.ids[k]].sp_col.size();
+  for (size_t k = 0; k < cnt; k++) total += ctx->cons[g.ids[k]].rows.col.size();
   CXK_DEMAND(total <= (size_t)INT_MAX, g.type == CXK_SOC
                                            ? "a group of sparse second-order cones with more than 2^31 nonzeros is not supported"
                                            : "a group of sparse linear blocks with more than 2^31 nonzeros is not supported");
   std::vector<int> eptr(cnt + 1, 0), rowptr(cnt * (rows + 1)), colptr(cnt * (m + 1), 0), col(total), crow(total);
   std::vector<double> val(total), cval(total);
   for (size_t k = 0; k < cnt; k++) {
-    const ConstraintRec& c = ctx->cons[g.ids[k]];
+    const ConstraintRec::RowNonzeros& c = ctx->cons[g.ids[k]].rows;
     const size_t base = (size_t)eptr[k];
-    eptr[k + 1] = (int)(base + c.sp_col.size());
-    std::copy(c.sp_rowptr.begin(), c.sp_rowptr.end(), rowptr.begin() + k * (rows + 1));
-    std::copy(c.sp_col.begin(), c.sp_col.end(), col.begin() + base);
-    std::copy(c.sp_val.begin(), c.sp_val.end(), val.begin() + base);
+    eptr[k + 1] = (int)(base + c.col.size());
+    std::copy(c.ptr.begin(), c.ptr.end(), rowptr.begin() + k * (rows + 1));
+    std::copy(c.col.begin(), c.col.end(), col.begin() + base);
+    std::copy(c.val.begin(), c.val.end(), val.begin() + base);
     int* cp = colptr.data() + k * (m + 1);
-    for (int v : c.sp_col) cp[v + 1]++;
+    for (int v : c.col) cp[v + 1]++;
     for (size_t j = 0; j < m; j++) cp[j + 1] += cp[j];
     std::vector<int> next(cp, cp + m);
     for (size_t r = 0; r < rows; r++)  // (rows in order: every column's rows come out ascending)
-      for (int s = c.sp_rowptr[r]; s < c.sp_rowptr[r + 1]; s++) {
-        const size_t at = base + (size_t)next[(size_t)c.sp_col[(size_t)s]]++;
+      for (int s = c.ptr[r]; s < c.ptr[r + 1]; s++) {
+        const size_t at = base + (size_t)next[(size_t)c.col[(size_t)s]]++;
         crow[at] = (int)r;
-        cval[at] = c.sp_val[(size_t)s];
+        cval[at] = c.val[(size_t)s];
       }
   }
-  CXK_TRY(g.ls_eptr.upload(eptr));
-  CXK_TRY(g.ls_rowptr.upload(rowptr));
-  CXK_TRY(g.ls_col.upload(col));
-  CXK_TRY(g.ls_val.upload(val));
-  CXK_TRY(g.ls_colptr.upload(colptr));
-  CXK_TRY(g.ls_crow.upload(crow));
-  CXK_TRY(g.ls_cval.upload(cval));
+  CXK_TRY(nz.eptr.upload(eptr));
+  CXK_TRY(nz.rowptr.upload(rowptr));
+  CXK_TRY(nz.col.upload(col));
+  CXK_TRY(nz.val.upload(val));
+  CXK_TRY(nz.colptr.upload(colptr));
+  CXK_TRY(nz.crow.upload(crow));
+  CXK_TRY(nz.cval.upload(cval));
   return CXK_SUCCESS;
 }
 
 // Gf = alpha WA' WA of every member of a group (WA: len x m per member), lower triangles only: the batched GEMM with
 // SYRK-shaped output, split along len when that is long (the work space of AllocGramWorkspace).
-hipError_t LaunchGramLower(Group& g, const double* WA, double* Gf, int cnt, int len, int m, double alpha, hipStream_t st) {
+hipError_t LaunchGramLower(const GramWs& w, const double* WA, double* Gf, int cnt, int len, int m, double alpha, hipStream_t st) {
   const int64_t mm = (int64_t)m * m;
   constexpr int kMaxBatch = 65535;  // gridDim.z
   for (int b0 = 0; b0 < cnt; b0 += kMaxBatch) {
@@ -153,9 +161,9 @@ hipError_t LaunchGramLower(Group& g, const double* WA, double* Gf, int cnt, int 
     a.alpha = alpha;
     a.beta = 0.0;
     a.lower_only = 1;
-    a.splits = g.splits;
+    a.splits = w.splits;
     a.sCs = (int64_t)std::min(cnt, kMaxBatch) * mm;
-    const hipError_t e = LaunchGemmSplitK(a, true, false, nb, g.ws_part.p, st);
+    const hipError_t e = LaunchGemmSplitK(a, true, false, nb, w.part.p, st);
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
@@ -174,7 +182,7 @@ hipError_t LaunchLinearTiledSchur(Group& g, const Arena& ar, hipStream_t st) {
   linear_tiled_scalars<<<cnt, kLinTiledBlock, 0, st>>>(d, ar);
   if (m == 0) return hipGetLastError();
   linear_tiled_apply<<<(unsigned)((size_t)cnt * m), kLinTiledBlock, 0, st>>>(d, ar);
-  const hipError_t e = LaunchGramLower(g, d.WA, d.Gf, cnt, len, m, 1.0, st);
+  const hipError_t e = LaunchGramLower(g.lin.gram, d.WA, d.Gf, cnt, len, m, 1.0, st);
   if (e != hipSuccess) return e;
   linear_tiled_mirror<<<GridFor((size_t)cnt * m * m, kLinTiledBlock), kLinTiledBlock, 0, st>>>(d, ar);
   return hipGetLastError();

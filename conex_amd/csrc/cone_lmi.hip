@@ -1,6 +1,7 @@
 // Matrix inequalities on their three routes (kLmiDense, kLmiSparse, kLmiFactored): the views, the stages of
 // cxk_finalize, the choosers that name the kernel instance of each stage, and every launch.  Owns the kernels of
-// kernels_lmi / _lmi_sparse / _lmi_rows / _lmi_large / _lmi_wide / _lmi_factored.
+// kernels_lmi / _lmi_sparse / _lmi_rows / _lmi_large / _lmi_wide / _lmi_factored.  The family's state is Group::lmi
+// (cone_state.h).
 #include "cone_units.h"
 #include "kernels_gemm.hip.h"
 #include "kernels_lmi.hip.h"
@@ -22,21 +23,21 @@ LmiGroup MakeLmi(Group& g) {
   d.m = g.m;
   d.count = static_cast<int>(g.ids.size());
   d.A = g.A.p;
-  d.a_stride = (long long)(g.assembly != LmiAssembly::kGeneric ? g.m + 1 : g.m) * g.n * g.n;
+  d.a_stride = (long long)(g.lmi.assembly != LmiAssembly::kGeneric ? g.m + 1 : g.m) * g.n * g.n;
   d.C = g.C.p;
   d.W = g.W.p;
   d.T1 = g.T1.p;
   d.ids = g.dids.p;
-  d.Apk = g.Apk.n ? g.Apk.p : nullptr;
+  d.Apk = g.lmi.Apk.n ? g.lmi.Apk.p : nullptr;
   d.herm_d = g.herm_d;
   const bool sparse = g.route == ConeRoute::kLmiSparse;
-  d.sp_eptr = sparse ? g.sp_eptr.p : nullptr;
-  d.sp_erc = sparse ? g.sp_erc.p : nullptr;
-  d.sp_pairs = sparse ? g.sp_pairs.p : nullptr;
-  d.sp_eval = sparse ? g.sp_eval.p : nullptr;
-  d.sp_pptr = sparse ? g.sp_pptr.p : nullptr;
-  d.sp_pvar = sparse ? g.sp_pvar.p : nullptr;
-  d.sp_pval = sparse ? g.sp_pval.p : nullptr;
+  d.sp_eptr = sparse ? g.lmi.sp.eptr.p : nullptr;
+  d.sp_erc = sparse ? g.lmi.sp.erc.p : nullptr;
+  d.sp_pairs = sparse ? g.lmi.sp.pairs.p : nullptr;
+  d.sp_eval = sparse ? g.lmi.sp.eval.p : nullptr;
+  d.sp_pptr = sparse ? g.lmi.sp.pptr.p : nullptr;
+  d.sp_pvar = sparse ? g.lmi.sp.pvar.p : nullptr;
+  d.sp_pval = sparse ? g.lmi.sp.pval.p : nullptr;
   return d;
 }
 static int AllocGemmAssembly(cxk_context* ctx, Group& g, const FinalizeSwitches& sw);
@@ -45,7 +46,7 @@ static int AllocGemmAssembly(cxk_context* ctx, Group& g, const FinalizeSwitches&
 // space of the GEMM assembly (beside MakeLargeWs).
 int UploadLmiDense(cxk_context* ctx, Group& g, const FinalizeSwitches& sw) {
   const size_t cnt = g.ids.size();
-  if (g.assembly == LmiAssembly::kMfma && LmiMfmaPaddedOrder(g.n) != g.n && !(g.herm_d == 2 && g.n == 24)) {
+  if (g.lmi.assembly == LmiAssembly::kMfma && LmiMfmaPaddedOrder(g.n) != g.n && !(g.herm_d == 2 && g.n == 24)) {
     const int np = LmiMfmaPaddedOrder(g.n), n = g.n;
     const size_t blk = (size_t)(g.m + 1) * np * np;
     std::vector<double> hp(blk * cnt, 0.0);
@@ -57,9 +58,9 @@ int UploadLmiDense(cxk_context* ctx, Group& g, const FinalizeSwitches& sw) {
         for (int col = 0; col < n; col++) std::copy(src + (size_t)col * n, src + (size_t)col * n + n, dst + (size_t)col * np);
       }
     }
-    CXK_TRY(g.Apad.upload(hp));
+    CXK_TRY(g.lmi.Apad.upload(hp));
   }
-  if (g.herm_d > 1 && g.assembly == LmiAssembly::kGemm && !g.literal && !sw.no_herm_fold) {
+  if (g.herm_d > 1 && g.lmi.assembly == LmiAssembly::kGemm && !g.lmi.literal && !sw.no_herm_fold) {
     // Hermitian cones over C / H on the batched-GEMM assembly: the folded form needs only the first
     // n / herm_d columns of every matrix of the real representation (kernels_lmi_large.hip.h)
     const int n = g.n, n0 = g.n / g.herm_d;
@@ -72,9 +73,9 @@ int UploadLmiDense(cxk_context* ctx, Group& g, const FinalizeSwitches& sw) {
         std::copy(src, src + per, hl.begin() + (k * m1 + i) * per);
       }
     }
-    CXK_TRY(g.Aleft.upload(hl));
+    CXK_TRY(g.lmi.Aleft.upload(hl));
   }
-  if (!g.literal && !sw.no_packed_slack && g.n == 20 && LmiPrepareRowsSupports(g.n, g.m, g.herm_d, false)) {
+  if (!g.lmi.literal && !sw.no_packed_slack && g.n == 20 && LmiPrepareRowsSupports(g.n, g.m, g.herm_d, false)) {
     // the slack pass of PrepareStep / the eigenvalue query streams every A_i once more per call: a
     // packed copy of the lower triangles (the data is exactly symmetric) halves those bytes
     const int n = g.n, pk = n * (n + 1) / 2;
@@ -88,18 +89,18 @@ int UploadLmiDense(cxk_context* ctx, Group& g, const FinalizeSwitches& sw) {
           for (int row = col; row < n; row++) *dst++ = src[row + (size_t)col * n];
       }
     }
-    CXK_TRY(g.Apk.upload(hp));
+    CXK_TRY(g.lmi.Apk.upload(hp));
   }
-  return g.assembly == LmiAssembly::kGemm ? AllocGemmAssembly(ctx, g, sw) : CXK_SUCCESS;
+  return g.lmi.assembly == LmiAssembly::kGemm ? AllocGemmAssembly(ctx, g, sw) : CXK_SUCCESS;
 }
 // A sparse LMI group: its entry lists, and beyond the LDS-resident shapes the large-order work space.
 int UploadLmiSparse(cxk_context* ctx, Group& g) {
   const size_t cnt = g.ids.size(), nn = (size_t)g.n * g.n;
   if (UploadSparseLmi(ctx, g)) return CXK_FAILURE;
-  if (g.large || !g.sp_small) {
-    CXK_TRY(g.ws_main.alloc(cnt * 8 * nn));  // step temporaries; C W and W C W during assembly
-    CXK_TRY(g.ws_part.alloc(cnt * 2 * kSparseCParts));
-    CXK_TRY(g.ws_piv.alloc(cnt * (size_t)g.n));
+  if (g.lmi.large || !g.lmi.sp.small) {
+    CXK_TRY(g.lmi.ws_main.alloc(cnt * 8 * nn));  // step temporaries; C W and W C W during assembly
+    CXK_TRY(g.lmi.ws_part.alloc(cnt * 2 * kSparseCParts));
+    CXK_TRY(g.lmi.ws_piv.alloc(cnt * (size_t)g.n));
   }
   return CXK_SUCCESS;
 }
@@ -107,17 +108,17 @@ int UploadLmiSparse(cxk_context* ctx, Group& g) {
 LmiLargeWs MakeLargeWs(Group& g) {
   LmiLargeWs w;
   const size_t cnt = g.ids.size(), nn = (size_t)g.n * g.n, m1 = (size_t)g.m + 1;
-  w.P = g.ws_main.p;
-  w.PT = g.ws_main.p + cnt * m1 * nn;
-  w.tmp = g.ws_main.p;
-  w.Gf = g.ws_gf.p;
-  w.part = g.ws_part.p;
-  w.piv = g.ws_piv.p;
-  w.splits = g.splits;
-  w.fold = g.Aleft.n ? g.n / g.herm_d : 0;
-  w.Aleft = g.Aleft.p;
-  w.wide = g.ws_wide.n ? g.ws_wide.p : nullptr;
-  w.wide_reduce = g.wide_reduce;
+  w.P = g.lmi.ws_main.p;
+  w.PT = g.lmi.ws_main.p + cnt * m1 * nn;
+  w.tmp = g.lmi.ws_main.p;
+  w.Gf = g.lmi.ws_gf.p;
+  w.part = g.lmi.ws_part.p;
+  w.piv = g.lmi.ws_piv.p;
+  w.splits = g.lmi.splits;
+  w.fold = g.lmi.Aleft.n ? g.n / g.herm_d : 0;
+  w.Aleft = g.lmi.Aleft.p;
+  w.wide = g.lmi.ws_wide.n ? g.lmi.ws_wide.p : nullptr;
+  w.wide_reduce = g.lmi.wide_reduce;
   return w;
 }
 
@@ -130,12 +131,12 @@ static int AllocGemmAssembly(cxk_context* ctx, Group& g, const FinalizeSwitches&
   const int tiles = (int)(((m1 + 63) / 64) * ((m1 + 63) / 64));
   // (measured on BASELINE config 2, one constraint, K = 40 000: 39 / 78 / 156 / 312 / 512 / 768 / 1024
   // splits -> 115 / 93 / 82 / 81 / 76 / 80 / 82 us per KKT solve)
-  g.splits = std::max(1, std::min(std::max(1, ksteps / 4), (int)((512 + cnt * tiles - 1) / (cnt * tiles))));
-  if (sw.gram_splits > 0) g.splits = sw.gram_splits;  // (comparison runs)
-  CXK_TRY(g.ws_main.alloc(cnt * std::max(2 * m1 * nn, 8 * nn)));
-  CXK_TRY(g.ws_gf.alloc(cnt * m1 * m1));
-  CXK_TRY(g.ws_piv.alloc(cnt * (size_t)g.n));
-  CXK_TRY(g.ws_part.alloc(g.splits > 1 ? (size_t)g.splits * cnt * m1 * m1 : 0));
+  g.lmi.splits = std::max(1, std::min(std::max(1, ksteps / 4), (int)((512 + cnt * tiles - 1) / (cnt * tiles))));
+  if (sw.gram_splits > 0) g.lmi.splits = sw.gram_splits;  // (comparison runs)
+  CXK_TRY(g.lmi.ws_main.alloc(cnt * std::max(2 * m1 * nn, 8 * nn)));
+  CXK_TRY(g.lmi.ws_gf.alloc(cnt * m1 * m1));
+  CXK_TRY(g.lmi.ws_piv.alloc(cnt * (size_t)g.n));
+  CXK_TRY(g.lmi.ws_part.alloc(g.lmi.splits > 1 ? (size_t)g.lmi.splits * cnt * m1 * m1 : 0));
   return CXK_SUCCESS;
 }
 
@@ -147,19 +148,19 @@ int LmiLargeSpectrumMaxOrder() {
 
 LmiFactoredGroup MakeLmiFactored(Group& g) {
   LmiFactoredGroup f{};
-  const size_t cnt = g.ids.size(), nr = (size_t)g.n * g.f_R;
-  f.R = g.f_R;
+  const size_t cnt = g.ids.size(), nr = (size_t)g.n * g.lmi.f.R;
+  f.R = g.lmi.f.R;
   f.d = g.herm_d > 1 ? g.herm_d : 1;
-  f.rank_one = g.f_rank_one;
-  f.F = g.f_F.p;
-  f.sigma = g.f_sigma.p;
-  f.ptr = g.f_ptr.p;
-  f.var = g.f_var.p;
-  f.Z = g.f_ws.p;  // (the layout UploadLmiFactored sizes: LmiFactoredWsDoubles)
+  f.rank_one = g.lmi.f.rank_one;
+  f.F = g.lmi.f.F.p;
+  f.sigma = g.lmi.f.sigma.p;
+  f.ptr = g.lmi.f.ptr.p;
+  f.var = g.lmi.f.var.p;
+  f.Z = g.lmi.f.ws.p;  // (the layout UploadLmiFactored sizes: LmiFactoredWsDoubles)
   f.Y = f.Z + cnt * nr;
   f.Fs = f.Y + cnt * nr;
   f.P = f.Fs + cnt * nr * f.d;
-  f.part = g.ws_part.p;
+  f.part = g.lmi.ws_part.p;
   f.npart = kSparseCParts;
   return f;
 }
@@ -169,36 +170,36 @@ size_t LmiFactoredWsDoubles(size_t cnt, size_t n, size_t R, size_t d) { return c
 // A group of LMIs given by factors: every member's F, sigma, column pointers and column -> variable map, the work
 // space of the factored kernels and of the large-order step kernels behind them.
 int UploadLmiFactored(cxk_context* ctx, Group& g) {
-  const size_t cnt = g.ids.size(), n = (size_t)g.n, R = (size_t)g.f_R, m = (size_t)g.m;
-  const size_t d = g.herm_d > 1 ? (size_t)g.herm_d : 1;  // (a Hermitian member's f_F is L(F): n x dR)
+  const size_t cnt = g.ids.size(), n = (size_t)g.n, R = (size_t)g.lmi.f.R, m = (size_t)g.m;
+  const size_t d = g.herm_d > 1 ? (size_t)g.herm_d : 1;  // (a Hermitian member's factors.F is L(F): n x dR)
   CXK_DEMAND(cnt <= 65535, "a group of more than 65535 equal-shaped factored LMIs is not supported");
   std::vector<double> hF(cnt * n * R * d), hs(cnt * R);
   std::vector<int> hp(cnt * (m + 1)), hv(cnt * R);
-  g.f_rank_one = true;
+  g.lmi.f.rank_one = true;
   for (size_t k = 0; k < cnt; k++) {
     const ConstraintRec& c = ctx->cons[g.ids[k]];
-    std::copy(c.f_F.begin(), c.f_F.end(), hF.begin() + k * n * R * d);
-    std::copy(c.f_sigma.begin(), c.f_sigma.end(), hs.begin() + k * R);
-    std::copy(c.f_ptr.begin(), c.f_ptr.end(), hp.begin() + k * (m + 1));
+    std::copy(c.factors.F.begin(), c.factors.F.end(), hF.begin() + k * n * R * d);
+    std::copy(c.factors.sigma.begin(), c.factors.sigma.end(), hs.begin() + k * R);
+    std::copy(c.factors.ptr.begin(), c.factors.ptr.end(), hp.begin() + k * (m + 1));
     for (size_t i = 0; i < m; i++) {
-      g.f_rank_one = g.f_rank_one && c.f_ptr[i + 1] - c.f_ptr[i] == 1;
-      for (int q = c.f_ptr[i]; q < c.f_ptr[i + 1]; q++) hv[k * R + (size_t)q] = (int)i;
+      g.lmi.f.rank_one = g.lmi.f.rank_one && c.factors.ptr[i + 1] - c.factors.ptr[i] == 1;
+      for (int q = c.factors.ptr[i]; q < c.factors.ptr[i + 1]; q++) hv[k * R + (size_t)q] = (int)i;
     }
   }
-  CXK_TRY(g.f_F.upload(hF));
-  CXK_TRY(g.f_sigma.upload(hs));
-  CXK_TRY(g.f_ptr.upload(hp));
-  CXK_TRY(g.f_var.upload(hv));
-  CXK_TRY(g.f_ws.alloc(LmiFactoredWsDoubles(cnt, n, R, d)));
-  CXK_TRY(g.ws_main.alloc(cnt * 8 * n * n));  // step temporaries; C W and W C W during assembly
-  CXK_TRY(g.ws_part.alloc(cnt * 2 * kSparseCParts));
-  CXK_TRY(g.ws_piv.alloc(cnt * n));
+  CXK_TRY(g.lmi.f.F.upload(hF));
+  CXK_TRY(g.lmi.f.sigma.upload(hs));
+  CXK_TRY(g.lmi.f.ptr.upload(hp));
+  CXK_TRY(g.lmi.f.var.upload(hv));
+  CXK_TRY(g.lmi.f.ws.alloc(LmiFactoredWsDoubles(cnt, n, R, d)));
+  CXK_TRY(g.lmi.ws_main.alloc(cnt * 8 * n * n));  // step temporaries; C W and W C W during assembly
+  CXK_TRY(g.lmi.ws_part.alloc(cnt * 2 * kSparseCParts));
+  CXK_TRY(g.lmi.ws_piv.alloc(cnt * n));
   return CXK_SUCCESS;
 }
 
 // What Choose (cone_route.h) asks about an LMI added with its dense matrices.
 void MeasureLmi(const ConstraintRec& c, ConeShape* s) {
-  double nnz = c.csr_only ? (double)c.e_ptr[c.m] : 0;  // (held by its nonzeros: A is empty)
+  double nnz = c.csr_only ? (double)c.entries.ptr[c.m] : 0;  // (held by its nonzeros: A is empty)
   for (double v : c.A) nnz += (v != 0.0);
   s->mfma_supports = LmiMfmaSupports(c.n, c.m, c.herm_d);
   s->sparse_pays = LmiSparsePays(c.n, c.m, nnz, LmiLdsResident(c.n, c.m), s->mfma_supports);
@@ -208,16 +209,20 @@ void MeasureLmi(const ConstraintRec& c, ConeShape* s) {
 // whether it is `large`, and for a large group the work space of the chip-wide Lanczos run.
 int PlanLmiGroup(cxk_context* ctx, Group& g, const FinalizeSwitches& sw) {
   const size_t cnt = g.ids.size();
-  const LmiAssemblyChoice a = ChooseLmiAssembly(g.route, g.n, g.m, cnt, g.literal, LmiMfmaSupports(g.n, g.m, g.herm_d),
+  const LmiAssemblyChoice a = ChooseLmiAssembly(g.route, g.n, g.m, cnt, g.lmi.literal, LmiMfmaSupports(g.n, g.m, g.herm_d),
                                                 sw.schur_generic, sw.gemm_min_n);
-  g.large = a.large;
-  g.assembly = a.assembly;
+  g.lmi.large = a.large;
+  g.lmi.assembly = a.assembly;
   const int wide = WideSpectrumMode(ctx, sw);
-  if (g.large && (wide == 1 || (wide == -1 && g.n > LmiLargeSpectrumMaxOrder())))
-    CXK_TRY(g.ws_wide.alloc(cnt * LmiWideDoubles(g.n, g.herm_d)));
-  g.wide_reduce = g.n >= (sw.wide_reduce_min_order >= 0 ? sw.wide_reduce_min_order : kWideReduceMinOrder);
+  if (g.lmi.large && (wide == 1 || (wide == -1 && g.n > LmiLargeSpectrumMaxOrder())))
+    CXK_TRY(g.lmi.ws_wide.alloc(cnt * LmiWideDoubles(g.n, g.herm_d)));
+  g.lmi.wide_reduce = g.n >= (sw.wide_reduce_min_order >= 0 ? sw.wide_reduce_min_order : kWideReduceMinOrder);
   return CXK_SUCCESS;
 }
+
+// What the C-ABI unit counts (cxk_count_lmi_kernel, cxk_count_wide_spectrum).
+LmiAssembly LmiAssemblyOf(const Group& g) { return g.lmi.assembly; }
+bool LmiOnWideSpectrum(const Group& g) { return g.lmi.ws_wide.n != 0; }
 
 // StepTailOk: lmi_prepare_rows, the kernel that carries the tail workgroup, has an instance for the group's shape.
 bool LmiRowsServePrepare(const Group& g) {
@@ -326,17 +331,17 @@ LmiKernel LmiSchurKernel(const Group& g) {
   // not one of the instances: a code outside the reported range, which no Is*() test accepts and
   // cxk_lmi_kernel_name has no name for (LaunchSchur switches on the route first, cxk_lmi_kernels refuses the constraint)
   if (g.route == ConeRoute::kLmiFactored) return kLmiKernelCount;
-  if (g.route == ConeRoute::kLmiSparse && g.sp_affine) return kSchurSparseAffine;
-  if (g.route == ConeRoute::kLmiSparse) return (LmiKernel)((g.sp_small ? kSchurSparseSmall : kSchurSparse) + (g.sp_cdense ? 1 : 0));
-  if (g.assembly == LmiAssembly::kGemm) {  // (fold and split counts as LmiLargeSchur reads them: MakeLargeWs, LmiFoldedSplits)
-    const bool fold = g.Aleft.n != 0;
-    const int splits = fold ? LmiFoldedSplits(g.splits, g.n, g.n / g.herm_d) : g.splits;
-    return (LmiKernel)(kSchurGemm + (fold ? 4 : 0) + (g.large ? 2 : 0) + (splits > 1 ? 1 : 0));
+  if (g.route == ConeRoute::kLmiSparse && g.lmi.sa.on) return kSchurSparseAffine;
+  if (g.route == ConeRoute::kLmiSparse) return (LmiKernel)((g.lmi.sp.small ? kSchurSparseSmall : kSchurSparse) + (g.lmi.sp.cdense ? 1 : 0));
+  if (g.lmi.assembly == LmiAssembly::kGemm) {  // (fold and split counts as LmiLargeSchur reads them: MakeLargeWs, LmiFoldedSplits)
+    const bool fold = g.lmi.Aleft.n != 0;
+    const int splits = fold ? LmiFoldedSplits(g.lmi.splits, g.n, g.n / g.herm_d) : g.lmi.splits;
+    return (LmiKernel)(kSchurGemm + (fold ? 4 : 0) + (g.lmi.large ? 2 : 0) + (splits > 1 ? 1 : 0));
   }
-  if (g.assembly == LmiAssembly::kMfma) {
+  if (g.lmi.assembly == LmiAssembly::kMfma) {
     const LmiMfmaInstance inst = LmiMfmaChoose(g.n, g.m, g.herm_d);
     if (inst.folded) return inst.single ? kSchurMfma24FoldedSingle : kSchurMfma24Folded;
-    const bool pad = g.Apad.p != nullptr;
+    const bool pad = g.lmi.Apad.p != nullptr;
     switch (inst.order) {
       case 8: return pad ? kSchurMfma8Pad : kSchurMfma8;
       case 12: return pad ? kSchurMfma12Pad : kSchurMfma12;
@@ -345,15 +350,15 @@ LmiKernel LmiSchurKernel(const Group& g) {
       default: return (LmiKernel)(kSchurMfma24 + (pad ? 2 : 0) + (inst.single ? 1 : 0));
     }
   }
-  return g.literal ? kSchurGenericLiteral : kSchurGenericSym;
+  return g.lmi.literal ? kSchurGenericLiteral : kSchurGenericSym;
 }
 
 // mode 0 PrepareStep, 1 the eigenvalue query, 2 the affine update
 LmiKernel LmiPrepareKernel(const cxk_context* ctx, const Group& g, int mode) {
   const int base = mode == 0 ? kPrepareRowsPacked : kQueryRowsPacked;
-  if (g.large) return mode == 2 ? kAffineLarge : (LmiKernel)(base + 6);
-  if (mode != 2 && !ctx->prepare_lds && !g.literal && LmiPrepareRowsSupports(g.n, g.m, g.herm_d, g.route == ConeRoute::kLmiSparse)) {
-    if (g.n == 20) return (LmiKernel)(base + (g.Apk.p ? 0 : 1));
+  if (g.lmi.large) return mode == 2 ? kAffineLarge : (LmiKernel)(base + 6);
+  if (mode != 2 && !ctx->prepare_lds && !g.lmi.literal && LmiPrepareRowsSupports(g.n, g.m, g.herm_d, g.route == ConeRoute::kLmiSparse)) {
+    if (g.n == 20) return (LmiKernel)(base + (g.lmi.Apk.p ? 0 : 1));
     return (LmiKernel)(base + ((g.n & 1) ? 2 : 3));
   }
   if (mode == 2) return g.n == 20 ? kAffineGeneric20 : kAffineGeneric;
@@ -366,8 +371,8 @@ bool TakeStepLdsSwitch() {
 }
 
 LmiKernel LmiTakeKernel(const Group& g) {
-  if (g.large) return g.herm_d ? kTakeLargeTaylor : kTakeLargePade;
-  if (LmiTakeStepRowsSupports(g.n) && !TakeStepLdsSwitch() && !g.literal) {
+  if (g.lmi.large) return g.herm_d ? kTakeLargeTaylor : kTakeLargePade;
+  if (LmiTakeStepRowsSupports(g.n) && !TakeStepLdsSwitch() && !g.lmi.literal) {
     if (g.herm_d == 0) return g.n <= 20 ? (g.n == 20 ? kTakeRows20 : kTakeRows20Pad) : (g.n == 32 ? kTakeRows32 : kTakeRows32Pad);
     return g.n <= 24 ? (g.n == 24 ? kTakeTaylor24 : kTakeTaylor24Pad) : (g.n == 32 ? kTakeTaylor32 : kTakeTaylor32Pad);
   }
@@ -398,7 +403,7 @@ struct LmiLists {
 };
 static void ReadLmiLists(const ConstraintRec& c, LmiLists* L) {
   if (c.csr_only) {
-    L->ptr = c.e_ptr.data(), L->rc = c.e_rc.data(), L->val = c.e_val.data();
+    L->ptr = c.entries.ptr.data(), L->rc = c.entries.rc.data(), L->val = c.entries.val.data();
     return;
   }
   const int n = c.n, m = c.m;
@@ -426,7 +431,7 @@ bool LmiTakesSparseAffine(const ConstraintRec& c, int mode, double min_ratio) {
   if (mode == 0 || LmiLdsResident(c.n, c.m)) return false;
   size_t nnz_c = 0;
   if (c.csr_only)
-    nnz_c = (size_t)(c.e_ptr[c.m + 1] - c.e_ptr[c.m]);
+    nnz_c = (size_t)(c.entries.ptr[c.m + 1] - c.entries.ptr[c.m]);
   else
     for (double v : c.C) nnz_c += (v != 0.0);
   if (nnz_c <= (size_t)kSparseAffineMinNnz) return false;
@@ -448,7 +453,7 @@ static int UploadSparseAffine(cxk_context* ctx, Group& g, const std::vector<LmiL
   CXK_DEMAND(cnt <= 65535, "a group of more than 65535 equal-shaped sparse LMIs with an affine term by its nonzeros is not supported");
   std::vector<int> cptr(cnt * ((size_t)n + 1), 0), crc, cslot, pptr(cnt + 1, 0), prc, eslot((size_t)eptr[cnt * m1], 0);
   std::vector<double> cval;
-  g.sa_pmax = 0;
+  g.lmi.sa.pmax = 0;
   for (size_t k = 0; k < cnt; k++) {
     const LmiLists& L = lists[k];
     std::vector<int> pos(L.rc, L.rc + L.ptr[m1]);
@@ -469,15 +474,15 @@ static int UploadSparseAffine(cxk_context* ctx, Group& g, const std::vector<LmiL
     prc.insert(prc.end(), pos.begin(), pos.end());
     CXK_DEMAND(prc.size() < ((size_t)1 << 31) && crc.size() < ((size_t)1 << 31), "sparse LMI group: too many nonzeros");
     pptr[k + 1] = (int)prc.size();
-    g.sa_pmax = std::max(g.sa_pmax, (int)pos.size());
+    g.lmi.sa.pmax = std::max(g.lmi.sa.pmax, (int)pos.size());
   }
-  CXK_TRY(g.sa_cptr.upload(cptr));
-  CXK_TRY(g.sa_crc.upload(crc));
-  CXK_TRY(g.sa_cslot.upload(cslot));
-  CXK_TRY(g.sa_cval.upload(cval));
-  CXK_TRY(g.sa_pptr.upload(pptr));
-  CXK_TRY(g.sa_prc.upload(prc));
-  CXK_TRY(g.sa_eslot.upload(eslot));
+  CXK_TRY(g.lmi.sa.cptr.upload(cptr));
+  CXK_TRY(g.lmi.sa.crc.upload(crc));
+  CXK_TRY(g.lmi.sa.cslot.upload(cslot));
+  CXK_TRY(g.lmi.sa.cval.upload(cval));
+  CXK_TRY(g.lmi.sa.pptr.upload(pptr));
+  CXK_TRY(g.lmi.sa.prc.upload(prc));
+  CXK_TRY(g.lmi.sa.eslot.upload(eslot));
   return CXK_SUCCESS;
 }
 
@@ -491,23 +496,23 @@ int UploadSparseLmi(cxk_context* ctx, Group& g) {
     CXK_DEMAND(!lists[k].too_many, "sparse LMI group: too many nonzeros");
   }
   // a dense affine term stays out of the pair sums (X = W C W is formed instead)
-  g.sp_cdense = false;
+  g.lmi.sp.cdense = false;
   for (size_t k = 0; k < cnt; k++)
-    if (lists[k].ptr[m1] - lists[k].ptr[m] > 64) g.sp_cdense = true;  // (C, C) alone would be nz^2 terms on one wavefront
+    if (lists[k].ptr[m1] - lists[k].ptr[m] > 64) g.lmi.sp.cdense = true;  // (C, C) alone would be nz^2 terms on one wavefront
   std::vector<int> eptr(cnt * m1 + 1, 0), erc, pptr(cnt * nn + 1, 0), pvar;
   std::vector<double> eval, pval;
-  g.sp_emax = 0;
+  g.lmi.sp.emax = 0;
   for (size_t k = 0; k < cnt; k++) {
     const LmiLists& L = lists[k];
     for (int i = 0; i < m1; i++) {
-      if (i < m || !g.sp_cdense) {
+      if (i < m || !g.lmi.sp.cdense) {
         erc.insert(erc.end(), L.rc + L.ptr[i], L.rc + L.ptr[i + 1]);
         eval.insert(eval.end(), L.val + L.ptr[i], L.val + L.ptr[i + 1]);
       }
       CXK_DEMAND(eval.size() < ((size_t)1 << 31), "sparse LMI group: too many nonzeros");
       eptr[k * m1 + i + 1] = (int)eval.size();
     }
-    g.sp_emax = std::max(g.sp_emax, eptr[k * m1 + m1] - eptr[k * m1]);
+    g.lmi.sp.emax = std::max(g.lmi.sp.emax, eptr[k * m1 + m1] - eptr[k * m1]);
     // position-major: the variables of a position in ascending order (the reference's order of i in sum_i y_i A_i)
     int* pp = pptr.data() + k * nn;
     const int base = (int)pval.size();
@@ -524,32 +529,32 @@ int UploadSparseLmi(cxk_context* ctx, Group& g) {
         pval[at] = L.val[e];
       }
   }
-  g.sp_small = !g.large && LmiSparseLds(n, m, true, g.sp_cdense, 0) <= kLdsLimit;
+  g.lmi.sp.small = !g.lmi.large && LmiSparseLds(n, m, true, g.lmi.sp.cdense, 0) <= kLdsLimit;
   // work split: lanes per pair from the average number of terms of a pair (each lane takes four
   // terms at a time); enough workgroups to fill the chip when the group is small
   const double per_mat = cnt ? (double)eval.size() / (double)(cnt * m1) : 0.0;
   const double avg_terms = per_mat * per_mat;
-  g.sp_lpp = avg_terms <= 8 ? 1 : avg_terms <= 64 ? 4 : avg_terms <= 1024 ? 16 : 64;
+  g.lmi.sp.lpp = avg_terms <= 8 ? 1 : avg_terms <= 64 ? 4 : avg_terms <= 1024 ? 16 : 64;
   const double pairs = 0.5 * m1 * (m1 + 1.0);
-  const double per_block = (256.0 / g.sp_lpp) * 4.0;  // pairs one workgroup takes in stride
+  const double per_block = (256.0 / g.lmi.sp.lpp) * 4.0;  // pairs one workgroup takes in stride
   int chunks = (int)std::ceil(pairs / per_block);
   const int cap = (int)std::max<size_t>(1, 2048 / std::max<size_t>(cnt, 1));
-  g.sp_chunks = std::max(1, std::min(chunks, cap));
+  g.lmi.sp.chunks = std::max(1, std::min(chunks, cap));
   {
     std::vector<int> pr;
     pr.reserve((size_t)m1 * (m1 + 1) / 2);
     for (int i = 0; i < m1; i++)
       for (int j = 0; j <= i; j++) pr.push_back(i | (j << 16));
-    CXK_TRY(g.sp_pairs.upload(pr));
+    CXK_TRY(g.lmi.sp.pairs.upload(pr));
   }
-  CXK_TRY(g.sp_eptr.upload(eptr));
-  CXK_TRY(g.sp_erc.upload(erc));
-  CXK_TRY(g.sp_eval.upload(eval));
-  CXK_TRY(g.sp_pptr.upload(pptr));
-  CXK_TRY(g.sp_pvar.upload(pvar));
-  CXK_TRY(g.sp_pval.upload(pval));
-  if (g.sp_affine) {
-    CXK_DEMAND(g.sp_cdense && !g.sp_small, "internal error: a sparse LMI group takes its affine term by nonzeros only beyond the LDS-resident orders");
+  CXK_TRY(g.lmi.sp.eptr.upload(eptr));
+  CXK_TRY(g.lmi.sp.erc.upload(erc));
+  CXK_TRY(g.lmi.sp.eval.upload(eval));
+  CXK_TRY(g.lmi.sp.pptr.upload(pptr));
+  CXK_TRY(g.lmi.sp.pvar.upload(pvar));
+  CXK_TRY(g.lmi.sp.pval.upload(pval));
+  if (g.lmi.sa.on) {
+    CXK_DEMAND(g.lmi.sp.cdense && !g.lmi.sp.small, "internal error: a sparse LMI group takes its affine term by nonzeros only beyond the LDS-resident orders");
     return UploadSparseAffine(ctx, g, lists, eptr);
   }
   return CXK_SUCCESS;
@@ -560,20 +565,20 @@ int UploadSparseLmi(cxk_context* ctx, Group& g) {
 
 template <bool SMALL, int LPP, bool AFF>
 hipError_t LaunchLmiSparseKernelL(Group& g, const LmiGroup& d, const Arena& ar, const double* X, hipStream_t st) {
-  const dim3 grid(d.count, g.sp_chunks);
-  const int emax = (g.sp_emax + 1) & ~1;  // keeps the arrays behind it 8-byte aligned
-  const bool stage = LmiSparseLds(g.n, g.m, SMALL, g.sp_cdense, emax) <= kLdsLimit;
-  const size_t lds = LmiSparseLds(g.n, g.m, SMALL, g.sp_cdense, stage ? emax : 0);
+  const dim3 grid(d.count, g.lmi.sp.chunks);
+  const int emax = (g.lmi.sp.emax + 1) & ~1;  // keeps the arrays behind it 8-byte aligned
+  const bool stage = LmiSparseLds(g.n, g.m, SMALL, g.lmi.sp.cdense, emax) <= kLdsLimit;
+  const size_t lds = LmiSparseLds(g.n, g.m, SMALL, g.lmi.sp.cdense, stage ? emax : 0);
   SparseLaunchOf<AFF> L;
   L.Xg = X;
-  L.part = g.ws_part.p;
+  L.part = g.lmi.ws_part.p;
   L.npart = kSparseCParts;
   L.emax = stage ? emax : 0;
-  L.cdense = g.sp_cdense;
+  L.cdense = g.lmi.sp.cdense;
   if constexpr (AFF) {
-    L.Xp = g.ws_main.p + (size_t)d.count * g.n * g.n;
-    L.eslot = g.sa_eslot.p;
-    L.ppos = g.sa_pptr.p;
+    L.Xp = g.lmi.ws_main.p + (size_t)d.count * g.n * g.n;
+    L.eslot = g.lmi.sa.eslot.p;
+    L.ppos = g.lmi.sa.pptr.p;
   }
   auto raise = [&](const void* k) -> hipError_t {  // dynamic LDS beyond 64 KB needs the attribute
     return lds > 64 * 1024 ? hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit)
@@ -592,7 +597,7 @@ hipError_t LaunchLmiSparseKernelL(Group& g, const LmiGroup& d, const Arena& ar, 
 
 template <bool SMALL, bool AFF = false>
 hipError_t LaunchLmiSparseKernel(Group& g, const LmiGroup& d, const Arena& ar, const double* X, hipStream_t st) {
-  switch (g.sp_lpp) {
+  switch (g.lmi.sp.lpp) {
     case 1: return LaunchLmiSparseKernelL<SMALL, 1, AFF>(g, d, ar, X, st);
     case 4: return LaunchLmiSparseKernelL<SMALL, 4, AFF>(g, d, ar, X, st);
     case 16: return LaunchLmiSparseKernelL<SMALL, 16, AFF>(g, d, ar, X, st);
@@ -607,29 +612,29 @@ hipError_t LaunchLmiSchurSparse(Group& g, LmiKernel kern, const Arena& ar, hipSt
   double* X = nullptr;
   if (kern == kSchurSparseAffine) {
     SparseAffine a;
-    a.cptr = g.sa_cptr.p;
-    a.crc = g.sa_crc.p;
-    a.cslot = g.sa_cslot.p;
-    a.cval = g.sa_cval.p;
-    a.pptr = g.sa_pptr.p;
-    a.prc = g.sa_prc.p;
-    a.U = g.ws_main.p;                               // count x n^2
-    a.Xp = g.ws_main.p + (size_t)d.count * n * n;    // at most count x n^2 positions
+    a.cptr = g.lmi.sa.cptr.p;
+    a.crc = g.lmi.sa.crc.p;
+    a.cslot = g.lmi.sa.cslot.p;
+    a.cval = g.lmi.sa.cval.p;
+    a.pptr = g.lmi.sa.pptr.p;
+    a.prc = g.lmi.sa.prc.p;
+    a.U = g.lmi.ws_main.p;                               // count x n^2
+    a.Xp = g.lmi.ws_main.p + (size_t)d.count * n * n;    // at most count x n^2 positions
     const int tiles = (n + 63) / 64;
     lmi_affine_wc<<<dim3(tiles, tiles, d.count), 256, 0, st>>>(d, a);
-    lmi_affine_x<<<dim3((g.sa_pmax + 3) / 4, d.count), 256, 0, st>>>(d, a);
-    lmi_affine_scalars<<<dim3(kSparseCParts, d.count), 256, 0, st>>>(d, a, g.ws_part.p);
+    lmi_affine_x<<<dim3((g.lmi.sa.pmax + 3) / 4, d.count), 256, 0, st>>>(d, a);
+    lmi_affine_scalars<<<dim3(kSparseCParts, d.count), 256, 0, st>>>(d, a, g.lmi.ws_part.p);
     return LaunchLmiSparseKernel<false, true>(g, d, ar, nullptr, st);
-  } else if (g.sp_cdense) {
+  } else if (g.lmi.sp.cdense) {
     const int64_t nn = (int64_t)n * n;
-    double* CW = g.ws_main.p;                  // count x nn
-    X = g.ws_main.p + (size_t)d.count * nn;    // count x nn
+    double* CW = g.lmi.ws_main.p;                  // count x nn
+    X = g.lmi.ws_main.p + (size_t)d.count * nn;    // count x nn
     hipError_t e;
     GemmArgs a = SquareGemm(n, d.C, nn, d.W, nn, CW, nn);
     if ((e = LaunchGemm(a, false, false, d.count, st)) != hipSuccess) return e;
     a = SquareGemm(n, d.W, nn, CW, nn, X, nn);
     if ((e = LaunchGemm(a, false, false, d.count, st)) != hipSuccess) return e;
-    lmi_dense_c_scalars<<<dim3(kSparseCParts, d.count), 256, 0, st>>>(d, X, g.ws_part.p);
+    lmi_dense_c_scalars<<<dim3(kSparseCParts, d.count), 256, 0, st>>>(d, X, g.lmi.ws_part.p);
   }
   return LaunchLmiSparseKernel<false>(g, d, ar, X, st);
 }
@@ -643,15 +648,15 @@ int LaunchLmiDenseSchur(cxk_context* ctx, Group& g, const Arena& ar) {
     CXK_TRY(LmiLargeSchur(MakeLmi(g), ar, MakeLargeWs(g), ctx->stream));
   } else if (IsSchurMfma(kern)) {
     LmiGroup lg = MakeLmi(g);
-    if (g.Apad.p) {  // the order runs on the next instance up (masked W loads in the kernel)
+    if (g.lmi.Apad.p) {  // the order runs on the next instance up (masked W loads in the kernel)
       const int np = LmiMfmaPaddedOrder(g.n);
-      lg.A = g.Apad.p;
+      lg.A = g.lmi.Apad.p;
       lg.a_stride = (long long)(g.m + 1) * np * np;
     }
     // every other launch of the group last to first: a launch then starts on the operands the previous one
     // ended with, which shortens its fill (the results are the same bits either way)
-    const int rev = ctx->lmi_order_forward ? 0 : (int)(g.schur_launches & 1);
-    g.schur_launches++;
+    const int rev = ctx->lmi_order_forward ? 0 : (int)(g.lmi.schur_launches & 1);
+    g.lmi.schur_launches++;
     CXK_TRY(LaunchLmiSchurMfma(lg, ar, ctx->cus, rev, ctx->stream, clock.clk.e0, clock.clk.e1));
   } else {
     lmi_schur_generic<<<(int)g.ids.size(), 256, LmiGenericLds(g.n), ctx->stream>>>(MakeLmi(g), ar);
@@ -695,7 +700,7 @@ int LmiPrepare(cxk_context* ctx, Group& g, int pmode, const StepArgs& sa, const 
           CXK_TRY(LmiLargePrepare(MakeLmi(g), sa, MakeLargeWs(g), MODE, ctx->stream));
           break;
         case kPrepareRowsPacked:
-        case kPrepareRowsExact:  // (the instance reads g.Apk when there is one)
+        case kPrepareRowsExact:  // (the instance reads g.lmi.Apk when there is one)
           CXK_LAUNCH_CLOCKED(clk, (lmi_prepare_rows<MODE, 20, true>), (cnt + 3) / 4 + tail_blocks, 256, MakeLmi(g), sa, tail);
           break;
         case kPrepareRowsOdd:
@@ -763,7 +768,7 @@ extern "C" {
 int cxk_lmi_kernels(const cxk_context* ctx, int constraint, int out[5]) {
   if (!ctx || !ctx->device_ready || !out || constraint < 0 || constraint >= (int)ctx->cons.size()) return CXK_FAILURE;
   const ConstraintRec& c = ctx->cons[constraint];
-  if (c.type != CXK_LMI || c.factored || !ctx->owned[constraint]) return CXK_FAILURE;
+  if (c.type != CXK_LMI || c.factors.given || !ctx->owned[constraint]) return CXK_FAILURE;
   const Group& g = ctx->groups[c.group];
   out[CXK_LMI_STAGE_SCHUR] = LmiSchurKernel(g);
   out[CXK_LMI_STAGE_PREPARE] = LmiPrepareKernel(ctx, g, 0);

@@ -1,6 +1,7 @@
 // Quadratic cones on their two routes (kQuadLds, kQuadStreamed): the views, the stages of cxk_finalize and every
 // launch.  Owns the kernels of kernels_quad / _quad_stream; the slack of the streamed route is the second-order
 // cones' kernel (cone_soc.hip: LaunchSocStreamSlack), the scaling point's identity the vector cones' (cone_linear.hip).
+// The family's state is Group::quad (cone_state.h).
 #include "cone_units.h"
 #include "kernels_gemm.hip.h"
 #include "kernels_quad.hip.h"
@@ -19,11 +20,11 @@ QuadGroup MakeQuad(Group& g) {
   d.count = static_cast<int>(g.ids.size());
   d.A = g.A.p;
   d.c = g.C.p;
-  d.Q = g.has_q ? g.qQ.p : nullptr;
-  d.Agram = g.qGram.p;
+  d.Q = g.quad.has_q ? g.quad.Q.p : nullptr;
+  d.Agram = g.quad.Gram.p;
   d.W = g.W.p;
   d.D = g.T1.p;
-  d.S = g.qS.p;
+  d.S = g.quad.S.p;
   d.ids = g.dids.p;
   return d;
 }
@@ -32,15 +33,15 @@ QuadGroup MakeQuad(Group& g) {
 int UploadQuadGram(cxk_context* ctx, Group& g) {
   const size_t cnt = g.ids.size();
   const int n = g.n, m = g.m, len = n + 1;
-  std::vector<double> hQ(g.has_q ? (size_t)n * n * cnt : 0), hG((size_t)m * m * cnt, 0.0), qa((size_t)n);
+  std::vector<double> hQ(g.quad.has_q ? (size_t)n * n * cnt : 0), hG((size_t)m * m * cnt, 0.0), qa((size_t)n);
   for (size_t k = 0; k < cnt; k++) {
     const ConstraintRec& c = ctx->cons[g.ids[k]];
-    if (g.has_q) std::copy(c.Q.begin(), c.Q.end(), hQ.begin() + k * (size_t)n * n);
+    if (g.quad.has_q) std::copy(c.Q.begin(), c.Q.end(), hQ.begin() + k * (size_t)n * n);
     for (int j = 0; j < m; j++) {
       const double* aj = c.A.data() + (size_t)j * len + 1;
       for (int i = 0; i < n; i++) {
-        double s2 = g.has_q ? 0.0 : aj[i];
-        if (g.has_q)
+        double s2 = g.quad.has_q ? 0.0 : aj[i];
+        if (g.quad.has_q)
           for (int q2 = 0; q2 < n; q2++) s2 += c.Q[(size_t)q2 * n + i] * aj[q2];
         qa[(size_t)i] = s2;
       }
@@ -52,9 +53,9 @@ int UploadQuadGram(cxk_context* ctx, Group& g) {
       }
     }
   }
-  CXK_TRY(g.qQ.upload(hQ));
-  CXK_TRY(g.qGram.upload(hG));
-  CXK_TRY(g.qS.alloc((size_t)len * cnt));
+  CXK_TRY(g.quad.Q.upload(hQ));
+  CXK_TRY(g.quad.Gram.upload(hG));
+  CXK_TRY(g.quad.S.alloc((size_t)len * cnt));
   return CXK_SUCCESS;
 }
 QuadStreamGroup MakeQuadStream(Group& g) {
@@ -63,17 +64,17 @@ QuadStreamGroup MakeQuadStream(Group& g) {
   d.n = g.n;
   d.m = g.m;
   d.count = static_cast<int>(cnt);
-  d.splits = g.splits;
+  d.splits = g.quad.splits;
   d.A = g.A.p;
   d.c = g.C.p;
-  d.Q = g.has_q ? g.qQ.p : nullptr;
-  d.Agram = g.qGram.p;
+  d.Q = g.quad.has_q ? g.quad.Q.p : nullptr;
+  d.Agram = g.quad.Gram.p;
   d.W = g.W.p;
   d.D = g.T1.p;
-  d.S = g.qS.p;
+  d.S = g.quad.S.p;
   d.ids = g.dids.p;
-  d.part = g.ws_part.p;
-  double* p = g.st_vec.p;  // (the layout UploadQuadStream sizes: QuadStreamVecDoubles)
+  d.part = g.quad.part.p;
+  double* p = g.quad.vec.p;  // (the layout UploadQuadStream sizes: QuadStreamVecDoubles)
   d.qc1 = p;
   d.qw = (p += cnt * n);
   d.dv = (p += cnt * n);
@@ -91,20 +92,20 @@ size_t QuadStreamVecDoubles(size_t cnt, size_t n, size_t m) { return cnt * (4 * 
 int UploadQuadStream(cxk_context* ctx, Group& g, const FinalizeSwitches& sw) {
   const size_t cnt = g.ids.size();
   const size_t n = (size_t)g.n, m = (size_t)g.m, tiles = (n + kQuadStreamRowTile - 1) / kQuadStreamRowTile;
-  g.splits = g.has_q ? QuadStreamSplits(g.n, (long long)cnt) : 1;
-  if (g.has_q && sw.gram_splits > 0) g.splits = sw.gram_splits;  // (comparison runs)
+  g.quad.splits = g.quad.has_q ? QuadStreamSplits(g.n, (long long)cnt) : 1;
+  if (g.quad.has_q && sw.gram_splits > 0) g.quad.splits = sw.gram_splits;  // (comparison runs)
   CXK_DEMAND(cnt * std::max<size_t>(std::max<size_t>(m, (m * m + kQuadStreamBlock - 1) / kQuadStreamBlock),
-                                    std::max<size_t>(tiles * (size_t)g.splits, (n + 1 + kSocStreamRowTile - 1) / kSocStreamRowTile)) <=
+                                    std::max<size_t>(tiles * (size_t)g.quad.splits, (n + 1 + kSocStreamRowTile - 1) / kSocStreamRowTile)) <=
                  (size_t)INT_MAX,
              "a group of streamed quadratic cones with more than 2^31 columns, row tiles or blocks is not supported");
-  std::vector<double> hQ(g.has_q ? n * n * cnt : 0);
-  if (g.has_q)
+  std::vector<double> hQ(g.quad.has_q ? n * n * cnt : 0);
+  if (g.quad.has_q)
     for (size_t k = 0; k < cnt; k++) std::copy(ctx->cons[g.ids[k]].Q.begin(), ctx->cons[g.ids[k]].Q.end(), hQ.begin() + k * n * n);
-  CXK_TRY(g.qQ.upload(hQ));
-  CXK_TRY(g.qGram.alloc(m * m * cnt));
-  CXK_TRY(g.qS.alloc((n + 1) * cnt));
-  CXK_TRY(g.st_vec.alloc(QuadStreamVecDoubles(cnt, n, m)));
-  CXK_TRY(g.ws_part.alloc(g.has_q ? cnt * (size_t)g.splits * 2 * n : 0));
+  CXK_TRY(g.quad.Q.upload(hQ));
+  CXK_TRY(g.quad.Gram.alloc(m * m * cnt));
+  CXK_TRY(g.quad.S.alloc((n + 1) * cnt));
+  CXK_TRY(g.quad.vec.alloc(QuadStreamVecDoubles(cnt, n, m)));
+  CXK_TRY(g.quad.part.alloc(g.quad.has_q ? cnt * (size_t)g.quad.splits * 2 * n : 0));
   return QuadStreamConstants(ctx, g);
 }
 // soc_stream_slack serves the streamed quadratic cone as it is (same layout, same formula): what it reads of the group.
@@ -169,7 +170,7 @@ int QuadStreamConstants(cxk_context* ctx, Group& g) {
   quad_stream_constants<<<cnt, kQuadStreamBlock, 0, ctx->stream>>>(d);
   CXK_TRY(hipGetLastError());
   DevBuf<double> T;
-  if (g.has_q && m > 0) CXK_TRY(T.alloc((size_t)cnt * n * m));
+  if (g.quad.has_q && m > 0) CXK_TRY(T.alloc((size_t)cnt * n * m));
   constexpr int kMaxBatch = 65535;  // gridDim.z
   for (int b0 = 0; b0 < cnt && m > 0; b0 += kMaxBatch) {
     const int nb = std::min(kMaxBatch, cnt - b0);
@@ -179,11 +180,11 @@ int QuadStreamConstants(cxk_context* ctx, Group& g) {
     a.alpha = 1.0;
     a.beta = 0.0;
     a.splits = 1;
-    if (g.has_q) {  // T = Q A1
+    if (g.quad.has_q) {  // T = Q A1
       a.M = n;
       a.N = m;
       a.K = n;
-      a.A = g.qQ.p + (size_t)b0 * n * n;
+      a.A = g.quad.Q.p + (size_t)b0 * n * n;
       a.lda = n;
       a.sA1 = (int64_t)n * n;
       a.B = A1;
@@ -200,10 +201,10 @@ int QuadStreamConstants(cxk_context* ctx, Group& g) {
     a.A = A1;
     a.lda = len;
     a.sA1 = (int64_t)len * m;
-    a.B = g.has_q ? T.p + (size_t)b0 * n * m : A1;
-    a.ldb = g.has_q ? n : len;
-    a.sB1 = g.has_q ? (int64_t)n * m : (int64_t)len * m;
-    a.C = g.qGram.p + (size_t)b0 * m * m;
+    a.B = g.quad.has_q ? T.p + (size_t)b0 * n * m : A1;
+    a.ldb = g.quad.has_q ? n : len;
+    a.sB1 = g.quad.has_q ? (int64_t)n * m : (int64_t)len * m;
+    a.C = g.quad.Gram.p + (size_t)b0 * m * m;
     a.ldc = m;
     a.sC1 = (int64_t)m * m;
     CXK_TRY(LaunchGemm(a, true, false, nb, ctx->stream));

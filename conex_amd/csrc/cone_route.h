@@ -126,7 +126,7 @@ inline size_t SocTakeLds(int n) { return sizeof(double) * 4 * ((size_t)n + 1); }
 inline size_t QuadSchurLds(int n, int m) { return sizeof(double) * (2 * (size_t)n + (size_t)m + 4); }
 inline size_t QuadPrepareLds(int n, int m) { return sizeof(double) * ((size_t)m + 4 * ((size_t)n + 1)); }
 inline size_t QuadTakeLds(int n) { return sizeof(double) * 3 * ((size_t)n + 1); }
-// the LDS-resident orders of a matrix inequality: beyond them the large-order kernels (Group::large)
+// the LDS-resident orders of a matrix inequality: beyond them the large-order kernels (Group::lmi.large)
 inline bool LmiLdsResident(int n, int m) { return LmiTakeLds(n) <= kLdsLimit && LmiPrepareLds(n, m) <= kLdsLimit; }
 
 // What is known of one constraint when its route is chosen.

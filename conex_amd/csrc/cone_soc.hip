@@ -1,6 +1,6 @@
 // Second-order cones on their three routes (kSocLds, kSocStreamed, kSocSparse): the views, the stages of cxk_finalize
 // and every launch.  Owns the kernels of kernels_soc / _soc_stream / _soc_sparse; the streamed quadratic cones reach
-// soc_stream_slack through LaunchSocStreamSlack.
+// soc_stream_slack through LaunchSocStreamSlack.  The family's state is Group::soc (cone_state.h).
 #include "cone_units.h"
 #include "kernels_soc.hip.h"
 #include "kernels_soc_stream.hip.h"
@@ -18,44 +18,45 @@ SocStreamGroup MakeSocStream(Group& g) {
   SocStreamGroup d;
   const size_t per = g.ids.size() * ((size_t)g.n + 1);
   d.v = MakeVec(g);
-  d.WA = g.ws_main.p;
-  d.s = g.st_vec.p;
-  d.wc = g.st_vec.p + per;
-  d.ms = g.st_vec.p + 2 * per;
-  d.dets = g.st_det.p;
-  d.Gf = g.ws_gf.p;
+  d.WA = g.soc.gram.WA.p;
+  d.s = g.soc.vec.p;
+  d.wc = g.soc.vec.p + per;
+  d.ms = g.soc.vec.p + 2 * per;
+  d.dets = g.soc.det.p;
+  d.Gf = g.soc.gram.Gf.p;
   return d;
 }
 int UploadSocStream(cxk_context* ctx, Group& g, const FinalizeSwitches& sw) {
   const size_t cnt = g.ids.size(), len = (size_t)g.n + 1, m = (size_t)g.m;
   CXK_DEMAND(cnt * std::max<size_t>(m, (len + kSocStreamRowTile - 1) / kSocStreamRowTile) <= (size_t)INT_MAX,
              "a group of streamed second-order cones with more than 2^31 columns or row tiles is not supported");
-  g.st_stages = sw.soc_stream_stages;
-  if (AllocGramWorkspace(ctx, g, len, sw)) return CXK_FAILURE;
-  CXK_TRY(g.st_vec.alloc(3 * cnt * len));
-  CXK_TRY(g.st_det.alloc(cnt));
+  g.soc.stages = sw.soc_stream_stages;
+  if (AllocGramWorkspace(ctx, g.soc.gram, cnt, len, m, sw)) return CXK_FAILURE;
+  CXK_TRY(g.soc.vec.alloc(3 * cnt * len));
+  CXK_TRY(g.soc.det.alloc(cnt));
   return CXK_SUCCESS;
 }
 SocSparseGroup MakeSocSparse(Group& g) {
   SocSparseGroup d{};
   const size_t cnt = g.ids.size(), len = (size_t)g.n + 1, m = (size_t)g.m;
   d.st.v = MakeVec(g);  // (A is null; WA, wc, dets and Gf stay null: the step kernels read v, s and ms only)
-  double* p = g.st_vec.p;  // (the layouts UploadSocSparse sizes: SocSparseVecDoubles, SocSparseConstDoubles)
+  double* p = g.soc.vec.p;  // (the layouts UploadSocSparse sizes: SocSparseVecDoubles, SocSparseConstDoubles)
   d.st.s = p;
   d.st.ms = (p += cnt * len);
   d.u = (p += cnt * len);
   d.scal = (p += cnt * m);
-  p = g.ss_const.p;
+  p = g.soc.consts.p;
   d.H = p;
   d.h = (p += cnt * m * m);
   d.z = (p += cnt * m);
-  d.eptr = g.ls_eptr.p;
-  d.rowptr = g.ls_rowptr.p;
-  d.col = g.ls_col.p;
-  d.val = g.ls_val.p;
-  d.colptr = g.ls_colptr.p;
-  d.crow = g.ls_crow.p;
-  d.cval = g.ls_cval.p;
+  const NonzeroLists& nz = g.soc.nz;
+  d.eptr = nz.eptr.p;
+  d.rowptr = nz.rowptr.p;
+  d.col = nz.col.p;
+  d.val = nz.val.p;
+  d.colptr = nz.colptr.p;
+  d.crow = nz.crow.p;
+  d.cval = nz.cval.p;
   return d;
 }
 size_t SocSparseVecDoubles(size_t cnt, size_t len, size_t m) { return cnt * (2 * len + m + 2); }
@@ -63,13 +64,13 @@ size_t SocSparseConstDoubles(size_t cnt, size_t m) { return cnt * (m * m + m + 1
 // A group of sparse second-order cones: the nonzeros, the work space, and the constants on the device (SocSparseConstants).
 int UploadSocSparse(cxk_context* ctx, Group& g) {
   const size_t cnt = g.ids.size(), len = (size_t)g.n + 1, m = (size_t)g.m, tiles = (len + kSocStreamRowTile - 1) / kSocStreamRowTile;
-  if (UploadSparseNonzeros(ctx, g)) return CXK_FAILURE;
+  if (UploadSparseNonzeros(ctx, g, g.soc.nz)) return CXK_FAILURE;
   CXK_DEMAND(cnt * std::max(std::max(m * (size_t)SocSparseGramChunks(g.m), tiles), (size_t)SocSparseCombineTiles(g.m)) <=
                  (size_t)INT_MAX,
              "a group of sparse second-order cones with more than 2^31 column chunks, row tiles or tiles of the Schur "
              "block is not supported");
-  CXK_TRY(g.st_vec.alloc(SocSparseVecDoubles(cnt, len, m)));
-  CXK_TRY(g.ss_const.alloc(SocSparseConstDoubles(cnt, m)));
+  CXK_TRY(g.soc.vec.alloc(SocSparseVecDoubles(cnt, len, m)));
+  CXK_TRY(g.soc.consts.alloc(SocSparseConstDoubles(cnt, m)));
   return SocSparseConstants(ctx, g);
 }
 
@@ -104,10 +105,10 @@ hipError_t LaunchSocStreamSchur(Group& g, const Arena& ar, hipStream_t st) {
   const SocStreamGroup d = MakeSocStream(g);
   const int cnt = d.v.count, len = d.v.len, m = d.v.m;
   soc_stream_vectors<<<cnt, kSocStreamBlock, 0, st>>>(d, ar);
-  if (m == 0 || g.st_stages == 1) return hipGetLastError();
+  if (m == 0 || g.soc.stages == 1) return hipGetLastError();
   soc_stream_apply<<<(unsigned)((size_t)cnt * m), kSocStreamBlock, 0, st>>>(d, ar);
-  if (g.st_stages == 2) return hipGetLastError();
-  const hipError_t e = LaunchGramLower(g, d.WA, d.Gf, cnt, len, m, 2.0, st);
+  if (g.soc.stages == 2) return hipGetLastError();
+  const hipError_t e = LaunchGramLower(g.soc.gram, d.WA, d.Gf, cnt, len, m, 2.0, st);
   if (e != hipSuccess) return e;
   soc_stream_mirror<<<GridFor((size_t)cnt * m * m, kSocStreamBlock), kSocStreamBlock, 0, st>>>(d, ar);
   return hipGetLastError();

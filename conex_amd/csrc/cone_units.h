@@ -6,7 +6,8 @@
 //   cone_quad.hip    kQuadLds, kQuadStreamed
 //   cone_lmi.hip     kLmiDense, kLmiSparse, kLmiFactored; the list of LMI kernel instances and its choosers
 // (kOct and kStatic are one launch per stage and stay in kkt_cone_launch.hip.)  Each unit holds the views of its routes
-// (Make*), their stages of cxk_finalize (Upload*) and their launches; `mode` of a PrepareStep / query call is 0 or 1 and
+// (Make*), their stages of cxk_finalize (Upload*) and their launches, and is the only one to touch its family's member
+// of Group (lin, soc, quad, lmi: cone_state.h, which lists the exceptions); `mode` of a PrepareStep / query call is 0 or 1 and
 // picks the <0> / <1> instance of the kernels.  Host declarations only, no device code.  Everything is hidden
 // (CXK_LOCAL) but the functions libconex.so has always exported: those keep their visibility.
 #pragma once
@@ -44,10 +45,12 @@ struct CXK_LOCAL AssemblyClock {
 // ---- cone_linear.hip
 VecGroup MakeVec(Group& g);
 CXK_LOCAL void LinearNonzeros(ConstraintRec* c);
-CXK_LOCAL int UploadSparseNonzeros(cxk_context* ctx, Group& g);  // second-order cones on the sparse route too
+CXK_LOCAL int AllocLinearT2(cxk_context* ctx, Group& g);  // UploadGroup: every group, ahead of its route's stage
+// the group's nonzeros into `nz` (its family's lists): second-order cones on the sparse route too
+CXK_LOCAL int UploadSparseNonzeros(cxk_context* ctx, const Group& g, NonzeroLists& nz);
 // Gf = alpha WA' WA of every member, and its work space: streamed second-order cones too
-CXK_LOCAL int AllocGramWorkspace(cxk_context* ctx, Group& g, size_t len, const FinalizeSwitches& sw);
-CXK_LOCAL hipError_t LaunchGramLower(Group& g, const double* WA, double* Gf, int cnt, int len, int m, double alpha, hipStream_t st);
+CXK_LOCAL int AllocGramWorkspace(cxk_context* ctx, GramWs& w, size_t cnt, size_t len, size_t m, const FinalizeSwitches& sw);
+CXK_LOCAL hipError_t LaunchGramLower(const GramWs& w, const double* WA, double* Gf, int cnt, int len, int m, double alpha, hipStream_t st);
 CXK_LOCAL int UploadLinearTiled(cxk_context* ctx, Group& g, const FinalizeSwitches& sw);
 CXK_LOCAL int UploadLinearSparse(cxk_context* ctx, Group& g);
 CXK_LOCAL void LaunchLinearLdsSchur(Group& g, const Arena& ar, hipStream_t st);
@@ -90,6 +93,8 @@ CXK_LOCAL int PlanLmiGroup(cxk_context* ctx, Group& g, const FinalizeSwitches& s
 CXK_LOCAL int UploadLmiDense(cxk_context* ctx, Group& g, const FinalizeSwitches& sw);
 CXK_LOCAL int UploadLmiSparse(cxk_context* ctx, Group& g);
 CXK_LOCAL int UploadLmiFactored(cxk_context* ctx, Group& g);
+CXK_LOCAL LmiAssembly LmiAssemblyOf(const Group& g);   // cxk_count_lmi_kernel
+CXK_LOCAL bool LmiOnWideSpectrum(const Group& g);      // cxk_count_wide_spectrum: its Lanczos runs take the chip-wide kernels
 CXK_LOCAL bool LmiRowsServePrepare(const Group& g);  // lmi_prepare_rows has an instance for the group's shape
 // the group's PrepareStep / query (pmode: LmiPrepareKernel's) or TakeStep is one launch of a rows kernel
 CXK_LOCAL bool LmiPrepareOnRows(const cxk_context* ctx, const Group& g, int pmode);

@@ -30,7 +30,7 @@ static int UploadDenseData(cxk_context* ctx, Group& g, size_t a_sz, size_t c_sz)
   const size_t cnt = g.ids.size();
   // lmi_schur_mfma reads [A_1 .. A_m | C] of a constraint as one contiguous array of stacked
   // rows: such groups keep a copy of C right behind the A_i (LmiGroup::a_stride)
-  const size_t a_blk = a_sz + (g.assembly != LmiAssembly::kGeneric ? c_sz : 0);
+  const size_t a_blk = a_sz + (g.lmi.assembly != LmiAssembly::kGeneric ? c_sz : 0);
   std::vector<double> hA(a_blk * cnt), hC(c_sz * cnt);
   for (size_t k = 0; k < cnt; k++) {
     const ConstraintRec& c = ctx->cons[g.ids[k]];
@@ -164,7 +164,7 @@ int LaunchSchur(cxk_context* ctx) {
 // The nonzero statistics Choose asks for, of a dense-added linear block (rows = n) or second-order cone (rows = n + 1)
 // whose sparse mode is not 0; and the nonzeros themselves (LinearNonzeros) when ints can point at them.
 static void MeasureNonzeros(ConstraintRec* c, ConeShape* s) {
-  if (c->sp_rowptr.empty()) {
+  if (c->rows.ptr.empty()) {
     size_t nnz = 0;
     for (double v : c->A) nnz += v != 0.0;
     s->nnz = (double)nnz;
@@ -172,13 +172,13 @@ static void MeasureNonzeros(ConstraintRec* c, ConeShape* s) {
     if (!s->nnz_fits_int) return;
     LinearNonzeros(c);
   }
-  s->nnz = (double)c->sp_col.size();
-  for (size_t r = 0; r + 1 < c->sp_rowptr.size(); r++) {
-    const double nz = c->sp_rowptr[r + 1] - c->sp_rowptr[r];
+  s->nnz = (double)c->rows.col.size();
+  for (size_t r = 0; r + 1 < c->rows.ptr.size(); r++) {
+    const double nz = c->rows.ptr[r + 1] - c->rows.ptr[r];
     s->sum_nnz_sq += nz * nz;
   }
   std::vector<int> per_col((size_t)c->m, 0);
-  for (int v : c->sp_col) per_col[(size_t)v]++;
+  for (int v : c->rows.col) per_col[(size_t)v]++;
   s->longest_column = c->m ? *std::max_element(per_col.begin(), per_col.end()) : 0;
 }
 
@@ -200,22 +200,22 @@ int GroupConstraints(cxk_context* ctx, const FinalizeSwitches& sw) {
   for (int i = 0; i < K; i++) {
     ConstraintRec& c = ctx->cons[i];
     c.route = ConeRoute::kStatic;
-    c.sparse_affine = false;
+    c.entries.sparse_affine = false;
     if (!ctx->owned[i]) continue;
-    ConeShape s{c.type, c.n, c.m, c.herm_d, c.symmetric, c.csr_only, c.factored, c.type == CXK_QUAD && !c.Q.empty()};
+    ConeShape s{c.type, c.n, c.m, c.herm_d, c.symmetric, c.csr_only, c.factors.given, c.type == CXK_QUAD && !c.Q.empty()};
     const int sparse_mode = c.type == CXK_LINEAR ? modes.sparse_linear : c.type == CXK_SOC ? modes.sparse_soc : 0;
     if (sparse_mode != 0 && !c.csr_only) MeasureNonzeros(&c, &s);
-    if (c.type == CXK_LMI && !c.factored) MeasureLmi(c, &s);
+    if (c.type == CXK_LMI && !c.factors.given) MeasureLmi(c, &s);
     const RouteChoice choice = Choose(s, modes);
     CXK_DEMAND(!choice.refusal, choice.refusal);
     c.route = choice.route;
     const bool literal = c.type == CXK_LMI && !c.symmetric;
-    const int f_R = c.factored ? c.f_R : 0;
+    const int f_R = c.factors.given ? c.factors.R : 0;
     // (nobody said: the default of the entry point the constraint came through; a group mixes no modes)
     if (c.route == ConeRoute::kLmiSparse)
-      c.sparse_affine = LmiTakesSparseAffine(c, modes.sparse_affine != -2 ? modes.sparse_affine : c.affine_default,
+      c.entries.sparse_affine = LmiTakesSparseAffine(c, modes.sparse_affine != -2 ? modes.sparse_affine : c.entries.affine_default,
                                              modes.sparse_affine_min_ratio);
-    const auto key = std::make_tuple(c.type, c.n, c.m, c.herm_d, c.route, literal, s.has_q, f_R, c.sparse_affine);
+    const auto key = std::make_tuple(c.type, c.n, c.m, c.herm_d, c.route, literal, s.has_q, f_R, c.entries.sparse_affine);
     auto it = gmap.find(key);
     if (it == gmap.end()) {
       it = gmap.emplace(key, (int)ctx->groups.size()).first;
@@ -225,10 +225,11 @@ int GroupConstraints(cxk_context* ctx, const FinalizeSwitches& sw) {
       g.m = c.m;
       g.herm_d = c.herm_d;
       g.route = c.route;
-      g.literal = literal;
-      g.has_q = s.has_q;
-      g.f_R = f_R;
-      g.sp_affine = c.sparse_affine;
+      // the rest of the key: the one place outside a family's unit that writes its state (cone_state.h)
+      g.lmi.literal = literal;
+      g.quad.has_q = s.has_q;
+      g.lmi.f.R = f_R;
+      g.lmi.sa.on = c.entries.sparse_affine;
     }
     c.group = it->second;
     c.member = (int)ctx->groups[it->second].ids.size();
@@ -249,7 +250,7 @@ int UploadGroup(cxk_context* ctx, Group& g, const FinalizeSwitches& sw) {
   if (UploadDenseData(ctx, g, dense_a ? sz.a : 0, sz.c)) return CXK_FAILURE;
   CXK_TRY(g.W.alloc(sz.w * cnt));
   CXK_TRY(g.T1.alloc(sz.w * cnt));
-  CXK_TRY(g.T2.alloc(g.type == CXK_LINEAR ? sz.w * cnt : 0));
+  if (AllocLinearT2(ctx, g)) return CXK_FAILURE;
   CXK_TRY(g.dids.upload(g.ids));
   switch (g.route) {
     case ConeRoute::kLinearLds: case ConeRoute::kSocLds: case ConeRoute::kStatic: case ConeRoute::kOct:
@@ -421,7 +422,7 @@ int SyncMailbox(cxk_context* ctx) {
 bool TakeStepFromDeviceOk(const cxk_context* ctx) {
   if (ctx->world > 1 || ctx->use_ldlt) return false;
   for (const Group& g : ctx->groups)
-    if (g.type == CXK_LMI && g.large && !g.ids.empty()) return false;  // its step argument kernel takes the value
+    if (g.type == CXK_LMI && g.lmi.large && !g.ids.empty()) return false;  // its step argument kernel takes the value
   return true;
 }
 
@@ -482,7 +483,7 @@ bool StepTailOk(const cxk_context* ctx, int affine) {
     if (only) return false;
     only = &g;
   }
-  return only && only->type == CXK_LMI && !only->large && !only->literal && only->ids.size() == ctx->cons.size() &&
+  return only && only->type == CXK_LMI && !only->lmi.large && !only->lmi.literal && only->ids.size() == ctx->cons.size() &&
          LmiRowsServePrepare(*only);
 }
 namespace {

@@ -3,7 +3,7 @@
 // Host side = structure + launches only.  All fp64 state (A_i, C, W, Schur blocks, the
 // supernodal slab, right-hand sides) lives in HBM for the lifetime of the context; per
 // Newton step only scalars cross PCIe.
-#include "kkt_launch.h"
+#include "cone_units.h"  // what the counters ask the LMI unit (LmiAssemblyOf, LmiOnWideSpectrum)
 #include "kernels_gemm.hip.h"  // GemmArgs, LaunchGemmSplitK (cxk_gemm_f64)
 
 namespace cxk_host {
@@ -214,10 +214,10 @@ static int AllocateSystemBuffers(cxk_context* ctx) {
 static int FinalizeImpl(cxk_context* ctx) {
   const FinalizeSwitches sw = ReadFinalizeSwitches();
   for (const ConstraintRec& c : ctx->cons)
-    if (c.factored && c.herm_d) {
-      // Hermitian factors (order c.n = d x the hyper-complex order, f_F = L(F) of d R columns): the Taylor TakeStep
+    if (c.factors.given && c.herm_d) {
+      // Hermitian factors (order c.n = d x the hyper-complex order, factors.F = L(F) of d R columns): the Taylor TakeStep
       // has no LU; what bounds the order is the one-workgroup Lanczos of lmi_large_spectrum, then the int indexing
-      const int64_t N = c.n, R = c.f_R, d = c.herm_d;
+      const int64_t N = c.n, R = c.factors.R, d = c.herm_d;
       if (c.n > LmiLargeSpectrumMaxOrder()) {
         ctx->err = "a factored Hermitian constraint whose real representation has an order above " +
                    std::to_string(LmiLargeSpectrumMaxOrder()) + " is not supported (the vectors of its Lanczos run exceed the " +
@@ -229,15 +229,15 @@ static int FinalizeImpl(cxk_context* ctx) {
       CXK_DEMAND(d * R * R <= INT_MAX, "a factored Hermitian constraint whose d x R x R entries exceed the int range is not supported");
       CXK_DEMAND(N * d * R <= INT_MAX, "a factored Hermitian constraint whose N x dR entries (N = d n) exceed the int range is not supported");
       CXK_DEMAND((int64_t)c.m * c.m <= INT_MAX, "a factored Hermitian constraint whose m x m entries exceed the int range is not supported");
-    } else if (c.factored) {  // the limit of LmiLargeLuSolve, and the int indexing of kernels_lmi_factored.hip.h
+    } else if (c.factors.given) {  // the limit of LmiLargeLuSolve, and the int indexing of kernels_lmi_factored.hip.h
       CXK_DEMAND(c.n <= 1024, "a factored LMI of order above 1024 is not supported (one panel row per thread in the Pade LU)");
-      CXK_DEMAND((int64_t)c.n * c.f_R <= INT_MAX && (int64_t)c.f_R * c.f_R <= INT_MAX && (int64_t)c.m * c.m <= INT_MAX,
+      CXK_DEMAND((int64_t)c.n * c.factors.R <= INT_MAX && (int64_t)c.factors.R * c.factors.R <= INT_MAX && (int64_t)c.m * c.m <= INT_MAX,
                  "a factored LMI whose n x R, R x R or m x m entries exceed the int range is not supported");
     }
   // matrix inequalities given by their matrices: any order whose n x n entries the kernels can index; beyond the
   // one-workgroup Lanczos run (lmi_large_spectrum) only with the chip-wide one (cxk_set_wide_spectrum)
   for (const ConstraintRec& c : ctx->cons)
-    if (c.type == CXK_LMI && !c.factored) {
+    if (c.type == CXK_LMI && !c.factors.given) {
       CXK_DEMAND((int64_t)c.n * c.n <= INT_MAX,
                  "a matrix inequality of order above 46340 is not supported (the kernels index its n x n entries with ints)");
       if (c.n > LmiLargeSpectrumMaxOrder() && WideSpectrumMode(ctx, sw) == 0) {
@@ -378,14 +378,14 @@ int cxk_add_lmi_factored(cxk_context* ctx, int n, int m, const int* rank_ptr, co
   r.type = CXK_LMI;
   r.n = n;
   r.m = m;
-  r.factored = true;
-  r.f_R = R;
-  r.f_ptr.assign(rank_ptr, rank_ptr + m + 1);
-  r.f_F.assign(F, F + nr);
+  r.factors.given = true;
+  r.factors.R = R;
+  r.factors.ptr.assign(rank_ptr, rank_ptr + m + 1);
+  r.factors.F.assign(F, F + nr);
   if (sigma)
-    r.f_sigma.assign(sigma, sigma + R);
+    r.factors.sigma.assign(sigma, sigma + R);
   else
-    r.f_sigma.assign((size_t)R, 1.0);
+    r.factors.sigma.assign((size_t)R, 1.0);
   r.C.assign(C, C + nn);
   return AddConstraint(ctx, std::move(r), vars);
 }
@@ -413,8 +413,8 @@ int cxk_add_lmi_coo(cxk_context* ctx, int n, int m, const int* ptr, const int* r
   r.n = n;
   r.m = m;
   r.csr_only = true;
-  r.affine_default = -1;
-  r.e_ptr.assign((size_t)m + 2, 0);
+  r.entries.affine_default = -1;
+  r.entries.ptr.assign((size_t)m + 2, 0);
   std::vector<std::pair<int, double>> list;  // (row | col << 16, value): both triangles of one matrix
   for (int i = 0; i <= m; i++) {
     list.clear();
@@ -431,15 +431,15 @@ int cxk_add_lmi_coo(cxk_context* ctx, int n, int m, const int* ptr, const int* r
       if (list[s].first == list[s - 1].first) return refuse("a list names a position twice");
     for (const auto& e : list)
       if (e.second != 0.0) {  // explicit zeros are dropped
-        r.e_rc.push_back(e.first);
-        r.e_val.push_back(e.second);
+        r.entries.rc.push_back(e.first);
+        r.entries.val.push_back(e.second);
       }
-    if (r.e_rc.size() > (size_t)INT_MAX) return refuse("more than 2^31 nonzeros");
-    r.e_ptr[(size_t)i + 1] = (int)r.e_rc.size();
+    if (r.entries.rc.size() > (size_t)INT_MAX) return refuse("more than 2^31 nonzeros");
+    r.entries.ptr[(size_t)i + 1] = (int)r.entries.rc.size();
   }
   r.C.assign((size_t)n * n, 0.0);
-  for (int e = r.e_ptr[m]; e < r.e_ptr[m + 1]; e++)
-    r.C[(size_t)(r.e_rc[e] & 0xffff) + (size_t)(r.e_rc[e] >> 16) * n] = r.e_val[e];
+  for (int e = r.entries.ptr[m]; e < r.entries.ptr[m + 1]; e++)
+    r.C[(size_t)(r.entries.rc[e] & 0xffff) + (size_t)(r.entries.rc[e] >> 16) * n] = r.entries.val[e];
   return AddConstraint(ctx, std::move(r), vars);
 }
 
@@ -536,15 +536,15 @@ int cxk_add_hermitian_factored(cxk_context* ctx, int n, int d, int m, const int*
   r.herm_d = d;
   r.n = d * n;
   r.m = m;
-  r.factored = true;
-  r.f_R = R;
-  r.f_ptr.assign(rank_ptr, rank_ptr + m + 1);
-  r.f_F.resize((size_t)d * d * nr);  // L(F): (d n) x (d R); its first R columns are the stacked planes
-  if (R > 0) EmbedPlanesRect(d, n, R, F, r.f_F.data());
+  r.factors.given = true;
+  r.factors.R = R;
+  r.factors.ptr.assign(rank_ptr, rank_ptr + m + 1);
+  r.factors.F.resize((size_t)d * d * nr);  // L(F): (d n) x (d R); its first R columns are the stacked planes
+  if (R > 0) EmbedPlanesRect(d, n, R, F, r.factors.F.data());
   if (sigma)
-    r.f_sigma.assign(sigma, sigma + R);
+    r.factors.sigma.assign(sigma, sigma + R);
   else
-    r.f_sigma.assign((size_t)R, 1.0);
+    r.factors.sigma.assign((size_t)R, 1.0);
   r.C.resize((size_t)r.n * r.n);
   EmbedPlanes(d, n, C, r.C.data());
   return AddConstraint(ctx, std::move(r), vars);
@@ -583,7 +583,7 @@ static int AddCsrConstraint(cxk_context* ctx, const char* fn, const char* size, 
   rec.m = m;
   rec.csr_only = true;
   rec.C.assign(c, c + rows);
-  rec.sp_rowptr.assign((size_t)rows + 1, 0);
+  rec.rows.ptr.assign((size_t)rows + 1, 0);
   std::vector<std::pair<int, double>> row;
   for (int r = 0; r < rows; r++) {
     row.clear();
@@ -596,10 +596,10 @@ static int AddCsrConstraint(cxk_context* ctx, const char* fn, const char* size, 
       if (row[s].first == row[s - 1].first) return refuse("a row names a column twice");
     for (const auto& e : row)
       if (e.second != 0.0) {  // explicit zeros are dropped
-        rec.sp_col.push_back(e.first);
-        rec.sp_val.push_back(e.second);
+        rec.rows.col.push_back(e.first);
+        rec.rows.val.push_back(e.second);
       }
-    rec.sp_rowptr[(size_t)r + 1] = (int)rec.sp_col.size();
+    rec.rows.ptr[(size_t)r + 1] = (int)rec.rows.col.size();
   }
   return AddConstraint(ctx, std::move(rec), vars);
 }
@@ -763,7 +763,7 @@ int cxk_set_sparse_affine(cxk_context* ctx, int mode) {
 int cxk_count_sparse_affine(const cxk_context* ctx) {
   if (!ctx || !ctx->finalized) return -1;
   int k = 0;
-  for (size_t i = 0; i < ctx->cons.size(); i++) k += ctx->owned[i] && ctx->cons[i].route == ConeRoute::kLmiSparse && ctx->cons[i].sparse_affine;
+  for (size_t i = 0; i < ctx->cons.size(); i++) k += ctx->owned[i] && ctx->cons[i].route == ConeRoute::kLmiSparse && ctx->cons[i].entries.sparse_affine;
   return k;
 }
 
@@ -778,7 +778,7 @@ int cxk_count_wide_spectrum(const cxk_context* ctx) {
   if (!ctx || !ctx->finalized) return -1;
   int k = 0;
   for (const Group& g : ctx->groups)
-    if (g.ws_wide.n) k += (int)g.ids.size();
+    if (LmiOnWideSpectrum(g)) k += (int)g.ids.size();
   return k;
 }
 
@@ -1503,7 +1503,7 @@ int cxk_count_sparse_lmi(const cxk_context* ctx) { return CountOnRoute(ctx, Cone
 int cxk_count_factored_lmi(const cxk_context* ctx) {
   if (!ctx || !ctx->finalized) return -1;
   int k = 0;  // (how a constraint was added, not a choice of cxk_finalize: a host-only context counts them too)
-  for (size_t i = 0; i < ctx->cons.size(); i++) k += ctx->cons[i].type == CXK_LMI && ctx->owned[i] && ctx->cons[i].factored;
+  for (size_t i = 0; i < ctx->cons.size(); i++) k += ctx->cons[i].type == CXK_LMI && ctx->owned[i] && ctx->cons[i].factors.given;
   return k;
 }
 
@@ -1552,7 +1552,8 @@ int cxk_count_lmi_kernel(const cxk_context* ctx, int which) {
   int k = 0;
   for (const Group& g : ctx->groups) {
     if (g.type != CXK_LMI || g.route == ConeRoute::kLmiFactored) continue;
-    const int kind = g.route == ConeRoute::kLmiSparse ? 4 : g.assembly == LmiAssembly::kGemm ? 3 : g.assembly == LmiAssembly::kMfma ? 2 : 0;
+    const LmiAssembly how = LmiAssemblyOf(g);
+    const int kind = g.route == ConeRoute::kLmiSparse ? 4 : how == LmiAssembly::kGemm ? 3 : how == LmiAssembly::kMfma ? 2 : 0;
     if (kind == which) k += (int)g.ids.size();
   }
   return k;
@@ -1565,13 +1566,13 @@ int cxk_assembly_work(const cxk_context* ctx, double* bytes, double* flops) {
     const ConstraintRec& c = ctx->cons[i];
     if (c.type != CXK_LMI || !ctx->owned[i]) continue;
     const double n = c.n, m = c.m;
-    if (c.factored) {
+    if (c.factors.given) {
       // Z = W F, Y = C Z, P = F' Z (lower), C W and W (C W), then the sums of the finalize kernel; bytes: F, W, C,
       // Z (written, read twice), Y, P, the two squares of the scalars, G's triangle and the three vectors
-      const double R = c.f_R;
+      const double R = c.factors.R;
       double terms = 0;  // sum over i >= j of r_i r_j
       for (int i = 0, below = 0; i < c.m; i++) {
-        const double ri = c.f_ptr[i + 1] - c.f_ptr[i];
+        const double ri = c.factors.ptr[i + 1] - c.factors.ptr[i];
         below += (int)ri;
         terms += ri * below;
       }

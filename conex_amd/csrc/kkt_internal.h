@@ -26,6 +26,7 @@
 
 #include "../../include/conex_kkt_hip.h"
 #include "cone_route.h"   // ConeRoute, LmiAssembly, kLdsLimit and the dynamic-LDS formulas: plain C++
+#include "cone_state.h"   // DevBuf, Group and the state of each cone family
 #include "kkt_records.h"  // record and argument types, FactorPlan, TopDenseArgs: no device code
 #include "lmi_types.h"
 #include "symbolic.h"
@@ -47,146 +48,37 @@ struct ConstraintRec {
   // every A_i and C equals its transpose.  The fast kernels use tr(W A_i W A_j) = tr(P_i P_j),
   // P = A W, which needs that; anything else takes the literal kernels (dense_lmi_constraint.cc:72-88)
   bool symmetric = true;
+  bool csr_only = false;  // added by cxk_add_linear_csr / cxk_add_soc_csr / cxk_add_lmi_coo: no dense A
+  // What only one way of adding a constraint fills:
   // linear block: its nonzeros by rows, columns ascending (cxk_add_linear_csr gives them and leaves A empty: such a
-  // block can only take the sparse route; GroupConstraints reads them off the A of a dense-added block)
-  bool csr_only = false;  // added by cxk_add_linear_csr / cxk_add_soc_csr: no dense A
-  // second-order cone on the sparse route (kernels_soc_sparse.hip.h): the same sp_* vectors hold the nonzeros of its
+  // block can only take the sparse route; GroupConstraints reads them off the A of a dense-added block).
+  // second-order cone on the sparse route (kernels_soc_sparse.hip.h): the same vectors hold the nonzeros of its
   // (n + 1) x m matrix, given by cxk_add_soc_csr (csr_only) or read off the A of a cone added by cxk_add_soc
-  std::vector<int> sp_rowptr, sp_col;
-  std::vector<double> sp_val;
+  struct RowNonzeros {
+    std::vector<int> ptr, col;
+    std::vector<double> val;
+  } rows;
   // CXK_LMI given by factors (cxk_add_lmi_factored, kernels_lmi_factored.hip.h): A_i = sum sigma_k f_k f_k', k in
-  // [f_ptr[i], f_ptr[i + 1]); F is n x f_R column-major.  A stays empty: the matrices are never formed.
-  bool factored = false;
-  int f_R = 0;
-  std::vector<int> f_ptr;
-  std::vector<double> f_F, f_sigma;
+  // [ptr[i], ptr[i + 1]); F is n x R column-major.  A stays empty: the matrices are never formed.
+  struct Factors {
+    bool given = false;
+    int R = 0;
+    std::vector<int> ptr;
+    std::vector<double> F, sigma;
+  } factors;
   // CXK_LMI given by its nonzeros (cxk_add_lmi_coo; csr_only is set and A stays empty, C is the n x n square the slack
   // kernels read): list i < m holds A_i, list m holds C, both triangles of each, sorted by column then row -- the order
-  // in which UploadSparseLmi scans a dense matrix -- as e_rc = row | col << 16 and e_val from e_ptr[i] on (m + 2 pointers)
-  std::vector<int> e_ptr, e_rc;
-  std::vector<double> e_val;
-  // how a sparse group beyond the LDS-resident orders evaluates this constraint's affine term when nobody says
-  // (cxk_set_sparse_affine, CXK_SPARSE_AFFINE): 0 the two GEMMs, -1 from C's nonzeros when that pays; and what
-  // GroupConstraints made of it (members of one group agree)
-  int affine_default = 0;
-  bool sparse_affine = false;
+  // in which UploadSparseLmi scans a dense matrix -- as rc = row | col << 16 and val from ptr[i] on (m + 2 pointers)
+  struct Entries {
+    std::vector<int> ptr, rc;
+    std::vector<double> val;
+    // how a sparse group beyond the LDS-resident orders evaluates this constraint's affine term when nobody says
+    // (cxk_set_sparse_affine, CXK_SPARSE_AFFINE): 0 the two GEMMs, -1 from C's nonzeros when that pays; and what
+    // GroupConstraints made of it (members of one group agree)
+    int affine_default = 0;
+    bool sparse_affine = false;
+  } entries;
 };
-
-template <typename T>
-struct DevBuf {
-  T* p = nullptr;
-  size_t n = 0;
-  ~DevBuf() { release(); }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-  }
-  // `zeroed`: the code relies on the initial zeros (slots that are never written but read).
-  // Everything else is scratch that must be written before it is read: with CXK_DEBUG_FILL_NAN=1
-  // in the environment such buffers start as NaN (all-ones bytes), so that a read of unwritten
-  // memory shows up in the results instead of passing by luck (diagnostic runs of the test suite).
-  hipError_t alloc(size_t count, bool zeroed = false) {
-    release();
-    n = count;
-    if (count == 0) count = 1;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), count * sizeof(T));
-    static const bool nan_fill = [] {
-      const char* v = getenv("CXK_DEBUG_FILL_NAN");
-      return v && atoi(v) != 0;
-    }();
-    // the fill runs on the null stream, kernels on the context's stream, which may be
-    // non-blocking (no implicit ordering with the null stream): wait for it on the host
-    if (e == hipSuccess) e = hipMemset(p, (nan_fill && !zeroed) ? 0xFF : 0, count * sizeof(T));
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    return e;
-  }
-  hipError_t upload(const std::vector<T>& v) {
-    hipError_t e = alloc(v.size());
-    if (e != hipSuccess || v.empty()) return e;
-    e = hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    return e;
-  }
-};
-
-struct Group {
-  int type = 0, n = 0, m = 0;
-  std::vector<int> ids;
-  DevBuf<double> A, C, W, T1, T2;
-  DevBuf<double> Apad;  // lmi_schur_mfma at a padded order: [A_1 .. A_m | C] per member, zero-padded (LmiMfmaPaddedOrder)
-  DevBuf<int> dids;
-  bool has_q = false;             // CXK_QUAD: the members carry an inner-product matrix Q
-  DevBuf<double> Aleft;           // Hermitian C / H groups on the GEMM assembly: first n / herm_d columns of [A_i | C]
-  DevBuf<double> Apk;             // CXK_LMI: packed lower triangles of the A_i (LmiGroup::Apk), may be empty
-  DevBuf<double> qQ, qGram, qS;   // CXK_QUAD: Q, A1' Q A1, the state kept between PrepareStep and TakeStep
-  int herm_d = 0;
-  // the set of kernels every member runs on, and for CXK_LMI how the Schur complement is assembled: the batched MFMA
-  // GEMM pipeline always when `large`, and for LDS-resident shapes from order 9 up without a register-kernel instance,
-  // where it measured 1.5-3.3x faster than the LDS kernel (cone_route.h: Choose, ChooseLmiAssembly)
-  ConeRoute route = ConeRoute::kStatic;
-  LmiAssembly assembly = LmiAssembly::kGeneric;
-  // lmi_schur_mfma launches of this group so far: an odd one walks each workgroup's constraints backwards, so
-  // that it starts on the operands its predecessor ended with (cxk_context::lmi_order_forward turns that off)
-  unsigned schur_launches = 0;
-  bool literal = false;  // non-symmetric data: literal kernels only
-  // orders beyond the LDS-resident kernels: HBM-resident matrices + MFMA GEMM pipeline
-  bool large = false;
-  // a `large` group whose Lanczos runs take the chip-wide kernels (kernels_lmi_wide.hip.h, cxk_set_wide_spectrum):
-  // their per-constraint work space; empty: lmi_large_spectrum on one workgroup per constraint
-  DevBuf<double> ws_wide;
-  bool wide_reduce = false;  // ... with lmi_wide_reduce between pass and step (orders from kWideReduceMinOrder on)
-  DevBuf<double> ws_main, ws_gf, ws_part;
-  DevBuf<int> ws_piv;
-  int splits = 1;
-  // sparse LMI groups (kLmiSparse): nonzeros matrix-major and position-major instead of the dense A
-  int sp_lpp = 1;                  // lanes sharing one (i, j) pair sum
-  int sp_chunks = 1, sp_emax = 0;  // sp_emax: most nonzeros in one constraint
-  bool sp_cdense = false;          // dense affine term: X = W C W instead of pair sums with C
-  bool sp_small = false;           // W (and X) of a constraint fit in LDS
-  DevBuf<int> sp_eptr, sp_erc, sp_pptr, sp_pvar, sp_pairs;
-  DevBuf<double> sp_eval, sp_pval;
-  // ... whose dense-route affine term is evaluated from C's nonzeros (cxk_set_sparse_affine; kernels_lmi_sparse.hip.h:
-  // lmi_affine_wc / _x / _scalars): every member's C by columns (sa_cptr: n + 1 pointers per member into sa_crc = row | col << 16
-  // and sa_cval), the distinct positions of W C W that an entry of some A_i or of C names (sa_pptr: count + 1 pointers
-  // into sa_prc = row | col << 16, ascending), and the slot in that list of every entry of the A_i (sa_eslot, beside
-  // sp_erc) and of C (sa_cslot, beside sa_crc).  (W C)' in the first half of ws_main, the values at the positions in
-  // the second.
-  bool sp_affine = false;
-  int sa_pmax = 0;  // most positions in one member
-  DevBuf<int> sa_cptr, sa_crc, sa_cslot, sa_pptr, sa_prc, sa_eslot;
-  DevBuf<double> sa_cval;
-  // second-order cones beyond LDS (kSocStreamed, cxk_set_streamed_cones): the kernels of kernels_soc_stream.hip.h; WA in ws_main,
-  // the Gram product's output in ws_gf and its split partials in ws_part (`splits` of them)
-  DevBuf<double> st_vec;   // s, Q(s) c, the slack: three vectors per cone
-  DevBuf<double> st_det;   // det(s) per cone
-  int st_stages = 0;       // CXK_SOC_STREAM_STAGES: 1 / 2 = the assembly stops after the vectors / the apply stage (timing runs)
-  // linear blocks on the tiled route (kLinearTiled, cxk_set_tiled_linear): the kernels of kernels_linear_tiled.hip.h; diag(w) A in
-  // ws_main, the Gram product's output in ws_gf, its split partials in ws_part, four doubles per row tile in lt_part
-  DevBuf<double> lt_part;
-  // quadratic cones held in HBM (kQuadStreamed, cxk_set_streamed_quadratic): the kernels of kernels_quad_stream.hip.h; the split
-  // partials of the products with Q in ws_part (`splits` column splits), every vector and scalar of the work space
-  // in st_vec (MakeQuadStream lays it out)
-  // linear blocks on the sparse route (kLinearSparse, cxk_set_sparse_linear): the kernels of kernels_linear_sparse.hip.h; every
-  // member's nonzeros by rows (ls_col, ls_val) and by columns (ls_crow, ls_cval) from ls_eptr[member] on, the
-  // pointers of its rows and columns relative to that; four doubles per row tile in lt_part.  No dense A.
-  DevBuf<int> ls_eptr, ls_rowptr, ls_col, ls_colptr, ls_crow;
-  DevBuf<double> ls_val, ls_cval;
-  // second-order cones on the sparse route (kSocSparse, cxk_set_sparse_soc): the kernels of kernels_soc_sparse.hip.h; the nonzeros
-  // in the ls_* arrays as above (rows = n + 1); the constants H = A' J A, h = A' J c, z = c' J c of every member in
-  // ss_const (formed on the device at finalize), s, ms, u = A' w and (det w, w . c) in st_vec (MakeSocSparse lays
-  // both out).  No dense A, no WA, no GEMM output.
-  DevBuf<double> ss_const;
-  // LMIs given by factors (kLmiFactored, cxk_add_lmi_factored): the kernels of kernels_lmi_factored.hip.h in front of the large-order
-  // route's (`large` is set: HBM-resident W, ws_main's step temporaries, ws_piv).  Every member's F, sigma, column
-  // pointers and column -> variable map; Z, Y, Fs and P in f_ws (MakeLmiFactored lays it out); the slices of the two
-  // scalars in ws_part.  No dense A.
-  bool f_rank_one = false;
-  int f_R = 0;
-  DevBuf<double> f_F, f_sigma, f_ws;
-  DevBuf<int> f_ptr, f_var;
-};
-
 
 }  // namespace cxk_host
 using namespace cxk_host;
@@ -272,7 +164,7 @@ struct cxk_context {
     int nwg = 0, shape_p = 0, shape_c = 0;
     DevBuf<BackPairEntry> tab;
   };
-  std::vector<std::unique_ptr<BackPair>> back_pairs;
+  std::vector<std::unique_ptr<BackPair>> back_pairs;  // (null: the level starts no pair)
   // supernodes whose panel exceeds LDS sit at the END of their level list and are swept one by
   // one through the blocked HBM path (kernels_kkt_big.hip.h); level_nh = count of the others
   std::vector<int> level_nh;
@@ -283,11 +175,11 @@ struct cxk_context {
   int big_gen = 0;
   // Level ranges below the top that are swept by one launch each: workgroup g of range r sweeps
   // one connected piece of the elimination forest restricted to levels [lo, hi)
-  struct SweepRange {
+  struct CXK_LOCAL SweepRange {
     int lo = 0, hi = 0, groups = 0, waves = 1;
     DevBuf<int> wg_lev;  // [groups * (hi - lo + 1)] positions into rec_r
   };
-  std::vector<std::unique_ptr<SweepRange>> ranges;
+  std::vector<SweepRange> ranges;
   // the top levels as one dense factorization (kernels_kkt_top.hip.h), when they hold <= 64 columns
   struct TopDense {
     bool on = false;
@@ -503,7 +395,7 @@ int Fail(cxk_context* ctx, const char* msg);
 // a constraint added by cxk_add_lmi_factored: such a context keeps its assembly and its tree in separate launches
 inline bool HasFactoredLmi(const cxk_context* ctx) {
   for (const ConstraintRec& c : ctx->cons)
-    if (c.factored) return true;
+    if (c.factors.given) return true;
   return false;
 }
 // two-shape chains tree_chain_lean is compiled for (kkt_tree_launch.hip, LaunchChain)

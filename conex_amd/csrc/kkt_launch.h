@@ -24,8 +24,6 @@ enum { kOpSum = 0, kOpMax = 1, kOpMin = 2 };  // ShardAllReduce, cxk_allreduce_f
 
 constexpr int kSparseCParts = 64;  // slices of the <w,c>, <c,Qc> sums of a dense C beyond LDS orders
 
-// A function only the units of the cxk_* path call in one another: not part of the library's dynamic symbols.
-#define CXK_LOCAL __attribute__((visibility("hidden")))
 
 // The current HIP device is per-thread state: every entry point binds the context's device for
 // its own duration and restores the caller's (another thread, a second context on another GPU,

@@ -43,7 +43,7 @@ double ConstraintWork(const ConstraintRec& c) {
   switch (c.type) {
     case CXK_LMI:
       // (a Hermitian factored record: n = d x order, P = L(F)' Z has d planes)
-      if (c.factored) return 4 * n * n * c.f_R + 2 * n * (double)c.f_R * c.f_R * std::max(c.herm_d, 1) + 4 * n * n * n;
+      if (c.factors.given) return 4 * n * n * c.factors.R + 2 * n * (double)c.factors.R * c.factors.R * std::max(c.herm_d, 1) + 4 * n * n * n;
       return 4 * n * n * n * (m + 1) + n * n * m * m;
     case CXK_LINEAR: return n * m * m;
     case CXK_SOC: return (n + 1) * m * m;
@@ -1691,10 +1691,10 @@ int PlanRanges(cxk_context* ctx) {
       continue;
     }
     if (hi - lo > 1) {
-      auto rg = std::make_unique<cxk_context::SweepRange>();
-      rg->lo = lo;
-      rg->hi = hi;
-      rg->groups = (int)pieces.size();
+      cxk_context::SweepRange rg;
+      rg.lo = lo;
+      rg.hi = hi;
+      rg.groups = (int)pieces.size();
       std::vector<int> tab;
       size_t widest = 1;
       for (auto& piece : pieces) {
@@ -1705,8 +1705,8 @@ int PlanRanges(cxk_context* ctx) {
         }
         tab.push_back((int)rr.size());
       }
-      rg->waves = (int)widest;
-      CXK_TRY(rg->wg_lev.upload(tab));
+      rg.waves = (int)widest;
+      CXK_TRY(rg.wg_lev.upload(tab));
       ctx->ranges.push_back(std::move(rg));
     }
     lo = hi;

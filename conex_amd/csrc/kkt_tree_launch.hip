@@ -695,7 +695,7 @@ int LaunchTreeCore(cxk_context* ctx, int mode, bool with_rhs, bool backward) {
   auto range_at = [&](int l) -> cxk_context::SweepRange* {
     if (ctx->no_ranges) return nullptr;
     for (auto& r : ctx->ranges)
-      if (r->lo == l) return r.get();
+      if (r.lo == l) return &r;
     return nullptr;
   };
   std::vector<std::pair<int, cxk_context::SweepRange*>> order;  // (first level, range or null)
