@@ -47,27 +47,37 @@ namespace cxk {
 
 constexpr int kFusedSpinLimit = 1 << 18;
 
-// Diagnostic build (-DCXK_FUSED_STAMPS, `make dbg`): every wavefront keeps seven time stamps
-// (s_memrealtime: 100 MHz, one clock for the whole chip) in registers and writes them at its end to
-// a buffer nothing else reads (tools/fused_tree_stamps.py).
+// Diagnostic build (-DCXK_FUSED_STAMPS, `make dbg`): every wavefront keeps sixteen words in registers -- time stamps
+// 0 .. 9 (s_memrealtime: 100 MHz, one clock for the whole chip), counts 10 .. 14 (10, 11 placement; 12, 14 polls), its
+// level in 15 -- and writes them at its end to a buffer nothing else reads (tools/fused_tree_stamps.py).
+// The stamps are an object, FusedStamps, that can be handed to whoever stamps or counts; in the normal build it is
+// FusedNoStamps: empty, its methods no-ops (their arguments have no side effects, so nothing of them is left).
+struct FusedNoStamps {
+  __device__ __forceinline__ void Stamp(int) {}
+  __device__ __forceinline__ void Count(int, long long) {}
+  __device__ __forceinline__ void Placement() {}
+  __device__ __forceinline__ void Flush(int) {}
+};
 #ifdef CXK_FUSED_STAMPS
 constexpr int kFusedStampWaves = 8192;
 __device__ long long g_fused_tree_stamp[kFusedStampWaves * 16];
-#define FT_STAMP(i) ft_stamp[i] = __builtin_amdgcn_s_memrealtime()
-#define FT_COUNT(i, v) ft_stamp[i] = (v)
-#define FT_STAMP_DECL long long ft_stamp[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}
-#define FT_STAMP_FLUSH(level)                                                              \
-  do {                                                                                     \
-    if ((threadIdx.x & 63) == 0 && blockIdx.x < kFusedStampWaves) {                        \
-      ft_stamp[15] = (level);                                                              \
-      for (int i_ = 0; i_ < 16; i_++) g_fused_tree_stamp[blockIdx.x * 16 + i_] = ft_stamp[i_]; \
-    }                                                                                      \
-  } while (0)
+struct FusedStamps {
+  long long t[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  __device__ __forceinline__ void Stamp(int i) { t[i] = __builtin_amdgcn_s_memrealtime(); }
+  __device__ __forceinline__ void Count(int i, long long v) { t[i] = v; }
+  __device__ __forceinline__ void Placement() {
+    t[10] = __builtin_amdgcn_s_getreg((31 << 11) | 4);   // HW_ID: wave, SIMD, CU, SH, SE (tools/fused_tree_stamps.py: placement)
+    t[11] = __builtin_amdgcn_s_getreg((31 << 11) | 20);  // XCC_ID
+  }
+  __device__ __forceinline__ void Flush(int level) {
+    if ((threadIdx.x & 63) == 0 && blockIdx.x < kFusedStampWaves) {
+      t[15] = level;
+      for (int i = 0; i < 16; i++) g_fused_tree_stamp[blockIdx.x * 16 + i] = t[i];
+    }
+  }
+};
 #else
-#define FT_STAMP(i) do { } while (0)
-#define FT_COUNT(i, v) do { } while (0)
-#define FT_STAMP_DECL do { } while (0)
-#define FT_STAMP_FLUSH(level) do { } while (0)
+using FusedStamps = FusedNoStamps;
 #endif
 
 __device__ __forceinline__ double LoadAgent(const double* p) {
@@ -88,10 +98,43 @@ __device__ __forceinline__ void SleepUnits(int units) {
   for (; units >= 4; units -= 4) __builtin_amdgcn_s_sleep(4);
 }
 
-__device__ __forceinline__ void ReportTimeout(const FusedTreeArgs& A) {
-  if ((threadIdx.x & 63) == 0) {
+// A wait ran out: reported from lane 0, or (every_lane: a wait that is each lane's own, WaitValue) from every lane that calls
+__device__ __forceinline__ void ReportTimeout(const FusedTreeArgs& A, bool every_lane = false) {
+  if (every_lane || (threadIdx.x & 63) == 0) {
     atomicExch(A.fail + 1, A.tag);
     __hip_atomic_store(A.host_flag, 1.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+
+// The run's two sets of hand-off slots: this run's (G) and the other one, re-armed at the end (O); and those of
+// right-hand sides 1, 2 of the triple launch (T, TO), which alternate with the triple launches only (A.tgen).
+struct FusedSlots {
+  double *handG, *handO, *ysG, *ysO;
+  double *handT, *handTO, *ysT, *ysTO;
+};
+__device__ __forceinline__ FusedSlots FusedSlotSets(const FusedTreeArgs& A) {
+  FusedSlots Q;
+  const int gen = A.gen;
+  Q.handG = A.hand + (int64_t)gen * A.hand_stride;        // this run's set of hand-off slots
+  Q.handO = A.hand + (int64_t)(gen ^ 1) * A.hand_stride;  // the other one: re-armed at the end
+  Q.ysG = A.ysig + (int64_t)gen * A.ysig_stride;
+  Q.ysO = A.ysig + (int64_t)(gen ^ 1) * A.ysig_stride;
+  // (right-hand sides 1, 2: this run's set and the other one)
+  Q.handT = A.hand + (int64_t)A.tgen * A.hand_stride;
+  Q.handTO = A.hand + (int64_t)(A.tgen ^ 1) * A.hand_stride;
+  Q.ysT = A.ysig + (int64_t)A.tgen * A.ysig_stride;
+  Q.ysTO = A.ysig + (int64_t)(A.tgen ^ 1) * A.ysig_stride;
+  return Q;
+}
+
+// Re-arm published slots in the other set: slot(r) = where value number lane + 64 r of the supernode's nv sits there
+template <int PR, class SLOT>
+__device__ __forceinline__ void FusedRearm(int nv, SLOT slot) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int r = 0; r < PR; r++) {
+    double* p = slot(r);
+    if (lane + 64 * r < nv) StoreAgent(p, SentinelValue());
   }
 }
 
@@ -188,12 +231,11 @@ __device__ __forceinline__ void FusedSupernode(const FusedTreeArgs& A, const int
   constexpr int NVMAX = SMAX * (SMAX + 1) / 2 + NRHS * SMAX;  // values a supernode publishes
   constexpr int PR = (NVMAX + 63) / 64;                // ... in this many store instructions
   const int lane = threadIdx.x & 63;
-  FT_STAMP_DECL;
-  FT_STAMP(0);
-  FT_COUNT(10, __builtin_amdgcn_s_getreg((31 << 11) | 4));   // HW_ID: wave, SIMD, CU, SH, SE (tools/fused_tree_stamps.py: placement)
-  FT_COUNT(11, __builtin_amdgcn_s_getreg((31 << 11) | 20));  // XCC_ID
+  FusedStamps T;
+  T.Stamp(0);
+  T.Placement();
   const SnRec R = DecodeRec(w);
-  FT_STAMP(1);  // the record is here
+  T.Stamp(1);  // the record is here
   auto f = [&](int i) { return __builtin_amdgcn_readlane(w, 32 + i); };
   const int ns = R.ns, s = R.nsep;
   const bool is_row = lane < ns;
@@ -212,16 +254,7 @@ __device__ __forceinline__ void FusedSupernode(const FusedTreeArgs& A, const int
     st = is_row ? (unsigned)ns : 1u;
     lim = is_row ? lane + 1 : (is_sep ? ns : 0);
   }
-  const int gen = A.gen;
-  double* handG = A.hand + (int64_t)gen * A.hand_stride;        // this run's set of hand-off slots
-  double* handO = A.hand + (int64_t)(gen ^ 1) * A.hand_stride;  // the other one: re-armed at the end
-  double* ysG = A.ysig + (int64_t)gen * A.ysig_stride;
-  double* ysO = A.ysig + (int64_t)(gen ^ 1) * A.ysig_stride;
-  // (right-hand sides 1, 2: this run's set and the other one)
-  double* handT = A.hand + (int64_t)A.tgen * A.hand_stride;
-  double* handTO = A.hand + (int64_t)(A.tgen ^ 1) * A.hand_stride;
-  double* ysT = A.ysig + (int64_t)A.tgen * A.ysig_stride;
-  double* ysTO = A.ysig + (int64_t)(A.tgen ^ 1) * A.ysig_stride;
+  const FusedSlots Q = FusedSlotSets(A);
   const int pub_beg = __builtin_amdgcn_readlane(w, 23);
   const int npairs = s * (s + 1) / 2, nv = npairs + NRHS * s;
 
@@ -444,7 +477,7 @@ __device__ __forceinline__ void FusedSupernode(const FusedTreeArgs& A, const int
     rv[1] = is_row ? aqv * A.cs : 0.0;
     rv[2] = is_row ? awv : 0.0;
   }
-  FT_STAMP(2);  // panel and right-hand side assembled (own block; further sources still to add)
+  T.Stamp(2);  // panel and right-hand side assembled (own block; further sources still to add)
 
   const bool pulls = ntg > 0 || R.mf > 0;
   if (nxt > 0 || ntg > 0) {
@@ -495,10 +528,10 @@ __device__ __forceinline__ void FusedSupernode(const FusedTreeArgs& A, const int
     // polled first, then the values) paid two dependent round trips behind every level of the tree.
     double pv0[MMAX], pv1[MMAX], pb[MFMAX];
     double pbx[NRHS > 1 ? NRHS - 1 : 1][MFMAX];  // forward values of right-hand sides 1, 2
-    const double* srcx = handT + A.updb_base + A.fwd_stride + R.fbase + (is_row ? lane : 0) * R.mf;  // (2: fwd_stride further)
-    const double* src0 = handG + R.ubase + (int64_t)(lane < ntg ? lane : 0) * R.m;
-    const double* src1 = handG + R.ubase + (int64_t)(lane + 64 < ntg ? lane + 64 : 0) * R.m;
-    const double* srcb = handG + A.updb_base + R.fbase + (is_row ? lane : 0) * R.mf;
+    const double* srcx = Q.handT + A.updb_base + A.fwd_stride + R.fbase + (is_row ? lane : 0) * R.mf;  // (2: fwd_stride further)
+    const double* src0 = Q.handG + R.ubase + (int64_t)(lane < ntg ? lane : 0) * R.m;
+    const double* src1 = Q.handG + R.ubase + (int64_t)(lane + 64 < ntg ? lane + 64 : 0) * R.m;
+    const double* srcb = Q.handG + A.updb_base + R.fbase + (is_row ? lane : 0) * R.mf;
     // Lists longer than the MMAX slots a round holds (the interfaces near the top of a segmented chain
     // collect an update from every step that carried them: ~2 log2(segments)) are taken MMAX slots at
     // a time, in slot order -- the order of the subtractions is the list's either way.
@@ -546,7 +579,7 @@ __device__ __forceinline__ void FusedSupernode(const FusedTreeArgs& A, const int
         for (int spin = 0;; spin++) {
           CXK_FUSED_ISSUE(q0, qb, qbx);
           if (arrived(p0, pf, pfx)) {
-            FT_COUNT(12, 2 * spin);
+            T.Count(12, 2 * spin);
             break;
           }
           CXK_FUSED_ISSUE(p0, pf, pfx);
@@ -562,7 +595,7 @@ __device__ __forceinline__ void FusedSupernode(const FusedTreeArgs& A, const int
 #pragma unroll
                 for (int i = 0; i < MM; i++) pfx[q][i] = qbx[q][i];
             }
-            FT_COUNT(12, 2 * spin + 1);
+            T.Count(12, 2 * spin + 1);
             break;
           }
         }
@@ -623,7 +656,7 @@ __device__ __forceinline__ void FusedSupernode(const FusedTreeArgs& A, const int
 #pragma unroll
         for (int i = 0; i < MFMAX; i++) pending |= is_row & IsSentinel(pb[i]);
         if (__ballot(pending) == 0) {
-          FT_COUNT(12, spin);
+          T.Count(12, spin);
           break;
         }
         if (spin >= kFusedSpinLimit) {
@@ -689,7 +722,7 @@ __device__ __forceinline__ void FusedSupernode(const FusedTreeArgs& A, const int
 #pragma unroll
     for (int q = 0; q < NRHS; q++) a[RB + q] = rv[q];
   }
-  FT_STAMP(3);  // descendants' values are in
+  T.Stamp(3);  // descendants' values are in
   bool bad = false;
   if constexpr (NSMAX > 32) {
     // a supernode of 33 .. 64 columns without separator (the one dense block of a single-constraint
@@ -704,7 +737,7 @@ __device__ __forceinline__ void FusedSupernode(const FusedTreeArgs& A, const int
   } else {
     ElimSteps<NSMAX, SMAX, 0, NCOL, !ROWRHS>::run(a, lane, bad, ns);  // (ROWRHS: the pivots are judged by the solution, below)
   }
-  FT_STAMP(4);  // eliminated
+  T.Stamp(4);  // eliminated
   if (bad && lane == 0) atomicExch(A.fail + 1, A.tag);  // (carries on: everybody above must still drain)
   // ---- publish (the ancestors are waiting): the values sit in the separator lanes' registers --
   // value (k, c), c >= k, in a[NSMAX + c] of lane NSMAX + k -- and leave through LDS so that ONE
@@ -720,12 +753,12 @@ __device__ __forceinline__ void FusedSupernode(const FusedTreeArgs& A, const int
 #pragma unroll
       for (int r = 0; r < PR; r++) {
         const double v = -my[prd[r]];
-        if (lane + 64 * r < nv) StoreAgent((NRHS > 1 && pdt[r] ? handT : handG) + pd[r], v);
+        if (lane + 64 * r < nv) StoreAgent((NRHS > 1 && pdt[r] ? Q.handT : Q.handG) + pd[r], v);
       }
       WaveSync();
     }
   }
-  FT_STAMP(7);  // published
+  T.Stamp(7);  // published
   if constexpr (UP_ONLY) {
 #pragma unroll
     for (int j = 0; j < NSMAX; j++)
@@ -736,11 +769,7 @@ __device__ __forceinline__ void FusedSupernode(const FusedTreeArgs& A, const int
       A.AQc[R.start + lane] = aqv;
     }
     if constexpr (SMAX > 0) {
-      if (s > 0) {
-#pragma unroll
-        for (int r = 0; r < PR; r++)
-          if (lane + 64 * r < nv) StoreAgent(handO + pd[r], SentinelValue());
-      }
+      if (s > 0) FusedRearm<PR>(nv, [&](int r) { return Q.handO + pd[r]; });
     }
     return;
   }
@@ -759,13 +788,13 @@ __device__ __forceinline__ void FusedSupernode(const FusedTreeArgs& A, const int
     for (int j = 0; j < NSMAX; j++)
       if (j < lim) base[o0 + j * st] = a[j];
   }
-  FT_STAMP(8);  // factor stored
+  T.Stamp(8);  // factor stored
   const int li = active ? lane : 0;
   double col[NSMAX];
 #pragma unroll
   for (int k = 0; k < NSMAX; k++) col[k] = my[65 * li + k];
   double dg = my[66 * li];
-  FT_STAMP(9);  // columns of L back from the image
+  T.Stamp(9);  // columns of L back from the image
   constexpr int QN = SMAX < 8 ? SMAX : 8;
   double bv[QN > 0 ? QN : 1], yv[QN > 0 ? QN : 1], Mb[QN > 0 ? QN : 1];
   double yvx[NRHS > 1 ? NRHS - 1 : 1][QN > 0 ? QN : 1];
@@ -856,7 +885,7 @@ __device__ __forceinline__ void FusedSupernode(const FusedTreeArgs& A, const int
       // lane qq < cnt polls the solution entry of separator variable qq
       const int sepw = __builtin_amdgcn_ds_bpermute(4 * (24 + (lane < 8 ? lane : 0)), w);
       const int sidx = lane < cnt ? (sepw & 0x3ffffff) : (R.sep[0] & 0x3ffffff);
-      const double* src = ysG + sidx;
+      const double* src = Q.ysG + sidx;
       double v;
       double vx[NRHS > 1 ? NRHS - 1 : 1];
       vx[0] = 0.0;
@@ -866,12 +895,12 @@ __device__ __forceinline__ void FusedSupernode(const FusedTreeArgs& A, const int
         if constexpr (NRHS > 1) {
 #pragma unroll
           for (int q = 0; q < NRHS - 1; q++) {
-            vx[q] = LoadAgent(ysT + (int64_t)(1 + q) * A.y_stride + sidx);
+            vx[q] = LoadAgent(Q.ysT + (int64_t)(1 + q) * A.y_stride + sidx);
             pending |= (lane < cnt) & IsSentinel(vx[q]);
           }
         }
         if (__ballot(pending) == 0) {
-          FT_COUNT(14, spin);
+          T.Count(14, spin);
           break;
         }
         if (spin >= kFusedSpinLimit) {
@@ -903,7 +932,7 @@ __device__ __forceinline__ void FusedSupernode(const FusedTreeArgs& A, const int
       }
     }
   }
-  FT_STAMP(5);  // the separator's solution is in
+  T.Stamp(5);  // the separator's solution is in
   double accx[NRHS > 1 ? NRHS - 1 : 1];
   accx[0] = 0.0;
   double acc = ub;
@@ -947,13 +976,13 @@ __device__ __forceinline__ void FusedSupernode(const FusedTreeArgs& A, const int
       for (int qq = 0; qq < QN; qq++) acc = fma(-Mb[qq], yv[qq], acc);
     }
   }
-  if (active) StoreAgent(ysG + R.start + lane, acc);
+  if (active) StoreAgent(Q.ysG + R.start + lane, acc);
   if constexpr (NRHS > 1) {
 #pragma unroll
     for (int q = 0; q < NRHS - 1; q++)
-      if (active) StoreAgent(ysT + (int64_t)(1 + q) * A.y_stride + R.start + lane, accx[q]);
+      if (active) StoreAgent(Q.ysT + (int64_t)(1 + q) * A.y_stride + R.start + lane, accx[q]);
   }
-  FT_STAMP(6);
+  T.Stamp(6);
   if constexpr (ROWRHS) {
     // a pivot that was not positive (here or in a descendant) has left NaNs in everything behind it: the test of
     // the factorization, two instructions per pivot inside the elimination, is one comparison out here (behind
@@ -970,14 +999,14 @@ __device__ __forceinline__ void FusedSupernode(const FusedTreeArgs& A, const int
       A.y3[A.y_stride + R.start + lane] = accx[0];
       A.y3[2 * A.y_stride + R.start + lane] = accx[1];
       A.y[R.start + lane] = accx[0] - acc;
-      StoreAgent(ysTO + A.y_stride + R.start + lane, SentinelValue());
-      StoreAgent(ysTO + 2 * A.y_stride + R.start + lane, SentinelValue());
+      StoreAgent(Q.ysTO + A.y_stride + R.start + lane, SentinelValue());
+      StoreAgent(Q.ysTO + 2 * A.y_stride + R.start + lane, SentinelValue());
     } else {
       A.y[R.start + lane] = acc;
     }
     A.AW[R.start + lane] = awv;
     A.AQc[R.start + lane] = aqv;
-    StoreAgent(ysO + R.start + lane, SentinelValue());
+    StoreAgent(Q.ysO + R.start + lane, SentinelValue());
   }
   if (NSMAX <= 32 && cnt == 0) {
 #pragma unroll
@@ -986,12 +1015,14 @@ __device__ __forceinline__ void FusedSupernode(const FusedTreeArgs& A, const int
   }
   if constexpr (SMAX > 0) {
     if (s > 0) {
+      // (FusedRearm's loop, written out: through the helper the five tree_fused<.., 32, 16, 2> instances, which are at
+      // their register limit, come out with another allocation -- CHANGELOG, "tree_fused: shared hand-off helpers")
 #pragma unroll
       for (int r = 0; r < PR; r++)
-        if (lane + 64 * r < nv) StoreAgent((NRHS > 1 && pdt[r] ? handTO : handO) + pd[r], SentinelValue());
+        if (lane + 64 * r < nv) StoreAgent((NRHS > 1 && pdt[r] ? Q.handTO : Q.handO) + pd[r], SentinelValue());
     }
   }
-  FT_STAMP_FLUSH(f(31));
+  T.Flush(f(31));
 }
 
 // The solve-only sweep on a stored factor (mu selection, Newton direction after it, line search,
@@ -1019,11 +1050,7 @@ __device__ __forceinline__ void FusedSolveSupernode(const FusedTreeArgs& A, cons
   const unsigned o0 = is_row ? (unsigned)lane : (is_sep ? rel + (unsigned)(sc * ns) : 0u);
   const unsigned st = is_row ? (unsigned)ns : 1u;
   const int lim = is_row ? lane : (is_sep ? ns : 0);  // strictly lower part of a row; a whole off column
-  const int gen = A.gen;
-  double* handG = A.hand + (int64_t)gen * A.hand_stride;
-  double* handO = A.hand + (int64_t)(gen ^ 1) * A.hand_stride;
-  double* ysG = A.ysig + (int64_t)gen * A.ysig_stride;
-  double* ysO = A.ysig + (int64_t)(gen ^ 1) * A.ysig_stride;
+  const FusedSlots Q = FusedSlotSets(A);
   const int pub_beg = __builtin_amdgcn_readlane(w, 23);
   const int npairs = s * (s + 1) / 2, nv = npairs + s;
   const int cnt = R.bs_end - R.bs_beg;
@@ -1063,7 +1090,7 @@ __device__ __forceinline__ void FusedSolveSupernode(const FusedTreeArgs& A, cons
   if constexpr (PHASE != 2) b = is_row ? b : 0.0;
   if (PHASE != 2 && R.mf > 0) {
     // (two rounds of loads in flight, every load unconditional: see the factor sweep)
-    const double* srcb = handG + A.updb_base + R.fbase + (is_row ? lane : 0) * R.mf;
+    const double* srcb = Q.handG + A.updb_base + R.fbase + (is_row ? lane : 0) * R.mf;
     for (int sb0 = 0; sb0 < R.mf; sb0 += MFMAX) {
       const int fleft = R.mf - sb0;
       double pb[MFMAX], qb[MFMAX];
@@ -1109,7 +1136,7 @@ __device__ __forceinline__ void FusedSolveSupernode(const FusedTreeArgs& A, cons
   }
   if constexpr (SMAX > 0) {
     if (s > 0) {
-      if (is_sep) StoreAgent(handG + pdb, dot);
+      if (is_sep) StoreAgent(Q.handG + pdb, dot);
     }
   }
   }  // PHASE != 2
@@ -1121,7 +1148,7 @@ __device__ __forceinline__ void FusedSolveSupernode(const FusedTreeArgs& A, cons
   if constexpr (QN > 0) {
     if (cnt > 0) {
       const int sepw = __builtin_amdgcn_ds_bpermute(4 * (24 + (lane < 8 ? lane : 0)), w);
-      const double* src = ysG + (lane < cnt ? (sepw & 0x3ffffff) : (R.sep[0] & 0x3ffffff));
+      const double* src = Q.ysG + (lane < cnt ? (sepw & 0x3ffffff) : (R.sep[0] & 0x3ffffff));
       double v;
       for (int spin = 0;; spin++) {
         v = LoadAgent(src);
@@ -1151,22 +1178,19 @@ __device__ __forceinline__ void FusedSolveSupernode(const FusedTreeArgs& A, cons
     acc = fma(-col[k], ReadLane(acc, k), acc);  // col[k] is zero for lanes >= k
   }
   if (active) {
-    StoreAgent(ysG + R.start + lane, acc);
+    StoreAgent(Q.ysG + R.start + lane, acc);
     A.y[R.start + lane] = acc;
-    StoreAgent(ysO + R.start + lane, SentinelValue());
+    StoreAgent(Q.ysO + R.start + lane, SentinelValue());
   }
   }  // PHASE != 1
   // re-arm the other set: ALL of this supernode's slots, the Schur-update ones too (a factor sweep
   // may be the next run)
   if constexpr (SMAX > 0 && PHASE != 2) {
-    if (s > 0) {
-#pragma unroll
-      for (int r = 0; r < PR; r++) {
+    if (s > 0)
+      FusedRearm<PR>(nv, [&](int r) {
         const int t = lane + 64 * r;
-        const int d = A.pub[pub_beg + (t < nv ? t : 0)];
-        if (t < nv) StoreAgent(handO + d, SentinelValue());
-      }
-    }
+        return Q.handO + A.pub[pub_beg + (t < nv ? t : 0)];
+      });
   }
 }
 
@@ -1196,6 +1220,12 @@ __device__ __forceinline__ void FusedScalars(const FusedTreeArgs& A) {
 // the pair: no supernode it sends to <NB, SB> fits <NA, SA>; for the frames of RegisterShape this is its choice).
 template <int NA, int SA>
 __device__ __forceinline__ bool FitsFrame(int ns, int s) { return ns <= NA && s <= SA; }
+template <int NA, int SA, int NB, int SB>
+__device__ __forceinline__ bool InFirstFrame(const int w) {
+  const int ns = __builtin_amdgcn_readlane(w, 1), s = __builtin_amdgcn_readlane(w, 2);
+  if (NA == NB && SA == SB) return true;
+  return FitsFrame<NA, SA>(ns, s);
+}
 
 // MODE 0: the whole sweep (assembly + factor + solve); 1: its upward half only (two launches: trees
 // too large to be resident at once); 2: the whole sweep with three right-hand sides (kFusedTriple)
@@ -1213,14 +1243,10 @@ __global__ void __launch_bounds__(64, 2) tree_fused(FusedTreeArgs A) {
     // (the image is asked for in the same trip as the record, before the record says which frame it is for)
     using Img = FusedImgOf<NA, SA, NB, SB, NRHS>;
     const typename Img::type I = Img::Load(A, pos);
-    const int ns = __builtin_amdgcn_readlane(w, 1), s = __builtin_amdgcn_readlane(w, 2);
-    if (NA == NB && SA == SB) {
+    if (InFirstFrame<NA, SA, NB, SB>(w))
       FusedSupernode<NA, SA, MODE == 1, false, NRHS>(A, w, lds, I);
-    } else if (FitsFrame<NA, SA>(ns, s)) {
-      FusedSupernode<NA, SA, MODE == 1, false, NRHS>(A, w, lds, I);
-    } else {
+    else
       FusedSupernode<NB, SB, MODE == 1, false, NRHS>(A, w, lds, I);
-    }
   } else {
     // (the wide frames: one supernode of 33 .. 64 columns, load phase computed from the record)
     static_assert(NA == NB && SA == SB, "the wide instances are single-frame");
@@ -1234,8 +1260,7 @@ __device__ __forceinline__ double WaitValue(const FusedTreeArgs& A, const double
   double v = LoadAgent(p);
   for (int spin = 0; IsSentinel(v); spin++) {
     if (spin >= kFusedSpinLimit) {
-      atomicExch(A.fail + 1, A.tag);
-      __hip_atomic_store(A.host_flag, 1.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      ReportTimeout(A, /*every_lane=*/true);
       break;
     }
     __builtin_amdgcn_s_sleep(1);
@@ -1250,7 +1275,7 @@ __device__ __forceinline__ double WaitValue(const FusedTreeArgs& A, const double
 // in slot order, then subtracted); per top variable the partial AW / AQc and the sum of the
 // published forward values.
 __device__ __forceinline__ void ShardPackItem(const FusedTreeArgs& A, int64_t item) {
-  const double* handG = A.hand + (int64_t)A.gen * A.hand_stride;
+  const FusedSlots Q = FusedSlotSets(A);
   if (item < A.n_xs) {
     const GatherRec g = A.xg[item];
     double s = 0;
@@ -1262,7 +1287,7 @@ __device__ __forceinline__ void ShardPackItem(const FusedTreeArgs& A, int64_t it
     const int t = A.xs_pt[item];
     if (t >= 0) {
       double u = 0;
-      for (int q = A.pt_ptr[t]; q < A.pt_ptr[t + 1]; q++) u += WaitValue(A, handG + A.pt_src[q]);
+      for (int q = A.pt_ptr[t]; q < A.pt_ptr[t + 1]; q++) u += WaitValue(A, Q.handG + A.pt_src[q]);
       s -= u;
     }
     A.x[item] = s;
@@ -1279,7 +1304,7 @@ __device__ __forceinline__ void ShardPackItem(const FusedTreeArgs& A, int64_t it
       aq += A.AQcc[A.rs_src[k]];
     }
     double fw = 0;
-    for (int q = A.pf_ptr[j]; q < A.pf_ptr[j + 1]; q++) fw += WaitValue(A, handG + A.updb_base + A.pf_src[q]);
+    for (int q = A.pf_ptr[j]; q < A.pf_ptr[j + 1]; q++) fw += WaitValue(A, Q.handG + A.updb_base + A.pf_src[q]);
     A.x[A.n_xs + j] = aw;
     A.x[A.n_xs + A.n_xv + j] = aq;
     A.x[A.n_xs + 2 * (int64_t)A.n_xv + j] = fw;
@@ -1300,10 +1325,7 @@ __device__ __forceinline__ void ShardPackTail(const FusedTreeArgs& A) {
       const unsigned long long have = __hip_atomic_load(A.done + 16 * lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if (__ballot(have < want) == 0) break;
       if (spin >= kFusedSpinLimit) {
-        if (lane == 0) {
-          atomicExch(A.fail + 1, A.tag);
-          __hip_atomic_store(A.host_flag, 1.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
+        ReportTimeout(A);
         break;
       }
       __builtin_amdgcn_s_sleep(2);
@@ -1335,14 +1357,10 @@ __global__ void __launch_bounds__(64) tree_fused_shard_up(FusedTreeArgs A) {
     const int w = A.rec[(size_t)pos * kFusedRecWords + (threadIdx.x & 63)];
     using Img = FusedImgOf<NA, SA, NB, SB, 1>;
     const typename Img::type I = Img::Load(A, pos);
-    const int ns = __builtin_amdgcn_readlane(w, 1), s = __builtin_amdgcn_readlane(w, 2);
-    if (NA == NB && SA == SB) {
+    if (InFirstFrame<NA, SA, NB, SB>(w))
       FusedSupernode<NA, SA, true>(A, w, lds, I);
-    } else if (FitsFrame<NA, SA>(ns, s)) {
-      FusedSupernode<NA, SA, true>(A, w, lds, I);
-    } else {
+    else
       FusedSupernode<NB, SB, true>(A, w, lds, I);
-    }
     // Behind this wavefront's failure report, if any (an atomic too: the wait orders the two).  64
     // counters on lines of their own, position modulo 64: one counter would serialise its adders at
     // ~12 ns each (2300 supernodes of a rank of config 5: 28 us behind the last elimination), and an
@@ -1380,8 +1398,7 @@ __global__ void __launch_bounds__(64) tree_fused_shard_top(FusedTreeArgs A) {
   }
   const int pos = b < ntop ? A.count_up + b : A.count - 1 - b;
   const int w = A.rec[(size_t)pos * kFusedRecWords + (threadIdx.x & 63)];
-  const int ns = __builtin_amdgcn_readlane(w, 1), s = __builtin_amdgcn_readlane(w, 2);
-  const bool isA = (NA == NB && SA == SB) || FitsFrame<NA, SA>(ns, s);
+  const bool isA = InFirstFrame<NA, SA, NB, SB>(w);
   if (b < ntop) {
     if (isA)
       FusedSupernode<NA, SA, false, true>(A, w, lds);
@@ -1401,14 +1418,10 @@ template <int NA, int SA, int NB, int SB, int PHASE>
 __global__ void __launch_bounds__(64) tree_fused_solve(FusedTreeArgs A) {
   const int pos = PHASE == 2 ? A.count - 1 - (int)blockIdx.x : (int)blockIdx.x;
   const int w = A.rec[(size_t)pos * kFusedRecWords + (threadIdx.x & 63)];
-  const int ns = __builtin_amdgcn_readlane(w, 1), s = __builtin_amdgcn_readlane(w, 2);
-  if (NA == NB && SA == SB) {
+  if (InFirstFrame<NA, SA, NB, SB>(w))
     FusedSolveSupernode<NA, SA, PHASE>(A, w);
-  } else if (FitsFrame<NA, SA>(ns, s)) {
-    FusedSolveSupernode<NA, SA, PHASE>(A, w);
-  } else {
+  else
     FusedSolveSupernode<NB, SB, PHASE>(A, w);
-  }
 }
 
 namespace {
