@@ -734,23 +734,6 @@ __global__ void __launch_bounds__(256, 2) gemm_f64_dma128(GemmArgs g) {
 
 namespace {
 
-bool Aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-// The DMA path fetches 16-byte chunks (two doubles): every chunk must be aligned and inside its
-// matrix.  m-major operands: even leading dimension (a pair of rows of one column).  k-major
-// operands: even leading dimension and even K (a pair of k of one row).
-bool DmaEligible(const GemmArgs& g, bool ta, bool tb) {
-  if (getenv("CXK_GEMM_GENERAL")) return false;  // comparison runs
-  if (g.M < 2 || g.N < 2 || g.K < 2) return false;
-  if ((g.lda & 1) || (g.ldb & 1) || (g.sA1 & 1) || (g.sA2 & 1) || (g.sB1 & 1) || (g.sB2 & 1)) return false;
-  if (!Aligned16(g.A) || !Aligned16(g.B)) return false;
-  if ((ta || !tb) && (g.K & 1)) return false;
-  // byte offsets inside a tile are kept in 32 bits
-  if ((ta ? 64 * g.lda : (int64_t)g.K * g.lda) * 8 >= (1ll << 31)) return false;
-  if ((!tb ? 64 * g.ldb : (int64_t)g.K * g.ldb) * 8 >= (1ll << 31)) return false;
-  return true;
-}
-
 template <bool TA, bool TB, int BK>
 hipError_t LaunchDmaBK(const GemmArgs& g, dim3 grid, hipStream_t stream) {
   constexpr size_t lds = sizeof(double) * (4 * 64 * BK > 64 * 65 ? 4 * 64 * BK : 64 * 65);
@@ -765,7 +748,7 @@ hipError_t LaunchDmaBK(const GemmArgs& g, dim3 grid, hipStream_t stream) {
 }
 
 template <bool TA, bool TB, int NJ>
-hipError_t LaunchDma128T(const GemmArgs& g, int batch, hipStream_t stream) {
+hipError_t LaunchDma128T(const GemmArgs& g, dim3 grid, hipStream_t stream) {
   constexpr size_t lds = sizeof(double) * 2 * (2 + NJ / 2) * 64 * 16;
   static PerDeviceOnce once;
   const hipError_t ec = once.run([] {
@@ -773,90 +756,105 @@ hipError_t LaunchDma128T(const GemmArgs& g, int batch, hipStream_t stream) {
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   });
   if (ec != hipSuccess) return ec;
-  const dim3 grid(((g.M + 127) / 128) * ((g.N + 32 * NJ - 1) / (32 * NJ)), g.splits > 1 ? g.splits : 1, batch);
   gemm_f64_dma128<TA, TB, NJ><<<grid, 256, lds, stream>>>(g);
   return hipGetLastError();
 }
 
-template <bool TA, bool TB>
-hipError_t LaunchDma128(const GemmArgs& g, int nj, int batch, hipStream_t stream) {
-  return nj == 4 ? LaunchDma128T<TA, TB, 4>(g, batch, stream) : LaunchDma128T<TA, TB, 2>(g, batch, stream);
-}
+}  // namespace
 
-// Which tile a DMA-eligible product takes: 0 = the 64 x 64 kernel, 4 = 128 x 128, 2 = 128 x 64.  The big
-// tiles need enough workgroups to fill the chip (two per CU are resident) and more than one 64-row tile
-// of rows to be worth it; CXK_GEMM_TILE=64 | 128 | 12864 forces the choice (comparison runs).
-int ChooseTile(const GemmArgs& g, int batch) {
+// What this process is set to (cxk_host::GemmModes): CXK_GEMM_GENERAL is read at every call, CXK_GEMM_TILE and the
+// CU count once, at the first product that is launched (before the route moved into ChooseGemm the CU count was asked
+// for at the first call that reached ChooseTile's workgroup clause).
+cxk_host::GemmModes GemmProcessModes() {
   static const int forced = [] {
     const char* e = getenv("CXK_GEMM_TILE");
     return e ? atoi(e) : 0;
   }();
-  if (forced == 64) return 0;
-  if (g.M <= 32 && g.N <= 32) return 0;  // (the Gram products share one quadrant: gemm_f64_dma)
-  if (g.beta != 0.0 && g.splits <= 1) return 0;  // (accumulating calls: the 64 x 64 kernel fetches the old values before its K loop)
-  if (forced == 128) return 4;
-  if (forced == 12864) return 2;
-  if (g.M <= 64) return 0;
   static const int cus = [] {
     int dev = 0, n = 256;
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
     return n > 0 ? n : 256;
   }();
-  // (a ragged last tile of 1 .. 6 sub-tiles a side leaves the four workgroups of an order-200 matrix with
-  // shares of 16 / 12 / 12 / 9 MFMA tiles: measured 0.377 against 0.391 of the MFMA peak for the 64 x 64 tiles)
-  auto clean = [](int n, int t) { return n % t == 0 || n % t > t - 16; };
-  if (!clean(g.M, 128)) return 0;
-  const int64_t reps = (int64_t)(g.splits > 1 ? g.splits : 1) * batch * ((g.M + 127) / 128);
-  if (g.N > 64 && clean(g.N, 128) && reps * ((g.N + 127) / 128) >= cus) return 4;
-  if (clean(g.N, 64) && reps * ((g.N + 63) / 64) >= 2 * cus) return 2;
-  return 0;
+  cxk_host::GemmModes m;
+  m.cus = cus;
+  m.forced_tile = forced;
+  m.force_general = getenv("CXK_GEMM_GENERAL") != nullptr;  // comparison runs
+  return m;
 }
 
+namespace {
+
 template <bool TA, bool TB>
-hipError_t LaunchDma(const GemmArgs& g, dim3 grid, hipStream_t stream) {
-  const int ksteps = (g.K + kGemmBK - 1) / kGemmBK;
-  const int per_split = (ksteps + std::max(g.splits, 1) - 1) / std::max(g.splits, 1) * kGemmBK;
-  if (per_split >= 512) return LaunchDmaBK<TA, TB, 32>(g, grid, stream);
-  return LaunchDmaBK<TA, TB, 16>(g, grid, stream);
+hipError_t LaunchRoute(const GemmArgs& g, cxk_host::GemmLaunch l, int batch, hipStream_t stream) {
+  const dim3 grid(l.grid_x, g.splits > 1 ? g.splits : 1, batch);
+  switch (l.route) {
+    case cxk_host::GemmRoute::kGeneral:
+      gemm_f64_mfma<TA, TB><<<grid, 256, 0, stream>>>(g);
+      return hipGetLastError();
+    case cxk_host::GemmRoute::kDma16: return LaunchDmaBK<TA, TB, 16>(g, grid, stream);
+    case cxk_host::GemmRoute::kDma32: return LaunchDmaBK<TA, TB, 32>(g, grid, stream);
+    case cxk_host::GemmRoute::kDma128x128: return LaunchDma128T<TA, TB, 4>(g, grid, stream);
+    case cxk_host::GemmRoute::kDma128x64: return LaunchDma128T<TA, TB, 2>(g, grid, stream);
+  }
+  return hipErrorInvalidValue;
 }
 
 }  // namespace
 
+cxk_host::GemmShape GemmShapeOf(const GemmArgs& g, bool ta, bool tb, int batch) {
+  cxk_host::GemmShape s;
+  s.M = g.M;
+  s.N = g.N;
+  s.K = g.K;
+  s.lda = g.lda;
+  s.ldb = g.ldb;
+  s.ldc = g.ldc;
+  s.sA1 = g.sA1;
+  s.sA2 = g.sA2;
+  s.sB1 = g.sB1;
+  s.sB2 = g.sB2;
+  s.a_addr = (uint64_t) reinterpret_cast<uintptr_t>(g.A);
+  s.b_addr = (uint64_t) reinterpret_cast<uintptr_t>(g.B);
+  s.ta = ta;
+  s.tb = tb;
+  s.accumulate = g.beta != 0.0;
+  s.lower_only = g.lower_only != 0;
+  s.splits = g.splits;
+  s.has_ct = g.Ct != nullptr;
+  s.batch = batch;
+  return s;
+}
+
+hipError_t LaunchGemmWith(const GemmArgs& g, bool ta, bool tb, int batch, hipStream_t stream, const cxk_host::GemmModes& modes,
+                          cxk_host::GemmRoute* route) {
+  if (g.M <= 0 || g.N <= 0 || batch <= 0) return hipSuccess;
+  // The kernels disagree on what a transposed copy of a lower-only product holds (tiles above the diagonal are
+  // skipped, the tiles that run copy out entries above it), and no caller asks for one: refused.
+  if (g.Ct && g.lower_only) return hipErrorInvalidValue;
+  const cxk_host::GemmLaunch l = cxk_host::ChooseGemm(GemmShapeOf(g, ta, tb, batch), modes);
+  if (route) *route = l.route;
+  if (!ta && !tb) return LaunchRoute<false, false>(g, l, batch, stream);
+  if (ta && !tb) return LaunchRoute<true, false>(g, l, batch, stream);
+  if (!ta && tb) return LaunchRoute<false, true>(g, l, batch, stream);
+  return LaunchRoute<true, true>(g, l, batch, stream);
+}
+
 hipError_t LaunchGemm(const GemmArgs& g, bool ta, bool tb, int batch, hipStream_t stream) {
   if (g.M <= 0 || g.N <= 0 || batch <= 0) return hipSuccess;
-  const int tiles = ((g.M + kGemmBM - 1) / kGemmBM) * ((g.N + kGemmBN - 1) / kGemmBN);
-  dim3 grid(tiles, g.splits > 1 ? g.splits : 1, batch);
-  if (DmaEligible(g, ta, tb)) {
-    if (const int nj = ChooseTile(g, batch)) {
-      if (!ta && !tb) return LaunchDma128<false, false>(g, nj, batch, stream);
-      if (ta && !tb) return LaunchDma128<true, false>(g, nj, batch, stream);
-      if (!ta && tb) return LaunchDma128<false, true>(g, nj, batch, stream);
-      return LaunchDma128<true, true>(g, nj, batch, stream);
-    }
-    const int tiles_m = (g.M + kGemmBM - 1) / kGemmBM;
-    if (g.lower_only && g.M == g.N) grid.x = tiles_m * (tiles_m + 1) / 2;  // lower tiles only
-    if (!ta && !tb) return LaunchDma<false, false>(g, grid, stream);
-    if (ta && !tb) return LaunchDma<true, false>(g, grid, stream);
-    if (!ta && tb) return LaunchDma<false, true>(g, grid, stream);
-    return LaunchDma<true, true>(g, grid, stream);
-  }
-  if (!ta && !tb)
-    gemm_f64_mfma<false, false><<<grid, 256, 0, stream>>>(g);
-  else if (ta && !tb)
-    gemm_f64_mfma<true, false><<<grid, 256, 0, stream>>>(g);
-  else if (!ta && tb)
-    gemm_f64_mfma<false, true><<<grid, 256, 0, stream>>>(g);
-  else
-    gemm_f64_mfma<true, true><<<grid, 256, 0, stream>>>(g);
-  return hipGetLastError();
+  return LaunchGemmWith(g, ta, tb, batch, stream, GemmProcessModes(), nullptr);
 }
 
 hipError_t LaunchGemmSplitK(GemmArgs g, bool ta, bool tb, int batch, double* part, hipStream_t stream) {
-  if (g.splits <= 1) return LaunchGemm(g, ta, tb, batch, stream);
+  return LaunchGemmSplitKWith(g, ta, tb, batch, part, stream, GemmProcessModes(), nullptr);
+}
+
+hipError_t LaunchGemmSplitKWith(GemmArgs g, bool ta, bool tb, int batch, double* part, hipStream_t stream,
+                                const cxk_host::GemmModes& modes, cxk_host::GemmRoute* route) {
+  if (g.splits <= 1) return LaunchGemmWith(g, ta, tb, batch, stream, modes, route);
+  if (g.Ct) return hipErrorInvalidValue;  // (the ordered reduction writes no transposed copy)
   GemmArgs p = g;
   p.C = part;
-  p.Ct = nullptr;
-  hipError_t e = LaunchGemm(p, ta, tb, batch, stream);
+  hipError_t e = LaunchGemmWith(p, ta, tb, batch, stream, modes, route);
   if (e != hipSuccess) return e;
   const int64_t total = (int64_t)g.M * g.N;
   dim3 grid((unsigned)std::min<int64_t>((total + 3) / 4, 4096), 1, batch);

@@ -24,6 +24,8 @@
 
 #include <cstdint>
 
+#include "gemm_route.h"
+
 namespace cxk {
 
 struct GemmArgs {
@@ -53,5 +55,15 @@ hipError_t LaunchGemm(const GemmArgs& g, bool ta, bool tb, int batch, hipStream_
 // Split-K GEMM: partials into `part` (same batch strides as C, split stride g.sCs), then the
 // ordered reduction into C.
 hipError_t LaunchGemmSplitK(GemmArgs g, bool ta, bool tb, int batch, double* part, hipStream_t stream);
+// A transposed copy-out (g.Ct) is refused (hipErrorInvalidValue) with lower_only, and by LaunchGemmSplitK with splits > 1.
+//
+// The same two under modes the caller states instead of the process's (CXK_GEMM_TILE, CXK_GEMM_GENERAL, the CU count),
+// reporting the route taken (gemm_route.h): cxk_gemm_f64_layout reaches every kernel in one process through them.
+cxk_host::GemmShape GemmShapeOf(const GemmArgs& g, bool ta, bool tb, int batch);
+hipError_t LaunchGemmWith(const GemmArgs& g, bool ta, bool tb, int batch, hipStream_t stream, const cxk_host::GemmModes& modes,
+                          cxk_host::GemmRoute* route);
+hipError_t LaunchGemmSplitKWith(GemmArgs g, bool ta, bool tb, int batch, double* part, hipStream_t stream,
+                                const cxk_host::GemmModes& modes, cxk_host::GemmRoute* route);
+cxk_host::GemmModes GemmProcessModes();
 
 }  // namespace cxk

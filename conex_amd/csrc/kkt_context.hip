@@ -1493,6 +1493,120 @@ int cxk_gemm_f64(int device, int ta, int tb, int M, int N, int K, int batch, con
   return CXK_SUCCESS;
 }
 
+int cxk_gemm_f64_layout(int device, double* arena, long long arena_len, const long long* f, double alpha, double beta,
+                        int* route) {
+  if (!arena || !f || arena_len <= 0) return CXK_FAILURE;
+  enum { kM, kN, kK, kTa, kTb, kBatch, kInner, kLower, kSplits, kOrdered, kTile, kGeneral, kOffA, kLda, kSA1, kSA2, kOffB, kLdb,
+         kSB1, kSB2, kOffC, kLdc, kSC1, kSC2, kOffCt, kLdct, kST1, kST2, kCtb, kSTb, kOffPart, kSCs };
+  const long long M = f[kM], N = f[kN], K = f[kK], batch = f[kBatch], inner = f[kInner], splits = f[kSplits];
+  const bool ta = f[kTa] != 0, tb = f[kTb] != 0, ordered = f[kOrdered] != 0;
+  const long long kMaxDim = 1ll << 24;  // (keeps every product below in 64 bits)
+  if (M <= 0 || N <= 0 || K <= 0 || batch <= 0 || inner <= 0 || splits <= 0) return CXK_FAILURE;
+  if (M > kMaxDim || N > kMaxDim || K > kMaxDim || batch > kMaxDim || splits > kMaxDim || inner > kMaxDim) return CXK_FAILURE;
+  if (f[kTile] != 0 && f[kTile] != 64 && f[kTile] != 128 && f[kTile] != 12864) return CXK_FAILURE;
+  for (int i = kOffA; i <= kSCs; i++) {
+    const bool optional = i == kOffCt || i == kOffPart;
+    if (f[i] > arena_len || f[i] < (optional ? -1 : 0)) return CXK_FAILURE;
+  }
+  const bool has_ct = f[kOffCt] >= 0, split = splits > 1;
+  if (split && f[kOffPart] < 0) return CXK_FAILURE;
+  if (f[kCtb] < 0 || (has_ct && f[kLdct] < 1)) return CXK_FAILURE;
+  // Footprints, in 64-bit host arithmetic: of every operand and of C for every batch member (a matrix of `rows` rows
+  // in columns `ld` apart ends (columns - 1) ld + rows behind its first element, so that a block of a larger matrix
+  // may end where that matrix ends; an operand's rows count up to the next even number, the 16-byte chunks of the
+  // LDS-DMA kernels), the partials of every split, and the image of C in Ct.  Every offset, stride and leading
+  // dimension is in [0, arena_len] and every count at most 2^24, so no term below leaves 64 bits.
+  auto extent = [](long long rows, long long ld, long long cols) { return (cols - 1) * ld + std::min(ld, rows); };
+  auto inside = [&](long long lo, long long len) { return lo >= 0 && len >= 0 && lo <= arena_len && len <= arena_len - lo; };
+  const long long rows_a = ta ? K : M, cols_a = ta ? M : K, rows_b = tb ? N : K, cols_b = tb ? K : N;
+  if (f[kLda] < rows_a || f[kLdb] < rows_b || f[kLdc] < M) return CXK_FAILURE;
+  if (f[kLda] > arena_len / cols_a || f[kLdb] > arena_len / cols_b || f[kLdc] > arena_len / N) return CXK_FAILURE;
+  // Strides are not negative, so the footprints reach furthest at the first member, at the last one, and (inner > 1)
+  // at the last member of the last full group of `inner`; the last split reaches furthest among the splits.
+  const long long last = batch - 1, ends[3] = {0, last, (last / inner) * inner - 1};
+  for (int e = 0; e < 3; e++) {
+    const long long z = ends[e];
+    if (z < 0) continue;
+    const long long b1 = z / inner, b2 = z % inner;
+    if (b1 > 0 && (f[kSA1] > arena_len / b1 || f[kSB1] > arena_len / b1 || f[kSC1] > arena_len / b1 || f[kST1] > arena_len / b1))
+      return CXK_FAILURE;
+    if (b2 > 0 && (f[kSA2] > arena_len / b2 || f[kSB2] > arena_len / b2 || f[kSC2] > arena_len / b2 || f[kST2] > arena_len / b2))
+      return CXK_FAILURE;
+    if (!inside(f[kOffA] + b1 * f[kSA1] + b2 * f[kSA2], extent(rows_a + (rows_a & 1), f[kLda], cols_a))) return CXK_FAILURE;
+    if (!inside(f[kOffB] + b1 * f[kSB1] + b2 * f[kSB2], extent(rows_b + (rows_b & 1), f[kLdb], cols_b))) return CXK_FAILURE;
+    const long long c_rel = b1 * f[kSC1] + b2 * f[kSC2];
+    if (!split || ordered) {
+      if (!inside(f[kOffC] + c_rel, extent(M, f[kLdc], N))) return CXK_FAILURE;
+    }
+    if (split) {
+      if (f[kSCs] > arena_len / splits) return CXK_FAILURE;
+      for (long long sp = 0; sp < splits; sp += std::max(1ll, splits - 1))
+        if (!inside(f[kOffPart] + c_rel + sp * f[kSCs], extent(M, f[kLdc], N))) return CXK_FAILURE;
+    }
+    if (has_ct) {
+      // Ct[n + m ldct + (n / ctb) sTb]: largest at n = N - 1, m = M - 1 (strides are not negative)
+      const long long blocks = f[kCtb] > 0 ? (N - 1) / f[kCtb] : 0;
+      if (f[kLdct] > arena_len / M || (blocks > 0 && f[kSTb] > arena_len / blocks)) return CXK_FAILURE;
+      if (!inside(f[kOffCt] + b1 * f[kST1] + b2 * f[kST2], (N - 1) + (M - 1) * f[kLdct] + blocks * f[kSTb] + 1))
+        return CXK_FAILURE;
+    }
+  }
+  cxk_context scratch_ctx;  // carries the error string for CXK_TRY
+  cxk_context* ctx = &scratch_ctx;
+  DeviceGuard guard(device);
+  DevBuf<double> dev;
+  CXK_TRY(dev.alloc((size_t)arena_len));
+  CXK_TRY(hipMemcpy(dev.p, arena, sizeof(double) * (size_t)arena_len, hipMemcpyHostToDevice));
+  GemmArgs g{};
+  g.M = (int)M;
+  g.N = (int)N;
+  g.K = (int)K;
+  g.A = dev.p + f[kOffA];
+  g.lda = f[kLda];
+  g.sA1 = f[kSA1];
+  g.sA2 = f[kSA2];
+  g.B = dev.p + f[kOffB];
+  g.ldb = f[kLdb];
+  g.sB1 = f[kSB1];
+  g.sB2 = f[kSB2];
+  g.C = dev.p + ((split && !ordered) ? f[kOffPart] : f[kOffC]);  // raw partials: C = part, as LmiLargeSchur calls it
+  g.ldc = f[kLdc];
+  g.sC1 = f[kSC1];
+  g.sC2 = f[kSC2];
+  g.Ct = has_ct ? dev.p + f[kOffCt] : nullptr;
+  g.ldct = f[kLdct];
+  g.sT1 = f[kST1];
+  g.sT2 = f[kST2];
+  g.ctb = (int)f[kCtb];
+  g.sTb = f[kSTb];
+  g.inner = (int)inner;
+  g.alpha = alpha;
+  g.beta = beta;
+  g.lower_only = f[kLower] != 0;
+  g.splits = (int)splits;
+  g.sCs = f[kSCs];
+  cxk_host::GemmModes modes = GemmProcessModes();
+  if (f[kTile]) modes.forced_tile = (int)f[kTile];
+  if (f[kGeneral]) modes.force_general = true;
+  cxk_host::GemmRoute r = cxk_host::GemmRoute::kGeneral;
+  if (split && ordered)
+    CXK_TRY(LaunchGemmSplitKWith(g, ta, tb, (int)batch, dev.p + f[kOffPart], nullptr, modes, &r));
+  else
+    CXK_TRY(LaunchGemmWith(g, ta, tb, (int)batch, nullptr, modes, &r));
+  CXK_TRY(hipDeviceSynchronize());
+  CXK_TRY(hipMemcpy(arena, dev.p, sizeof(double) * (size_t)arena_len, hipMemcpyDeviceToHost));
+  if (route) {
+    switch (r) {
+      case cxk_host::GemmRoute::kGeneral: *route = CXK_GEMM_ROUTE_GENERAL; break;
+      case cxk_host::GemmRoute::kDma16: *route = CXK_GEMM_ROUTE_DMA16; break;
+      case cxk_host::GemmRoute::kDma32: *route = CXK_GEMM_ROUTE_DMA32; break;
+      case cxk_host::GemmRoute::kDma128x128: *route = CXK_GEMM_ROUTE_DMA128X128; break;
+      case cxk_host::GemmRoute::kDma128x64: *route = CXK_GEMM_ROUTE_DMA128X64; break;
+    }
+  }
+  return CXK_SUCCESS;
+}
+
 int cxk_dense_top_columns(const cxk_context* ctx) {
   if (!ctx || !ctx->finalized) return -1;
   return ctx->top_dense.on ? ctx->top_dense.args.T : 0;

@@ -983,3 +983,36 @@ def gemm_f64(A, B, C=None, ta=False, tb=False, alpha=1.0, beta=0.0, lower_only=F
     if rc != 0:
         raise RuntimeError("cxk_gemm_f64 failed")
     return Cp.transpose(0, 2, 1).copy(), ms.value
+
+
+# cxk_gemm_f64_layout: the route enumerators and the order of the call's fields (include/conex_kkt_hip.h)
+GEMM_ROUTES = ("general", "dma16", "dma32", "dma128x128", "dma128x64")
+GEMM_LAYOUT_FIELDS = ("M", "N", "K", "ta", "tb", "batch", "inner", "lower_only", "splits", "ordered", "tile", "general",
+                      "offA", "lda", "sA1", "sA2", "offB", "ldb", "sB1", "sB2", "offC", "ldc", "sC1", "sC2",
+                      "offCt", "ldct", "sT1", "sT2", "ctb", "sTb", "offPart", "sCs")
+
+
+def gemm_f64_layout(arena, fields, alpha=1.0, beta=0.0, device=0):
+    """One product through cxk_gemm_f64_layout on operands that live inside `arena` (1-d float64) at the element
+    offsets, leading dimensions and strides `fields` states (a dict over GEMM_LAYOUT_FIELDS; offCt / offPart
+    default to -1 = none, everything else to 0, inner / splits / ordered to 1).  Returns (arena after the call, name
+    of the route the call ran on).  A layout that leaves the arena raises before anything is launched."""
+    import ctypes as C_
+    L = load_library()
+    arena = np.ascontiguousarray(arena, dtype=np.float64)
+    if arena.ndim != 1:
+        raise ValueError("arena must be one-dimensional")
+    unknown = set(fields) - set(GEMM_LAYOUT_FIELDS)
+    if unknown:
+        raise ValueError("unknown layout fields: %s" % sorted(unknown))
+    default = {"offCt": -1, "offPart": -1, "inner": 1, "splits": 1, "ordered": 1}
+    f = (C_.c_longlong * len(GEMM_LAYOUT_FIELDS))(*[int(fields.get(k, default.get(k, 0))) for k in GEMM_LAYOUT_FIELDS])
+    out = arena.copy()
+    route = C_.c_int(-1)
+    L.cxk_gemm_f64_layout.restype = C_.c_int
+    L.cxk_gemm_f64_layout.argtypes = [C_.c_int, C_.c_void_p, C_.c_longlong, C_.POINTER(C_.c_longlong), C_.c_double,
+                                      C_.c_double, C_.POINTER(C_.c_int)]
+    rc = L.cxk_gemm_f64_layout(device, out.ctypes.data, out.size, f, float(alpha), float(beta), C_.byref(route))
+    if rc != 0:
+        raise RuntimeError("cxk_gemm_f64_layout refused the layout or failed")
+    return out, GEMM_ROUTES[route.value]

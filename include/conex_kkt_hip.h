@@ -590,6 +590,29 @@ int cxk_gemm_f64(int device, int ta, int tb, int M, int N, int K, int batch, con
                  const double* B, double* C, double alpha, double beta, int lower_only, int splits,
                  int reps, double* avg_ms);
 
+/* The same product on the operand layouts the library's own call sites pass (test entry).  `arena` (arena_len
+ * doubles) is copied to ONE device allocation, the product runs once, and the whole arena is copied back.  f[32]
+ * describes the call, offsets in doubles into the arena (so operands may alias, interleave, or sit 8 bytes off
+ * alignment):
+ *    0 M   1 N   2 K   3 ta   4 tb   5 batch   6 inner   7 lower_only   8 splits
+ *    9 ordered: with splits > 1, 1 = partials then the ordered reduction into C, 0 = raw partials only (C unused)
+ *   10 tile override (64 | 128 | 12864, the meaning of CXK_GEMM_TILE; 0 = the process's)   11 general-kernel override
+ *   12 offset of A  13 lda  14 sA1  15 sA2     16 offset of B  17 ldb  18 sB1  19 sB2
+ *   20 offset of C  21 ldc  22 sC1  23 sC2     24 offset of Ct (-1: none)  25 ldct  26 sT1  27 sT2  28 ctb  29 sTb
+ *   30 offset of the split partials (-1: none)  31 sCs
+ * Batch member z uses strides (z / inner, z % inner); Ct[n + m ldct + (n / ctb) sTb] = alpha (A B)(m, n).
+ * A layout whose footprints (each operand and C for every batch member and split, from the first element to
+ * (columns - 1) ld + rows behind it, an operand's rows counted up to the next even number; the image of C in
+ * Ct) leave the arena, a negative stride, or a combination the launchers refuse (Ct with lower_only, Ct
+ * with the ordered reduction) returns CXK_FAILURE before any launch.  *route: the kernel the call ran on. */
+#define CXK_GEMM_ROUTE_GENERAL 0    /* gemm_f64_mfma */
+#define CXK_GEMM_ROUTE_DMA16 1      /* gemm_f64_dma<16> */
+#define CXK_GEMM_ROUTE_DMA32 2      /* gemm_f64_dma<32> */
+#define CXK_GEMM_ROUTE_DMA128X128 3 /* gemm_f64_dma128<4> */
+#define CXK_GEMM_ROUTE_DMA128X64 4  /* gemm_f64_dma128<2> */
+int cxk_gemm_f64_layout(int device, double* arena, long long arena_len, const long long* f, double alpha,
+                        double beta, int* route);
+
 /* Number of (owned) LMI / Hermitian constraints evaluated from their nonzeros instead of dense
  * matrices (kernels_lmi_sparse.hip.h).  The C-ABI fills matrix inequalities
  * entry by entry (CONEX_UpdateLinearOperator, hermitian_psd.cc:249-275), so their A_i are

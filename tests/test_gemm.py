@@ -31,6 +31,21 @@ def check(M, N, K, batch, ta, tb, alpha=1.0, beta=0.0, lower_only=False, splits=
     assert err <= 1e-13, err
 
 
+def route_of(M, N, K, batch, ta, tb, lower_only=False, splits=1):
+    """The kernel the library chooses for the packed call check() makes: the same shapes, leading dimensions, strides
+    and alignment through cxk_gemm_f64_layout with no override (the values do not matter: zeros)."""
+    na, nb, nc = M * K, K * N, M * N
+    up = lambda x: -(-x // 32) * 32          # 256-byte aligned regions, as the three buffers of cxk_gemm_f64 are
+    offB = up(na * batch)
+    offC = offB + up(nb * batch)
+    offP = offC + up(nc * batch)
+    f = dict(M=M, N=N, K=K, ta=int(ta), tb=int(tb), batch=batch, lower_only=int(lower_only), splits=splits, offA=0,
+             lda=K if ta else M, sA1=na, offB=offB, ldb=N if tb else K, sB1=nb, offC=offC, ldc=M, sC1=nc,
+             offPart=offP if splits > 1 else -1, sCs=nc * batch)
+    _, route = kkt.gemm_f64_layout(np.zeros(offP + (nc * batch * splits if splits > 1 else 0)), f)
+    return route
+
+
 @pytest.mark.parametrize("ta,tb", [(False, False), (True, False), (False, True), (True, True)])
 @pytest.mark.parametrize("shape", [(64, 64, 16), (1, 1, 1), (17, 33, 5), (200, 200, 200),
                                    (130, 70, 259), (51, 51, 1000)])
@@ -56,6 +71,9 @@ def test_gram_products_share_one_quadrant(shape, splits):
     M, N, K, lower = shape
     for batch in (1, 13):   # 13 workgroups: a grid that is not a multiple of the 8 XCDs
         check(M, N, K, batch, True, False, lower_only=lower, splits=splits, seed=K + batch)
+        # the 64 x 64 LDS-DMA kernel (the one with the shared quadrant), 32 k-values a stage from 512 per split on
+        per_split = -(-(-(-K // 16)) // splits) * 16
+        assert route_of(M, N, K, batch, True, False, lower_only=lower, splits=splits) == ("dma32" if per_split >= 512 else "dma16")
 
 
 @pytest.mark.parametrize("n", [64, 65, 200, 257])
@@ -85,6 +103,8 @@ def test_big_tile_kernel_on_the_shapes_it_is_chosen_for(shape, ta, tb):
     sides that fill their last tile, enough workgroups for the chip."""
     M, N, K, batch = shape
     check(M, N, K, batch, ta, tb, seed=M + N + K)
+    # ... and the library did choose it: 128 x 128 where N fills 128-wide tiles, 128 x 64 otherwise
+    assert route_of(M, N, K, batch, ta, tb) == ("dma128x128" if N in (128, 250) else "dma128x64")
 
 
 def test_big_tile_kernel_split_k_and_lower_only():
