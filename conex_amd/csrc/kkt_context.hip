@@ -1389,9 +1389,15 @@ int cxk_get_constraint_schur(cxk_context* ctx, int i, double* G, double* AW, dou
   CXK_DEMAND(i >= 0 && i < (int)ctx->cons.size(), "invalid constraint");
   const int m = ctx->cons[i].m;
   CXK_TRY(hipStreamSynchronize(ctx->stream));
-  if (G)
+  if (G) {
+    // Entry (r, c) of the block sits at c * m + r, and the contract is r >= c (Arena::G, lmi_types.h): above the
+    // diagonal lies whatever the route left there, on the matrix-inequality routes memory nobody wrote.  The caller
+    // gets what the consumers read, mirrored into the full symmetric square.
     CXK_TRY(hipMemcpy(G, ctx->G.p + ctx->g_off[i], sizeof(double) * (size_t)m * m,
                       hipMemcpyDeviceToHost));
+    for (int c = 1; c < m; c++)
+      for (int r = 0; r < c; r++) G[(size_t)c * m + r] = G[(size_t)r * m + c];
+  }
   if (AW)
     CXK_TRY(hipMemcpy(AW, ctx->AWc.p + ctx->r_off[i], sizeof(double) * m, hipMemcpyDeviceToHost));
   if (AQc)
@@ -1422,7 +1428,7 @@ int cxk_owns_constraint(const cxk_context* ctx, int i) {
   return ctx->owned[i];
 }
 
-int cxk_get_valid_variables(const cxk_context* ctx, unsigned char* mask /* N, original order */) {
+int cxk_get_valid_variables(const cxk_context* ctx, unsigned char* mask /* one per variable and multiplier, original order */) {
   if (!ctx || !ctx->finalized) return CXK_FAILURE;
   for (int p = 0; p < ctx->md.N; p++) mask[ctx->md.permutation_inverse[p]] = ctx->var_valid[p];
   return CXK_SUCCESS;

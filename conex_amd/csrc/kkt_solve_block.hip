@@ -12,6 +12,9 @@ int CheckSolveBlock(cxk_context* ctx, const double* Y, int ld, int nrhs) {
   CXK_DEMAND(Y != nullptr, "cxk_solve_block: null pointer for the block of right-hand sides");
   CXK_DEMAND(nrhs >= 1, "cxk_solve_block: nrhs must be at least 1");
   CXK_DEMAND(ld >= ctx->md.N, "cxk_solve_block: leading dimension ld is smaller than the system size N");
+  // (rows are addressed by variable: with unused variables the N rows of a column would not hold every index)
+  CXK_DEMAND(ctx->md.num_vars <= ctx->md.N,
+             "cxk_solve_block: a program that leaves out a variable below the largest one it uses is not supported");
   CXK_DEMAND(ctx->solver_mode != 2, "cxk_solve_block: not available in QR solver mode (the factor lives on the host)");
   CXK_DEMAND(ctx->refine_iters <= 0,
              "cxk_solve_block: iterative refinement is on (cxk_set_iterative_refinement > 0); the block solve is the "

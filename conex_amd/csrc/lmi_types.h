@@ -43,7 +43,16 @@ struct LmiGroup {
 };
 
 struct Arena {
-  double* G;              // per-constraint m x m Schur blocks (lower triangle meaningful)
+  // Per-constraint m x m Schur blocks, entry (r, c) at g_off + c * m + r.  The contract is the lower triangle, r >= c:
+  // every consumer addresses hi + lo * m -- the assembly gather's sources (kkt_plans.hip, coeff), the assembly records
+  // of tree_factor_level_asm and of the fused leaves' load phase (AsmRec, the load images); the refinement mat-vec
+  // (kkt_matvec) reads the slab saved by the factor sweep, not G.  A route may leave r < c unwritten, and every
+  // matrix-inequality route does: lmi_schur_mfma (its epilogue walks the entries of the lower triangle),
+  // lmi_schur_generic and lmi_schur_sparse (pairs j <= i), lmi_large_reduce_finalize behind the GEMM pipeline and
+  // lmi_factored_finalize (i < j returns).  The linear, second-order, quadratic, octonion and constant-block kernels
+  // write the square.  cxk_get_constraint_schur hands out r >= c mirrored into the full symmetric square on the host:
+  // no caller sees what lies above the diagonal on the device.
+  double* G;
   const int64_t* g_off;   // [K]
   double* AWc;            // per-constraint AW / AQc
   double* AQcc;

@@ -432,6 +432,14 @@ class KktContext:
     def N(self):
         return self.L.cxk_system_size(self.h)
 
+    @property
+    def span(self):
+        """Entries of a vector in the original variable order (get_y, set_y, solve_inplace, residuals,
+        valid_variables): one per variable of the context and per multiplier (V of include/conex_kkt_hip.h).  Equal to
+        N when every variable occurs in a constraint; the library indexes such vectors by variable, so a context that
+        leaves variables out has span > N."""
+        return max(self.N, self.num_vars + sum(c[1] for c in self.cons if c[0] == "eq"))
+
     def order(self):
         o = np.zeros(self.K, dtype=np.int32)
         self.L.cxk_get_order(self.h, _ip(o))
@@ -516,9 +524,8 @@ class KktContext:
         return G.reshape(m, m).T.copy(), AW, AQc, sc
 
     def residuals(self):
-        N = self.N
-        AW = np.zeros(N)
-        AQc = np.zeros(N)
+        AW = np.zeros(self.span)   # indexed by variable: entries of unused variables stay 0
+        AQc = np.zeros(self.span)
         sc = np.zeros(2)
         self._check(self.L.cxk_get_residuals(self.h, _dp(AW), _dp(AQc), _dp(sc)),
                     "cxk_get_residuals")
@@ -535,7 +542,9 @@ class KktContext:
         return ok.value
 
     def solve_inplace(self, y):
-        y = np.ascontiguousarray(y, dtype=np.float64).copy()
+        y = np.ascontiguousarray(y, dtype=np.float64).ravel().copy()
+        if len(y) < self.span:
+            raise ValueError(f"solve_inplace: expected {self.span} entries (one per variable and multiplier), got {len(y)}")
         self._check(self.L.cxk_solve_inplace(self.h, _dp(y)), "cxk_solve_inplace")
         return y
 
@@ -629,12 +638,14 @@ class KktContext:
         return ok, self.get_y()
 
     def get_y(self):
-        y = np.zeros(self.N)
+        y = np.zeros(self.span)   # indexed by variable: entries of unused variables stay 0
         self._check(self.L.cxk_get_y(self.h, _dp(y)), "cxk_get_y")
         return y
 
     def set_y(self, y):
-        y = np.ascontiguousarray(y, dtype=np.float64)
+        y = np.ascontiguousarray(y, dtype=np.float64).ravel()
+        if len(y) < self.span:
+            raise ValueError(f"set_y: expected {self.span} entries (one per variable and multiplier), got {len(y)}")
         self._check(self.L.cxk_set_y(self.h, _dp(y)), "cxk_set_y")
 
     def prepare_step(self, y, c_weight, e_weight=1.0, affine=0):
@@ -760,7 +771,7 @@ class KktContext:
         return bool(self.L.cxk_owns_constraint(self.h, i))
 
     def valid_variables(self):
-        m = np.zeros(self.N, dtype=np.uint8)
+        m = np.zeros(self.span, dtype=np.uint8)   # indexed by variable: unused variables are not valid
         self._check(self.L.cxk_get_valid_variables(self.h, m.ctypes.data_as(C.POINTER(C.c_ubyte))),
                     "cxk_get_valid_variables")
         return m.astype(bool)

@@ -401,10 +401,17 @@ int cxk_step_scalars(cxk_context* ctx, double* out6);
 int cxk_kkt_solve_async(cxk_context* ctx, double inv_sqrt_mu, double b_scaling,
                         double c_scaling);
 int cxk_sync(cxk_context* ctx, int* factor_ok);
-/* SolveInPlace on a host vector of length N (copy in, solve, copy out). */
+/* Vectors in the ORIGINAL VARIABLE ORDER -- cxk_solve_inplace, cxk_get_y, cxk_set_y, cxk_get_residuals,
+ * cxk_get_valid_variables -- are indexed by variable: entry v belongs to variable v, the multipliers of the equality
+ * blocks follow the num_vars variables.  Their length, V below, is num_vars + multipliers.  V = N when every
+ * variable occurs in some constraint.  A program that leaves variables out has a smaller N (cxk_system_size
+ * counts the variables that occur) and the same indices: entries of unused variables are neither read nor written,
+ * but the vector still has V entries, and a shorter one is read and written past its end. */
+/* SolveInPlace on a host vector of length V (copy in, solve, copy out). */
 int cxk_solve_inplace(cxk_context* ctx, double* y);
 /* Y <- K^-1 Y for nrhs columns with the factor of the latest factorization.  Y is N x nrhs, column-major with
- * leading dimension ld >= N, in the ORIGINAL variable order (cxk_solve_inplace's convention).  The plain factor
+ * leading dimension ld >= N, in the ORIGINAL variable order (cxk_solve_inplace's convention; a program that leaves
+ * out a variable below the largest one it uses is refused: N rows would not hold every index).  The plain factor
  * solve: level-scheduled block substitution, cxk_solve_block_chunk_width() columns per workgroup, the factor read
  * once per chunk; column j of the result depends on column j of the input only, runs are bit-reproducible.
  * Leaves y, W, the slab, the residuals and the three solutions of cxk_factor_solve_triple_async alone.  Refused
@@ -416,8 +423,8 @@ int cxk_solve_block_device(cxk_context* ctx, double* Y_dev, int ld, int nrhs);  
 int cxk_solve_block_chunk_width(void);
 /* (sharded context with a communicator: a COLLECTIVE -- a sum all-reduce of N doubles assembles the
  * whole vector, so every rank must call it, in the same order relative to its other cxk_* calls) */
-int cxk_get_y(cxk_context* ctx, double* y /* N, original variable order */);
-int cxk_set_y(cxk_context* ctx, const double* y);
+int cxk_get_y(cxk_context* ctx, double* y /* V, original variable order (above cxk_solve_inplace) */);
+int cxk_set_y(cxk_context* ctx, const double* y /* V */);
 
 /* PrepareStep over all constraints (cone_program.h:69-90); info = {normsqrd, norminfd}.
  * Uses the device-resident y.  Syncs (returns two scalars). */
@@ -484,9 +491,13 @@ int cxk_prepare_take_step_device_mu(cxk_context* ctx, double c_scaling, double e
 /* ---- inspection (tests, KKTMatrix() kkt_solver.cc:265-269) ------------- */
 int cxk_get_slab(cxk_context* ctx, double* out);
 int cxk_set_slab(cxk_context* ctx, const double* in);
-int cxk_get_constraint_schur(cxk_context* ctx, int i, double* G /* m*m lower */, double* AW,
+/* G: the m x m Schur block of constraint i, column-major, G_ab = tr(A_a W A_b W) (symmetric for non-symmetric
+ * A too).  On the device the block's contract is its lower triangle (row >= column): that is all the
+ * factorization reads, and the matrix-inequality routes write nothing else.  The call returns that triangle
+ * mirrored into the full symmetric square, never what lies above the diagonal on the device. */
+int cxk_get_constraint_schur(cxk_context* ctx, int i, double* G /* m*m */, double* AW,
                              double* AQc, double* scalars /* 2 */);
-int cxk_get_residuals(cxk_context* ctx, double* AW /* N */, double* AQc /* N */,
+int cxk_get_residuals(cxk_context* ctx, double* AW /* V */, double* AQc /* V: original variable order */,
                       double* scalars /* 2 */);
 
 /* ---- multi-GPU (the reference is single process, so no counterpart) ----------
@@ -560,7 +571,7 @@ int cxk_exchange_upload(cxk_context* ctx, const double* in);
 int cxk_kkt_local_async(cxk_context* ctx, double inv_sqrt_mu, double b_scaling, double c_scaling);
 int cxk_kkt_finish_async(cxk_context* ctx, double inv_sqrt_mu, double b_scaling, double c_scaling);
 int cxk_owns_constraint(const cxk_context* ctx, int i);
-int cxk_get_valid_variables(const cxk_context* ctx, unsigned char* mask /* N, original order */);
+int cxk_get_valid_variables(const cxk_context* ctx, unsigned char* mask /* V, original variable order */);
 int cxk_shard_info(const cxk_context* ctx, int* cut_level, int* num_levels, long* exchange_count);
 /* single-GPU building blocks kept for symmetry with the reference call sequence */
 int cxk_assemble_local(cxk_context* ctx);

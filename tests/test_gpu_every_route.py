@@ -111,6 +111,23 @@ def run_stages(k, ids, y):
     return out
 
 
+def test_schur_blocks_come_back_as_full_symmetric_squares(monkeypatch):
+    """On the device a Schur block's contract is its lower triangle, and the matrix-inequality routes write nothing else
+    (Arena::G, lmi_types.h); constraint_schur hands out that triangle mirrored.  On every route: finite, exactly
+    symmetric, and not a triangle with zeros (or whatever the allocation held) above it."""
+    rows = constraints()
+    for row in rows:
+        name, _, _, settings, env = row
+        k, ids = build([row], settings or (lambda k: None), monkeypatch, env)
+        k.assemble()
+        G = k.constraint_schur(ids[name])[0]
+        assert G.shape[0] == G.shape[1] >= 2, name
+        assert np.all(np.isfinite(G)), name
+        assert same_bits(G, G.T.copy()), name
+        if name.startswith("lmi-"):  # the routes that leave the upper triangle unwritten on the device
+            assert np.any(np.triu(G, 1) != 0.0), name
+
+
 def test_one_constraint_on_every_route_is_what_it_is_alone(monkeypatch):
     rows = constraints()
     assert [r[0] for r in rows] == list(EVERY_ROUTE)  # (the shapes test_cone_route.py holds in its table)
