@@ -83,6 +83,9 @@ def api():
         "CONEX_HIP_AddLMIConstraintFromEntries": (ci, [vp, ci, ip, ip, ip, c_double_p, ci, C.POINTER(C.c_long)]),
         "CONEX_HIP_SetSparseAffine": (ci, [vp, ci]),
         "CONEX_HIP_CountSparseAffine": (ci, [vp]),
+        "CONEX_HIP_AddHermitianConstraintFromEntries": (ci, [vp, ci, ci, ip, ip, ip, c_double_p, ci, C.POINTER(C.c_long)]),
+        "CONEX_HIP_SetSparseFold": (ci, [vp, ci]),
+        "CONEX_HIP_CountSparseFold": (ci, [vp]),
         # the block solve of the cxk_* layer (include/conex_kkt_hip.h), as conex_amd.kkt declares it
         "cxk_solve_block": (ci, [vp, c_double_p, ci, ci]),
         "cxk_solve_block_device": (ci, [vp, vp, ci, ci]),

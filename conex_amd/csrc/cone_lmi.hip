@@ -104,6 +104,10 @@ int UploadLmiSparse(cxk_context* ctx, Group& g) {
   }
   return CXK_SUCCESS;
 }
+// Where a folded sparse group beyond the LDS-resident shapes keeps the projection of W onto the real representations
+// during an assembly (lmi_fold_project): the last of the eight squares of ws_main, which the assembly leaves alone.
+// (An LDS-resident group projects on its way into LDS.)
+static double* FoldedW(Group& g) { return g.lmi.ws_main.p + g.ids.size() * 7 * (size_t)g.n * g.n; }
 
 LmiLargeWs MakeLargeWs(Group& g) {
   LmiLargeWs w;
@@ -318,10 +322,25 @@ const char* const kLmiKernelNames[kLmiKernelCount] = {
 // "not an instance"), and cxk_lmi_kernel_name knows it.  lmi_schur_sparse behind lmi_affine_wc / _x / _scalars.
 constexpr LmiKernel kSchurSparseAffine = (LmiKernel)(kLmiKernelCount + 1);
 constexpr const char* kSchurSparseAffineName = "lmi_schur_sparse hbm sparse-C";
+// Likewise the folded forms of the five sparse instances (cxk_set_sparse_fold, cxk_add_hermitian_coo): the four listed
+// ones in their order, then the one above.
+constexpr LmiKernel kSchurSparseFolded = (LmiKernel)(kLmiKernelCount + 2);
+constexpr int kSchurSparseFoldedCount = 5;
+constexpr const char* kSchurSparseFoldedNames[kSchurSparseFoldedCount] = {
+    "lmi_schur_sparse small folded", "lmi_schur_sparse small dense-C folded", "lmi_schur_sparse hbm folded",
+    "lmi_schur_sparse hbm dense-C folded", "lmi_schur_sparse hbm sparse-C folded"};
 
 bool IsSchurMfma(LmiKernel k) { return k >= kSchurMfma8 && k <= kSchurMfma24FoldedSingle; }
 bool IsSchurGemm(LmiKernel k) { return k >= kSchurGemm && k <= kSchurGemmFoldedLargeSplit; }
-bool IsSchurSparse(LmiKernel k) { return (k >= kSchurSparseSmall && k <= kSchurSparseDenseC) || k == kSchurSparseAffine; }
+bool IsSchurSparseFolded(LmiKernel k) { return k >= kSchurSparseFolded && k < kSchurSparseFolded + kSchurSparseFoldedCount; }
+bool IsSchurSparse(LmiKernel k) {
+  return (k >= kSchurSparseSmall && k <= kSchurSparseDenseC) || k == kSchurSparseAffine || IsSchurSparseFolded(k);
+}
+// the instance a folded one is the form of
+LmiKernel UnfoldedSchurSparse(LmiKernel k) {
+  if (!IsSchurSparseFolded(k)) return k;
+  return k - kSchurSparseFolded == 4 ? kSchurSparseAffine : (LmiKernel)(kSchurSparseSmall + (k - kSchurSparseFolded));
+}
 bool IsPrepareRows(LmiKernel k) {
   return (k >= kPrepareRowsPacked && k <= kPrepareRowsEven) || (k >= kQueryRowsPacked && k <= kQueryRowsEven);
 }
@@ -331,6 +350,8 @@ LmiKernel LmiSchurKernel(const Group& g) {
   // not one of the instances: a code outside the reported range, which no Is*() test accepts and
   // cxk_lmi_kernel_name has no name for (LaunchSchur switches on the route first, cxk_lmi_kernels refuses the constraint)
   if (g.route == ConeRoute::kLmiFactored) return kLmiKernelCount;
+  if (g.route == ConeRoute::kLmiSparse && g.lmi.sp.fold)
+    return (LmiKernel)(kSchurSparseFolded + (g.lmi.sa.on ? 4 : (g.lmi.sp.small ? 0 : 2) + (g.lmi.sp.cdense ? 1 : 0)));
   if (g.route == ConeRoute::kLmiSparse && g.lmi.sa.on) return kSchurSparseAffine;
   if (g.route == ConeRoute::kLmiSparse) return (LmiKernel)((g.lmi.sp.small ? kSchurSparseSmall : kSchurSparse) + (g.lmi.sp.cdense ? 1 : 0));
   if (g.lmi.assembly == LmiAssembly::kGemm) {  // (fold and split counts as LmiLargeSchur reads them: MakeLargeWs, LmiFoldedSplits)
@@ -499,6 +520,31 @@ int UploadSparseLmi(cxk_context* ctx, Group& g) {
   g.lmi.sp.cdense = false;
   for (size_t k = 0; k < cnt; k++)
     if (lists[k].ptr[m1] - lists[k].ptr[m] > 64) g.lmi.sp.cdense = true;  // (C, C) alone would be nz^2 terms on one wavefront
+  // a folded group (kernels_lmi_sparse.hip.h, "The folded sums"): within every list that joins the sums the entries of
+  // the top block row, rows below n / herm_d, go first; both parts keep their order by column then row.  A dense C
+  // stays as it is (its list is read by columns: UploadSparseAffine).  Everything below reads the reordered lists.
+  std::vector<int> etop;
+  if (g.lmi.sp.fold) {
+    CXK_DEMAND(g.herm_d > 1, "internal error: only a Hermitian group over C or H folds its sums");
+    const int n0 = n / g.herm_d;
+    etop.assign(cnt * m1, 0);
+    for (size_t k = 0; k < cnt; k++) {
+      LmiLists& L = lists[k];
+      std::vector<int> rc(L.rc, L.rc + L.ptr[m1]);
+      std::vector<double> val(L.val, L.val + L.ptr[m1]);
+      const std::vector<int> ptr(L.ptr, L.ptr + m1 + 1);
+      for (int i = 0; i < (g.lmi.sp.cdense ? m : m1); i++) {
+        int at = ptr[i];
+        for (int pass = 0; pass < 2; pass++) {
+          for (int e = ptr[i]; e < ptr[i + 1]; e++)
+            if (((L.rc[e] & 0xffff) < n0) == (pass == 0)) rc[at] = L.rc[e], val[at++] = L.val[e];
+          if (pass == 0) etop[k * m1 + i] = at - ptr[i];
+        }
+      }
+      L.own_rc = std::move(rc), L.own_val = std::move(val), L.own_ptr = ptr;
+      L.ptr = L.own_ptr.data(), L.rc = L.own_rc.data(), L.val = L.own_val.data();
+    }
+  }
   std::vector<int> eptr(cnt * m1 + 1, 0), erc, pptr(cnt * nn + 1, 0), pvar;
   std::vector<double> eval, pval;
   g.lmi.sp.emax = 0;
@@ -529,11 +575,12 @@ int UploadSparseLmi(cxk_context* ctx, Group& g) {
         pval[at] = L.val[e];
       }
   }
-  g.lmi.sp.small = !g.lmi.large && LmiSparseLds(n, m, true, g.lmi.sp.cdense, 0) <= kLdsLimit;
+  g.lmi.sp.small = !g.lmi.large && LmiSparseLds(n, m, true, g.lmi.sp.cdense, 0, g.lmi.sp.fold) <= kLdsLimit;
   // work split: lanes per pair from the average number of terms of a pair (each lane takes four
   // terms at a time); enough workgroups to fill the chip when the group is small
+  // (a folded pair is top x full: 1 / herm_d of the terms)
   const double per_mat = cnt ? (double)eval.size() / (double)(cnt * m1) : 0.0;
-  const double avg_terms = per_mat * per_mat;
+  const double avg_terms = g.lmi.sp.fold ? per_mat * per_mat / g.herm_d : per_mat * per_mat;
   g.lmi.sp.lpp = avg_terms <= 8 ? 1 : avg_terms <= 64 ? 4 : avg_terms <= 1024 ? 16 : 64;
   const double pairs = 0.5 * m1 * (m1 + 1.0);
   const double per_block = (256.0 / g.lmi.sp.lpp) * 4.0;  // pairs one workgroup takes in stride
@@ -547,6 +594,7 @@ int UploadSparseLmi(cxk_context* ctx, Group& g) {
       for (int j = 0; j <= i; j++) pr.push_back(i | (j << 16));
     CXK_TRY(g.lmi.sp.pairs.upload(pr));
   }
+  if (g.lmi.sp.fold) CXK_TRY(g.lmi.sp.etop.upload(etop));
   CXK_TRY(g.lmi.sp.eptr.upload(eptr));
   CXK_TRY(g.lmi.sp.erc.upload(erc));
   CXK_TRY(g.lmi.sp.eval.upload(eval));
@@ -563,13 +611,13 @@ int UploadSparseLmi(cxk_context* ctx, Group& g) {
 // Sparse LMI group: the nonzero sums; a dense C first needs X = W C W (LDS for small orders, two
 // GEMMs otherwise).
 
-template <bool SMALL, int LPP, bool AFF>
+template <bool SMALL, int LPP, bool AFF, bool FOLD>
 hipError_t LaunchLmiSparseKernelL(Group& g, const LmiGroup& d, const Arena& ar, const double* X, hipStream_t st) {
   const dim3 grid(d.count, g.lmi.sp.chunks);
   const int emax = (g.lmi.sp.emax + 1) & ~1;  // keeps the arrays behind it 8-byte aligned
-  const bool stage = LmiSparseLds(g.n, g.m, SMALL, g.lmi.sp.cdense, emax) <= kLdsLimit;
-  const size_t lds = LmiSparseLds(g.n, g.m, SMALL, g.lmi.sp.cdense, stage ? emax : 0);
-  SparseLaunchOf<AFF> L;
+  const bool stage = LmiSparseLds(g.n, g.m, SMALL, g.lmi.sp.cdense, emax, FOLD) <= kLdsLimit;
+  const size_t lds = LmiSparseLds(g.n, g.m, SMALL, g.lmi.sp.cdense, stage ? emax : 0, FOLD);
+  SparseLaunchOf<AFF, FOLD> L;
   L.Xg = X;
   L.part = g.lmi.ws_part.p;
   L.npart = kSparseCParts;
@@ -580,35 +628,50 @@ hipError_t LaunchLmiSparseKernelL(Group& g, const LmiGroup& d, const Arena& ar, 
     L.eslot = g.lmi.sa.eslot.p;
     L.ppos = g.lmi.sa.pptr.p;
   }
+  if constexpr (FOLD) L.etop = g.lmi.sp.etop.p;
   auto raise = [&](const void* k) -> hipError_t {  // dynamic LDS beyond 64 KB needs the attribute
     return lds > 64 * 1024 ? hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit)
                            : hipSuccess;
   };
   hipError_t e;
   if (stage) {
-    if ((e = raise(reinterpret_cast<const void*>(&lmi_schur_sparse<SMALL, LPP, true, AFF>))) != hipSuccess) return e;
-    lmi_schur_sparse<SMALL, LPP, true, AFF><<<grid, 256, lds, st>>>(d, ar, L);
+    if ((e = raise(reinterpret_cast<const void*>(&lmi_schur_sparse<SMALL, LPP, true, AFF, FOLD>))) != hipSuccess) return e;
+    lmi_schur_sparse<SMALL, LPP, true, AFF, FOLD><<<grid, 256, lds, st>>>(d, ar, L);
   } else {
-    if ((e = raise(reinterpret_cast<const void*>(&lmi_schur_sparse<SMALL, LPP, false, AFF>))) != hipSuccess) return e;
-    lmi_schur_sparse<SMALL, LPP, false, AFF><<<grid, 256, lds, st>>>(d, ar, L);
+    if ((e = raise(reinterpret_cast<const void*>(&lmi_schur_sparse<SMALL, LPP, false, AFF, FOLD>))) != hipSuccess) return e;
+    lmi_schur_sparse<SMALL, LPP, false, AFF, FOLD><<<grid, 256, lds, st>>>(d, ar, L);
   }
   return hipGetLastError();
 }
 
-template <bool SMALL, bool AFF = false>
-hipError_t LaunchLmiSparseKernel(Group& g, const LmiGroup& d, const Arena& ar, const double* X, hipStream_t st) {
+template <bool SMALL, bool AFF, bool FOLD>
+hipError_t LaunchLmiSparseKernelF(Group& g, const LmiGroup& d, const Arena& ar, const double* X, hipStream_t st) {
   switch (g.lmi.sp.lpp) {
-    case 1: return LaunchLmiSparseKernelL<SMALL, 1, AFF>(g, d, ar, X, st);
-    case 4: return LaunchLmiSparseKernelL<SMALL, 4, AFF>(g, d, ar, X, st);
-    case 16: return LaunchLmiSparseKernelL<SMALL, 16, AFF>(g, d, ar, X, st);
-    default: return LaunchLmiSparseKernelL<SMALL, 64, AFF>(g, d, ar, X, st);
+    case 1: return LaunchLmiSparseKernelL<SMALL, 1, AFF, FOLD>(g, d, ar, X, st);
+    case 4: return LaunchLmiSparseKernelL<SMALL, 4, AFF, FOLD>(g, d, ar, X, st);
+    case 16: return LaunchLmiSparseKernelL<SMALL, 16, AFF, FOLD>(g, d, ar, X, st);
+    default: return LaunchLmiSparseKernelL<SMALL, 64, AFF, FOLD>(g, d, ar, X, st);
   }
 }
 
-hipError_t LaunchLmiSchurSparse(Group& g, LmiKernel kern, const Arena& ar, hipStream_t st) {
-  const LmiGroup d = MakeLmi(g);
+// (the folded form of an instance by the code: LmiSchurKernel)
+template <bool SMALL, bool AFF = false>
+hipError_t LaunchLmiSparseKernel(Group& g, bool fold, const LmiGroup& d, const Arena& ar, const double* X, hipStream_t st) {
+  return fold ? LaunchLmiSparseKernelF<SMALL, AFF, true>(g, d, ar, X, st) : LaunchLmiSparseKernelF<SMALL, AFF, false>(g, d, ar, X, st);
+}
+
+hipError_t LaunchLmiSchurSparse(Group& g, LmiKernel code, const Arena& ar, hipStream_t st) {
+  LmiGroup d = MakeLmi(g);
   const int n = g.n;
-  if (kern == kSchurSparseSmall || kern == kSchurSparseSmallDenseC) return LaunchLmiSparseKernel<true>(g, d, ar, nullptr, st);
+  const bool fold = IsSchurSparseFolded(code);
+  const LmiKernel kern = UnfoldedSchurSparse(code);
+  if (kern == kSchurSparseSmall || kern == kSchurSparseSmallDenseC) return LaunchLmiSparseKernel<true>(g, fold, d, ar, nullptr, st);
+  if (fold) {  // every launch below reads the projection of W onto the real representations (kernels_lmi_sparse.hip.h)
+    const int n0 = n / g.herm_d;
+    double* Wp = FoldedW(g);
+    lmi_fold_project<<<dim3((n0 * n0 + 255) / 256, g.herm_d, d.count), 256, 0, st>>>(d, Wp);
+    d.W = Wp;
+  }
   double* X = nullptr;
   if (kern == kSchurSparseAffine) {
     SparseAffine a;
@@ -624,7 +687,7 @@ hipError_t LaunchLmiSchurSparse(Group& g, LmiKernel kern, const Arena& ar, hipSt
     lmi_affine_wc<<<dim3(tiles, tiles, d.count), 256, 0, st>>>(d, a);
     lmi_affine_x<<<dim3((g.lmi.sa.pmax + 3) / 4, d.count), 256, 0, st>>>(d, a);
     lmi_affine_scalars<<<dim3(kSparseCParts, d.count), 256, 0, st>>>(d, a, g.lmi.ws_part.p);
-    return LaunchLmiSparseKernel<false, true>(g, d, ar, nullptr, st);
+    return LaunchLmiSparseKernel<false, true>(g, fold, d, ar, nullptr, st);
   } else if (g.lmi.sp.cdense) {
     const int64_t nn = (int64_t)n * n;
     double* CW = g.lmi.ws_main.p;                  // count x nn
@@ -636,7 +699,7 @@ hipError_t LaunchLmiSchurSparse(Group& g, LmiKernel kern, const Arena& ar, hipSt
     if ((e = LaunchGemm(a, false, false, d.count, st)) != hipSuccess) return e;
     lmi_dense_c_scalars<<<dim3(kSparseCParts, d.count), 256, 0, st>>>(d, X, g.lmi.ws_part.p);
   }
-  return LaunchLmiSparseKernel<false>(g, d, ar, X, st);
+  return LaunchLmiSparseKernel<false>(g, fold, d, ar, X, st);
 }
 
 // The Schur complement of a group of dense LMIs, on the instance LmiSchurKernel names.
@@ -780,6 +843,7 @@ int cxk_lmi_kernels(const cxk_context* ctx, int constraint, int out[5]) {
 
 const char* cxk_lmi_kernel_name(int code) {
   if (code == kSchurSparseAffine) return kSchurSparseAffineName;
+  if (IsSchurSparseFolded((LmiKernel)code)) return kSchurSparseFoldedNames[code - kSchurSparseFolded];
   return code >= 0 && code < kLmiKernelCount ? kLmiKernelNames[code] : nullptr;
 }
 

@@ -163,6 +163,10 @@ struct RouteModes {
   // said, each constraint keeps the default of its entry point (cxk_add_lmi 0, cxk_add_lmi_coo -1).  No route hangs on it.
   int sparse_affine = -2;
   double sparse_affine_min_ratio = kSparseAffineMinRatio;           // CXK_SPARSE_AFFINE_MIN_RATIO (comparison runs)
+  // CXK_SPARSE_FOLD: whether a sparse Hermitian LMI group over C or H sums over the top block row of its real
+  // representations (kernels_lmi_sparse.hip.h, "The folded sums"): 0 never, 1 always; -2: nobody said, each constraint
+  // keeps the default of its entry point (cxk_add_hermitian 0, cxk_add_hermitian_coo 1).  No route hangs on it.
+  int sparse_fold = -2;
 };
 
 // The route, or why there is none (`refusal` is the message cxk_finalize fails with; null with a route).
@@ -277,10 +281,14 @@ inline RouteChoice ChooseLmi(const ConeShape& s, const RouteModes& md) {
   // of the kernels)
   if (s.factored) return Take(ConeRoute::kLmiFactored);
   // held by its nonzeros (symmetric by construction, order and variables within kSparseLmiMaxIndex: cxk_add_lmi_coo)
+  // (a Hermitian one, herm_d set: cxk_add_hermitian_coo)
   if (s.csr_only) {
     if (md.sparse_lmi == 0)
-      return Refuse("a matrix inequality added by cxk_add_lmi_coo has no dense matrices and can only take the sparse route "
-                    "(CXK_SPARSE_LMI, which is 0)");
+      return Refuse(s.herm_d > 0
+                        ? "a matrix inequality added by cxk_add_hermitian_coo has no dense matrices and can only take the sparse "
+                          "route (CXK_SPARSE_LMI, which is 0)"
+                        : "a matrix inequality added by cxk_add_lmi_coo has no dense matrices and can only take the sparse route "
+                          "(CXK_SPARSE_LMI, which is 0)");
     return Take(ConeRoute::kLmiSparse);
   }
   // The reference accepts non-symmetric matrices and evaluates <W A_i W, A_j> as written; only the literal LDS

@@ -177,6 +177,10 @@ struct CXK_LOCAL LmiState {
     int chunks = 1, emax = 0;  // emax: most nonzeros in one constraint
     bool cdense = false;       // dense affine term: X = W C W instead of pair sums with C
     bool small = false;        // W (and X) of a constraint fit in LDS
+    // a Hermitian group over C or H whose sums run over the top block row of every first list (cxk_set_sparse_fold;
+    // kernels_lmi_sparse.hip.h, "The folded sums"): the top entries stand first in each list, etop counts them
+    bool fold = false;
+    DevBuf<int> etop;
     DevBuf<int> eptr, erc, pptr, pvar, pairs;
     DevBuf<double> eval, pval;
   } sp;

@@ -65,8 +65,16 @@ struct SparseLaunchAffine : SparseLaunch {
   const int* eslot;
   const int* ppos;
 };
-template <bool AFF>
-using SparseLaunchOf = typename std::conditional<AFF, SparseLaunchAffine, SparseLaunch>::type;
+// ... of the folded instances (FOLD; "The folded sums" below): etop[mem * (m + 1) + i], the number of entries of list
+// (mem, i) that lie in the top block row of the real representation.  They stand first in the list.
+template <class Base>
+struct SparseLaunchFolded : Base {
+  const int* etop;
+};
+template <bool AFF, bool FOLD = false>
+using SparseLaunchOf = typename std::conditional<
+    FOLD, SparseLaunchFolded<typename std::conditional<AFF, SparseLaunchAffine, SparseLaunch>::type>,
+    typename std::conditional<AFF, SparseLaunchAffine, SparseLaunch>::type>::type;
 
 // Dense C beyond LDS-resident orders: partial sums of <w,c> = sum C o W and <c,Qc> = sum C o X over
 // slices of the n^2 positions; grid (npart, count).  The sparse kernel adds them in block order.
@@ -189,6 +197,43 @@ __global__ void __launch_bounds__(256) lmi_affine_scalars(LmiGroup g, SparseAffi
   }
 }
 
+// A folded group (lmi_schur_sparse, "The folded sums") reads W through its projection onto the real representations:
+//   X_p[r,c] = 1/d sum_j sign[p][j] W[(p^j) n0 + r, j n0 + c],   Wp block (p^j, j) = sign[p][j] X_p      (n0 = n / d)
+// The W that the step kernels leave is a real representation only up to their rounding, which grows with the
+// conditioning of W over an interior-point run.  The unfolded sums average that deviation E over the d block rows: for
+// real representations A, B,  tr(A (W + E) B (W + E)) = tr(A (W + PE) B (W + PE)) + O(E^2)  with P this (orthogonal)
+// projection, because  tr(E S) = tr(PE S)  for every real representation S.  The folded sums read one block row, and on
+// W as stored they would see E itself; on PW they give the unfolded value to second order in E.  For a W that is a
+// real representation already (cxk_set_W embeds planes) the projection returns its bits: the averages are of equal
+// numbers and 1/d is a power of two.  grid (n0^2 / 256, d, count); a thread per plane entry, d reads and d writes;
+// fixed order.  W itself is left as it is: the step kernels of a folded group run as those of any other.
+// An LDS-resident group (SMALL) needs no launch for it: lmi_schur_sparse projects while it loads W into LDS
+// (FoldProjected, the same operations in the same order).
+__device__ __forceinline__ int HcSignOf(int p, int j) {
+  constexpr int sg[4][4] = {{1, 1, 1, 1}, {1, -1, -1, 1}, {1, 1, -1, -1}, {1, -1, 1, -1}};  // (kHcSign)
+  return sg[p][j];
+}
+// plane p of PW at (r, c): the average over the d blocks that carry it
+__device__ __forceinline__ double FoldPlane(const double* __restrict__ W, int n, int n0, int d, int p, int r, int c) {
+  double s = 0;
+  for (int j = 0; j < d; j++) s += HcSignOf(p, j) * W[(size_t)((p ^ j) * n0 + r) + (size_t)(j * n0 + c) * n];
+  return s * (1.0 / d);
+}
+// entry (row, col) of PW
+__device__ __forceinline__ double FoldProjected(const double* __restrict__ W, int n, int n0, int d, int row, int col) {
+  const int k = row / n0, j = col / n0, p = k ^ j;
+  return HcSignOf(p, j) * FoldPlane(W, n, n0, d, p, row - k * n0, col - j * n0);
+}
+__global__ void __launch_bounds__(256) lmi_fold_project(LmiGroup g, double* __restrict__ Wp) {
+  const int d = g.herm_d, n = g.n, n0 = n / d, p = blockIdx.y, mem = blockIdx.z;
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  if (q >= n0 * n0) return;
+  const int r = q % n0, c = q / n0;
+  double* O = Wp + (size_t)mem * n * n;
+  const double s = FoldPlane(g.W + (size_t)mem * n * n, n, n0, d, p, r, c);
+  for (int j = 0; j < d; j++) O[(size_t)((p ^ j) * n0 + r) + (size_t)(j * n0 + c) * n] = HcSignOf(p, j) * s;
+}
+
 // Sum over a group of LPP consecutive lanes (LPP a power of two <= 64) in a fixed butterfly order;
 // every lane of the group receives the total.
 template <int LPP>
@@ -214,9 +259,11 @@ __device__ __forceinline__ double GroupSum(double v) {
 // where a term-by-term walk over the ni x nj rectangle took ~30 (the kernel is bound by instruction
 // issue at the sparse-C4 shape: DESIGN 4.8).  sum_i a_i (sum_j b_j w w): fixed order, bit-reproducible;
 // every lane of the group returns the total.
-template <int LP>
+// FOLD: the first list is walked over its top entries only (ti, tj: their counts in the two lists; they stand first),
+// the second over all of its entries: after the swap by length, top(longer) x full(shorter).
+template <int LP, bool FOLD = false>
 __device__ __forceinline__ double PairSum(const int* erc, const double* eval, const double* W, int n, int bi,
-                                          int ni, int bj, int nj, int sub) {
+                                          int ni, int bj, int nj, int sub, int ti = 0, int tj = 0) {
   if (nj > ni) {  // (uniform over the group)
     int t = bi;
     bi = bj;
@@ -224,7 +271,9 @@ __device__ __forceinline__ double PairSum(const int* erc, const double* eval, co
     t = ni;
     ni = nj;
     nj = t;
+    if constexpr (FOLD) ti = tj;
   }
+  if constexpr (FOLD) ni = ti;
   double s = 0;
   for (int ei = sub; ei < ni; ei += LP) {
     const int rc = erc[bi + ei], r = rc & 0xffff, c = rc >> 16;
@@ -266,8 +315,20 @@ __device__ __forceinline__ double PairSum(const int* erc, const double* eval, co
 // constraint's entry list is copied to LDS first: a sweep reads entries at unrelated addresses,
 // which costs a cache line per lane from L1/L2 but only bank conflicts from LDS.
 // AFF (never with SMALL): AQc gathers W C W from the values at the positions.
-template <bool SMALL, int LPP, bool STAGE, bool AFF = false>
-__global__ void __launch_bounds__(256) lmi_schur_sparse(LmiGroup g, Arena ar, SparseLaunchOf<AFF> L) {
+//
+// The folded sums (FOLD: a Hermitian group over C or H, d = herm_d > 1, order n = d n0).  For a real representation
+// M = L(X) every diagonal block of M is X_0, so tr M / d is the trace of the top-left n0 x n0 block, and with M a
+// product that begins with L(A_i) only the rows r < n0 of L(A_i) reach it:
+//   tr(L(A_i) W L(A_j) W) / d = sum_{(r,c,a) in L(A_i), r < n0} sum_{(p,q,b) in L(A_j)} a b W[c,p] W[q,r]
+//   tr(L(A_i) X) / d          = sum_{(r,c,a) in L(A_i), r < n0} a X[c,r]            (X = W, or W C W)
+// The top block row holds the blocks (0, j) = +-X_j, every plane once: exactly 1 / d of the list.  So every sum over a
+// first list runs over its top entries and is multiplied by no 1 / d: d-fold fewer terms.  Within each list the top
+// entries stand first (by column, then row), the others behind them (by column, then row); L.etop has the count of
+// the former.  A pair (i, j) is top(longer) x full(shorter): the order of summation is fixed by the lists alone.
+// <w,c> and <c,Qc> of a dense C (the block sums over n^2 positions) keep the full form and their 1 / d.
+// The W (and the W C W) of a folded launch is the projection that lmi_fold_project makes (above).
+template <bool SMALL, int LPP, bool STAGE, bool AFF = false, bool FOLD = false>
+__global__ void __launch_bounds__(256) lmi_schur_sparse(LmiGroup g, Arena ar, SparseLaunchOf<AFF, FOLD> L) {
   extern __shared__ double lds[];
   const int n = g.n, m = g.m, m1 = m + 1, nn = n * n;
   const int mem = blockIdx.x, id = g.ids[mem];
@@ -275,7 +336,8 @@ __global__ void __launch_bounds__(256) lmi_schur_sparse(LmiGroup g, Arena ar, Sp
   const double* Wg = g.W + (size_t)mem * nn;
   const int* gptr = g.sp_eptr + (size_t)mem * m1;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
-  const double osc = g.herm_d > 1 ? 1.0 / g.herm_d : 1.0;
+  const double osc = g.herm_d > 1 ? 1.0 / g.herm_d : 1.0;  // (the sums over n^2 positions of a dense C)
+  const double lsc = FOLD ? 1.0 : osc;                      // (the sums over entry lists)
   const bool first = blockIdx.y == 0;
   const bool cdense = L.cdense != 0;
   // LDS: [W | C P X (dense C)] (SMALL), entry values, entry row/col, list pointers
@@ -283,9 +345,12 @@ __global__ void __launch_bounds__(256) lmi_schur_sparse(LmiGroup g, Arena ar, Sp
   double* s_val = lds + (SMALL ? (cdense ? 4 : 1) * (size_t)nn : 0);
   int* s_rc = reinterpret_cast<int*>(s_val + (STAGE ? L.emax : 0));
   int* s_ptr = s_rc + (STAGE ? L.emax : 0);
+  int* s_top = reinterpret_cast<int*>(reinterpret_cast<double*>(s_ptr + ((m1 + 3) & ~1)) + 16);  // (FOLD; behind the scratch)
   SPSTAMP(0);
   const int e0 = gptr[0];
   for (int q = threadIdx.x; q <= m1; q += blockDim.x) s_ptr[q] = gptr[q] - (STAGE ? e0 : 0);
+  if constexpr (FOLD)
+    for (int q = threadIdx.x; q < m1; q += blockDim.x) s_top[q] = L.etop[(size_t)mem * m1 + q];
   const int* erc = g.sp_erc;
   const double* eval = g.sp_eval;
   if (STAGE) {
@@ -299,7 +364,12 @@ __global__ void __launch_bounds__(256) lmi_schur_sparse(LmiGroup g, Arena ar, Sp
   }
   const double* W = Wg;
   if (SMALL) {
-    for (int q = threadIdx.x; q < nn; q += blockDim.x) sW[q] = Wg[q];
+    if constexpr (FOLD) {  // (the projection of lmi_fold_project, made on the way into LDS)
+      const int n0 = n / g.herm_d;
+      for (int q = threadIdx.x; q < nn; q += blockDim.x) sW[q] = FoldProjected(Wg, n, n0, g.herm_d, q % n, q / n);
+    } else {
+      for (int q = threadIdx.x; q < nn; q += blockDim.x) sW[q] = Wg[q];
+    }
     W = sW;
   }
   __syncthreads();
@@ -356,7 +426,9 @@ __global__ void __launch_bounds__(256) lmi_schur_sparse(LmiGroup g, Arena ar, Sp
     const int gpb = blockDim.x / LPV;
     for (int i = blockIdx.y * gpb + threadIdx.x / LPV; i < lists; i += gridDim.y * gpb) {
       double aw = 0, aq = 0;
-      for (int e = s_ptr[i] + (threadIdx.x % LPV); e < s_ptr[i + 1]; e += LPV) {
+      int e1 = s_ptr[i + 1];
+      if constexpr (FOLD) e1 = s_ptr[i] + s_top[i];
+      for (int e = s_ptr[i] + (threadIdx.x % LPV); e < e1; e += LPV) {
         const int rc = erc[e], r = rc & 0xffff, c = rc >> 16;
         const double a = eval[e];
         aw = fma(a, W[c + (size_t)r * n], aw);
@@ -370,10 +442,10 @@ __global__ void __launch_bounds__(256) lmi_schur_sparse(LmiGroup g, Arena ar, Sp
       if (cdense) aq = GroupSum<LPV>(aq);
       if (threadIdx.x % LPV == 0) {
         if (i < m) {
-          ar.AWc[ar.r_off[id] + i] = aw * osc;
-          if (cdense) ar.AQcc[ar.r_off[id] + i] = aq * osc;
+          ar.AWc[ar.r_off[id] + i] = aw * lsc;
+          if (cdense) ar.AQcc[ar.r_off[id] + i] = aq * lsc;
         } else {
-          ar.sc[2 * id] = aw * osc;
+          ar.sc[2 * id] = aw * lsc;
         }
       }
     }
@@ -394,14 +466,18 @@ __global__ void __launch_bounds__(256) lmi_schur_sparse(LmiGroup g, Arena ar, Sp
       const int ij = ij_next, i = ij & 0xffff, j = ij >> 16;
       ij_next = t + ngrp < t1 ? g.sp_pairs[t + ngrp] : 0;  // (asked for a pass ahead: off the chain)
       const int bi = s_ptr[i], bj = s_ptr[j];
-      const double s = PairSum<LPP>(erc, eval, W, n, bi, s_ptr[i + 1] - bi, bj, s_ptr[j + 1] - bj, sub);
+      double s;
+      if constexpr (FOLD)
+        s = PairSum<LPP, true>(erc, eval, W, n, bi, s_ptr[i + 1] - bi, bj, s_ptr[j + 1] - bj, sub, s_top[i], s_top[j]);
+      else
+        s = PairSum<LPP>(erc, eval, W, n, bi, s_ptr[i + 1] - bi, bj, s_ptr[j + 1] - bj, sub);
       if (sub == 0) {
         if (i < m)
-          G[i + (size_t)j * m] = s * osc;
+          G[i + (size_t)j * m] = s * lsc;
         else if (j < m)
-          ar.AQcc[ar.r_off[id] + j] = s * osc;
+          ar.AQcc[ar.r_off[id] + j] = s * lsc;
         else
-          ar.sc[2 * id + 1] = s * osc;
+          ar.sc[2 * id + 1] = s * lsc;
       }
     }
   }
@@ -412,11 +488,12 @@ __global__ void __launch_bounds__(256) lmi_schur_sparse(LmiGroup g, Arena ar, Sp
 #endif
 }
 
-// bytes of LDS: matrices, staged entries, list pointers (+ block-reduction scratch)
-inline size_t LmiSparseLds(int n, int m, bool small, bool cdense, int emax_staged) {
+// bytes of LDS: matrices, staged entries, list pointers (+ block-reduction scratch), the top counts of a folded group
+inline size_t LmiSparseLds(int n, int m, bool small, bool cdense, int emax_staged, bool fold = false) {
   size_t b = small ? sizeof(double) * (cdense ? 4 : 1) * (size_t)n * n : 0;
   b += (size_t)emax_staged * 12;
   b += sizeof(int) * (size_t)((m + 1 + 3) & ~1) + sizeof(double) * 16;
+  if (fold) b += sizeof(int) * (size_t)((m + 1 + 1) & ~1);
   return b;
 }
 

@@ -186,7 +186,7 @@ static void MeasureNonzeros(ConstraintRec* c, ConeShape* s) {
 // cxk_finalize fails with); constraints of one shape on one route form a group, numbered by first appearance.
 int GroupConstraints(cxk_context* ctx, const FinalizeSwitches& sw) {
   const int K = (int)ctx->cons.size();
-  std::map<std::tuple<int, int, int, int, ConeRoute, bool, bool, int, bool>, int> gmap;
+  std::map<std::tuple<int, int, int, int, ConeRoute, bool, bool, int, bool, bool>, int> gmap;
   ctx->groups.clear();
   ctx->sparse_soc_setup_ms = 0;
   // what the context was told (-1 / -2: nothing) goes in front of the environment's word
@@ -197,10 +197,12 @@ int GroupConstraints(cxk_context* ctx, const FinalizeSwitches& sw) {
   if (ctx->sparse_linear != -2) modes.sparse_linear = ctx->sparse_linear;
   if (ctx->sparse_soc != -2) modes.sparse_soc = ctx->sparse_soc;
   if (ctx->sparse_affine != -2) modes.sparse_affine = ctx->sparse_affine;
+  if (ctx->sparse_fold != -2) modes.sparse_fold = ctx->sparse_fold;
   for (int i = 0; i < K; i++) {
     ConstraintRec& c = ctx->cons[i];
     c.route = ConeRoute::kStatic;
     c.entries.sparse_affine = false;
+    c.entries.fold = false;
     if (!ctx->owned[i]) continue;
     ConeShape s{c.type, c.n, c.m, c.herm_d, c.symmetric, c.csr_only, c.factors.given, c.type == CXK_QUAD && !c.Q.empty()};
     const int sparse_mode = c.type == CXK_LINEAR ? modes.sparse_linear : c.type == CXK_SOC ? modes.sparse_soc : 0;
@@ -215,7 +217,10 @@ int GroupConstraints(cxk_context* ctx, const FinalizeSwitches& sw) {
     if (c.route == ConeRoute::kLmiSparse)
       c.entries.sparse_affine = LmiTakesSparseAffine(c, modes.sparse_affine != -2 ? modes.sparse_affine : c.entries.affine_default,
                                              modes.sparse_affine_min_ratio);
-    const auto key = std::make_tuple(c.type, c.n, c.m, c.herm_d, c.route, literal, s.has_q, f_R, c.entries.sparse_affine);
+    // (likewise the folded sums of a Hermitian constraint over C or H: the real one, d = 1, has nothing to fold)
+    if (c.route == ConeRoute::kLmiSparse && c.herm_d > 1)
+      c.entries.fold = (modes.sparse_fold != -2 ? modes.sparse_fold : c.entries.fold_default) != 0;
+    const auto key = std::make_tuple(c.type, c.n, c.m, c.herm_d, c.route, literal, s.has_q, f_R, c.entries.sparse_affine, c.entries.fold);
     auto it = gmap.find(key);
     if (it == gmap.end()) {
       it = gmap.emplace(key, (int)ctx->groups.size()).first;
@@ -230,6 +235,7 @@ int GroupConstraints(cxk_context* ctx, const FinalizeSwitches& sw) {
       g.quad.has_q = s.has_q;
       g.lmi.f.R = f_R;
       g.lmi.sa.on = c.entries.sparse_affine;
+      g.lmi.sp.fold = c.entries.fold;
     }
     c.group = it->second;
     c.member = (int)ctx->groups[it->second].ids.size();

@@ -111,6 +111,7 @@ static FinalizeSwitches ReadFinalizeSwitches() {
   if ((v = getenv("CXK_SPARSE_SOC_MIN_RATIO")) && v[0] != '\0') sw.modes.sparse_soc_min_ratio = std::max(0.0, atof(v));
   if ((v = getenv("CXK_SPARSE_AFFINE")) && v[0] != '\0') sw.modes.sparse_affine = std::max(-1, std::min(1, atoi(v)));
   if ((v = getenv("CXK_SPARSE_AFFINE_MIN_RATIO")) && v[0] != '\0') sw.modes.sparse_affine_min_ratio = std::max(0.0, atof(v));
+  if ((v = getenv("CXK_SPARSE_FOLD")) && v[0] != '\0') sw.modes.sparse_fold = atoi(v) != 0;
   if ((v = getenv("CXK_WIDE_SPECTRUM")) && v[0] != '\0') sw.wide_spectrum = std::max(-1, std::min(1, atoi(v)));
   if ((v = getenv("CXK_WIDE_REDUCE_MIN_ORDER")) && v[0] != '\0') sw.wide_reduce_min_order = std::max(0, atoi(v));
   return sw;
@@ -251,7 +252,7 @@ static int FinalizeImpl(cxk_context* ctx) {
   for (const ConstraintRec& c : ctx->cons)
     if (c.type == CXK_LMI && c.csr_only) {
       ConeShape s;
-      s.type = c.type, s.n = c.n, s.m = c.m, s.csr_only = true;
+      s.type = c.type, s.n = c.n, s.m = c.m, s.herm_d = c.herm_d, s.csr_only = true;
       const RouteChoice choice = Choose(s, sw.modes);
       CXK_DEMAND(!choice.refusal, choice.refusal);
     }
@@ -499,6 +500,79 @@ int cxk_add_hermitian(cxk_context* ctx, int n, int d, int m, const double* A, co
   r.C.resize(NN);
   for (int i = 0; i < m; i++) EmbedPlanes(d, n, A + (size_t)i * d * nn, r.A.data() + (size_t)i * NN);
   EmbedPlanes(d, n, C, r.C.data());
+  return AddConstraint(ctx, std::move(r), vars);
+}
+
+int cxk_add_hermitian_coo(cxk_context* ctx, int n, int d, int m, const int* ptr, const int* row, const int* col,
+                          const double* val, const int* vars) {
+  if (!ctx) return -1;
+  auto refuse = [ctx](const std::string& msg) {
+    ctx->err = "cxk_add_hermitian_coo: " + msg;
+    return -1;
+  };
+  if (n < 1 || m < 0) return refuse("n is at least 1 and m at least 0");
+  if (d == 8) return refuse("hyper-complex dimension 8: the octonions have no real representation, entries are for d = 1, 2, 4");
+  if (d != 1 && d != 2 && d != 4) return refuse("the hyper-complex dimension is 1, 2 or 4");
+  if (!ptr) return refuse("ptr is null");
+  // (before anything of size d n x d n is touched)
+  if ((int64_t)d * n > kSparseLmiMaxIndex || m > kSparseLmiMaxIndex)
+    return refuse("d n or m is above " + std::to_string(kSparseLmiMaxIndex) +
+                  " (the entry table packs row | col << 16 and the pair table i | j << 16 into ints that the kernels "
+                  "unpack with signed shifts)");
+  if (ptr[0] != 0) return refuse("ptr[0] is not 0");
+  for (int i = 0; i <= m; i++)
+    if (ptr[i + 1] < ptr[i]) return refuse("ptr decreases");
+  if (ptr[m + 1] > 0 && (!row || !col || !val)) return refuse("row, col or val is null");
+  ConstraintRec r;
+  r.type = CXK_LMI;
+  r.herm_d = d;
+  r.n = d * n;
+  r.m = m;
+  r.csr_only = true;
+  r.entries.fold_default = 1;
+  r.entries.ptr.assign((size_t)m + 2, 0);
+  std::vector<int> seen;                     // the positions of one list, both triangles
+  std::vector<std::pair<int, double>> list;  // (row | col << 16, value) of one real representation
+  for (int i = 0; i <= m; i++) {
+    seen.clear();
+    list.clear();
+    for (int s = ptr[i]; s < ptr[i + 1]; s++) {
+      const int rs = row[s], cs = col[s];
+      const double* v = val + (size_t)d * s;
+      if (rs < 0 || rs >= n || cs < 0 || cs >= n) return refuse("an index is outside [0, n)");
+      if (rs < cs) return refuse("an entry lies above the diagonal (row < col): the lower triangle is given");
+      for (int p = 0; p < d; p++)
+        if (!std::isfinite(v[p])) return refuse("a value is not finite");
+      for (int p = 1; p < d; p++)
+        if (rs == cs && v[p] != 0.0)
+          return refuse("a diagonal entry has a nonzero plane beyond the first (the diagonal of a Hermitian matrix is real)");
+      seen.push_back(rs | (cs << 16));
+      // block (k, j) of L(X) is kHcSign[k ^ j][j] X_{k ^ j}; the mirrored entry is the conjugate: X_p[c,r] = -X_p[r,c], p >= 1
+      for (int p = 0; p < d; p++) {
+        if (v[p] == 0.0) continue;  // (a zero plane makes no real entry; an entry of zero planes is dropped)
+        for (int j = 0; j < d; j++) {
+          const int k = p ^ j;
+          const double a = kHcSign[p][j] * v[p];
+          list.emplace_back((k * n + rs) | ((j * n + cs) << 16), a);
+          if (rs != cs) list.emplace_back((k * n + cs) | ((j * n + rs) << 16), p ? -a : a);
+        }
+      }
+    }
+    std::sort(seen.begin(), seen.end());
+    for (size_t s = 1; s < seen.size(); s++)
+      if (seen[s] == seen[s - 1]) return refuse("a list names a position twice");
+    // by column, then row: the packed word orders exactly so (distinct positions give distinct real entries)
+    std::sort(list.begin(), list.end(), [](const std::pair<int, double>& a, const std::pair<int, double>& b) { return a.first < b.first; });
+    if (r.entries.rc.size() + list.size() > (size_t)INT_MAX) return refuse("more than 2^31 nonzeros");
+    for (const auto& e : list) {
+      r.entries.rc.push_back(e.first);
+      r.entries.val.push_back(e.second);
+    }
+    r.entries.ptr[(size_t)i + 1] = (int)r.entries.rc.size();
+  }
+  r.C.assign((size_t)r.n * r.n, 0.0);
+  for (int e = r.entries.ptr[m]; e < r.entries.ptr[m + 1]; e++)
+    r.C[(size_t)(r.entries.rc[e] & 0xffff) + (size_t)(r.entries.rc[e] >> 16) * r.n] = r.entries.val[e];
   return AddConstraint(ctx, std::move(r), vars);
 }
 
@@ -764,6 +838,20 @@ int cxk_count_sparse_affine(const cxk_context* ctx) {
   if (!ctx || !ctx->finalized) return -1;
   int k = 0;
   for (size_t i = 0; i < ctx->cons.size(); i++) k += ctx->owned[i] && ctx->cons[i].route == ConeRoute::kLmiSparse && ctx->cons[i].entries.sparse_affine;
+  return k;
+}
+
+int cxk_set_sparse_fold(cxk_context* ctx, int mode) {
+  if (!ctx) return CXK_FAILURE;
+  CXK_DEMAND(!ctx->finalized, "cxk_set_sparse_fold: the context is finalized (the choice is made by cxk_finalize)");
+  CXK_DEMAND(mode == 0 || mode == 1, "cxk_set_sparse_fold: the mode is 0 (never) or 1 (every sparse Hermitian matrix inequality over C or H)");
+  ctx->sparse_fold = mode;
+  return CXK_SUCCESS;
+}
+int cxk_count_sparse_fold(const cxk_context* ctx) {
+  if (!ctx || !ctx->finalized) return -1;
+  int k = 0;
+  for (size_t i = 0; i < ctx->cons.size(); i++) k += ctx->owned[i] && ctx->cons[i].route == ConeRoute::kLmiSparse && ctx->cons[i].entries.fold;
   return k;
 }
 
@@ -1706,6 +1794,26 @@ int cxk_assembly_work(const cxk_context* ctx, double* bytes, double* flops) {
       }
       F += 4 * n * n * R + n * R * (R + 1) + 4 * n * n * n + 4 * n * n + 3 * terms + 2 * n * R + 2 * R;
       B += 8.0 * (n * R + 2 * n * n + 4 * n * R + n * R + R * (R + 1) / 2 + 4 * n * n + m * (m + 1) / 2 + 2 * m + R + m);
+      continue;
+    }
+    if (c.csr_only && c.herm_d > 0) {
+      // a Hermitian constraint held by its nonzeros (cxk_add_hermitian_coo): the sums over the entry lists, a pair
+      // (i, j) as first(longer) x full(shorter) -- `first` the top block row of a folded group, else the whole list --
+      // at three flops a term; a C of more than 64 nonzeros leaves the pair sums for W C W (4 n^3) and sums over n^2.
+      // Bytes: the entries (12 B each), W, G's triangle and the three vectors
+      const bool fold = c.entries.fold;
+      const int lists = c.entries.ptr[c.m + 1] - c.entries.ptr[c.m] > 64 ? c.m : c.m + 1;
+      double terms = 0, firsts = 0;
+      for (int a = 0; a < lists; a++) {
+        const double na = c.entries.ptr[a + 1] - c.entries.ptr[a];
+        firsts += fold ? na / c.herm_d : na;
+        for (int b = 0; b <= a; b++) {
+          const double nb = c.entries.ptr[b + 1] - c.entries.ptr[b];
+          terms += (fold ? std::max(na, nb) / c.herm_d : std::max(na, nb)) * std::min(na, nb);
+        }
+      }
+      F += 3 * terms + 4 * firsts + (lists == c.m ? 4 * n * n * n + 4 * n * n : 0);
+      B += 12.0 * c.entries.ptr[lists] + 8.0 * ((lists == c.m ? 4 : 1) * n * n + m * (m + 1) / 2 + 2 * m);
       continue;
     }
     // FLOPs = 4 n^3 (m+1) + n^2 (m^2 + 3m + 4) + n m ; bytes = 8 [m n^2 + 2 n^2 + m(m+1)/2 + 2m]

@@ -68,7 +68,8 @@ struct ConstraintRec {
   } factors;
   // CXK_LMI given by its nonzeros (cxk_add_lmi_coo; csr_only is set and A stays empty, C is the n x n square the slack
   // kernels read): list i < m holds A_i, list m holds C, both triangles of each, sorted by column then row -- the order
-  // in which UploadSparseLmi scans a dense matrix -- as rc = row | col << 16 and val from ptr[i] on (m + 2 pointers)
+  // in which UploadSparseLmi scans a dense matrix -- as rc = row | col << 16 and val from ptr[i] on (m + 2 pointers).
+  // cxk_add_hermitian_coo fills the same lists with the nonzeros of the real representations (herm_d set, n = d x order)
   struct Entries {
     std::vector<int> ptr, rc;
     std::vector<double> val;
@@ -77,6 +78,10 @@ struct ConstraintRec {
     // GroupConstraints made of it (members of one group agree)
     int affine_default = 0;
     bool sparse_affine = false;
+    // likewise whether a sparse group of a Hermitian constraint over C or H folds its sums (cxk_set_sparse_fold,
+    // CXK_SPARSE_FOLD): 0 for cxk_add_hermitian, 1 for cxk_add_hermitian_coo; and what GroupConstraints made of it
+    int fold_default = 0;
+    bool fold = false;
   } entries;
 };
 
@@ -123,6 +128,9 @@ struct cxk_context {
   // cxk_set_sparse_affine: -2 the environment's CXK_SPARSE_AFFINE (else every constraint's own default: 0 for
   // cxk_add_lmi / cxk_add_hermitian, -1 for cxk_add_lmi_coo), -1 when it pays, 0 never, 1 every eligible group
   int sparse_affine = -2;
+  // cxk_set_sparse_fold: -2 the environment's CXK_SPARSE_FOLD (else every constraint's own default: 0 for
+  // cxk_add_hermitian, 1 for cxk_add_hermitian_coo), 0 never, 1 every sparse Hermitian group over C or H
+  int sparse_fold = -2;
   std::vector<Group> groups;
   std::vector<int64_t> g_off, r_off;
   std::vector<unsigned char> owned;      // constraint i assembled/updated by this rank

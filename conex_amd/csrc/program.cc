@@ -70,7 +70,8 @@ struct Cone {
   std::vector<double> F, sigma;
   std::vector<int> rank_ptr;
   // kLmi added by CONEX_HIP_AddLMIConstraintFromEntries: the lower triangles of A_v (list v) and of the affine term
-  // (list vars.size()) as e_ptr / e_row / e_col / e_val; `mats` and `affine` stay empty: the matrices are never formed
+  // (list vars.size()) as e_ptr / e_row / e_col / e_val; `mats` and `affine` stay empty: the matrices are never formed.
+  // Added by CONEX_HIP_AddHermitianConstraintFromEntries (`hermitian` set): e_val holds `hyper` planes per entry
   bool from_entries = false;
   std::vector<int> e_ptr, e_row, e_col;
   std::vector<double> e_val;
@@ -93,6 +94,7 @@ struct Program {
   int sparse_linear = -1;       // linear blocks from their nonzeros: -1 by pattern; see CONEX_HIP_SetSparseLinear
   int sparse_soc = 0;           // second-order cones from their nonzeros: 0 none; see CONEX_HIP_SetSparseSoc
   int sparse_affine = -2;       // affine terms of sparse LMIs from their nonzeros: -2 nothing said; see CONEX_HIP_SetSparseAffine
+  int sparse_fold = -2;         // folded sums of sparse Hermitian LMIs: -2 nothing said; see CONEX_HIP_SetSparseFold
   int streamed_quadratic = -1;  // quadratic cones held in HBM: -1 beyond LDS or by size; see CONEX_HIP_SetStreamedQuadratic
   // multi-GPU (one process per GPU, every rank builds the same program): see CONEX_HIP_SetCommunicator
   int shard_rank = 0, shard_world = 1;
@@ -171,6 +173,7 @@ int BuildContext(Program* p) {
   cxk_set_sparse_soc(p->ctx, p->sparse_soc);
   // (nothing said: every constraint keeps the default of the entry point it comes through)
   if (p->sparse_affine != -2) cxk_set_sparse_affine(p->ctx, p->sparse_affine);
+  if (p->sparse_fold != -2) cxk_set_sparse_fold(p->ctx, p->sparse_fold);
   // (likewise no quadratic cone is refused for its size: automatic, where the cxk_* interface defaults to never)
   cxk_set_streamed_quadratic(p->ctx, p->streamed_quadratic);
   if (p->shard_world > 1) {
@@ -197,7 +200,9 @@ int BuildContext(Program* p) {
           break;
         }
         if (c.from_entries) {  // the lists go to the device as they are: nothing of size m n^2 is formed
-          id = cxk_add_lmi_coo(p->ctx, c.order, m, c.e_ptr.data(), c.e_row.data(), c.e_col.data(), c.e_val.data(), c.vars.data());
+          id = c.hermitian ? cxk_add_hermitian_coo(p->ctx, c.order, c.hyper, m, c.e_ptr.data(), c.e_row.data(), c.e_col.data(),
+                                                   c.e_val.data(), c.vars.data())
+                           : cxk_add_lmi_coo(p->ctx, c.order, m, c.e_ptr.data(), c.e_row.data(), c.e_col.data(), c.e_val.data(), c.vars.data());
           CONEX_DEMAND(id >= 0, cxk_last_error(p->ctx));
           break;
         }
@@ -1351,6 +1356,52 @@ int CONEX_HIP_AddLMIConstraintFromEntries(void* x, int n, const int* ptr, const 
   return AddCone(p, std::move(k));
 }
 
+/* not part of conex.h: a HermitianPsdConstraint over R / C / H (d = 1, 2, 4) whose matrices are sparse and given by
+ * their entries: the lists as for CONEX_HIP_AddLMIConstraintFromEntries (list v < num_vars holds A_v, list num_vars the
+ * affine term, row >= col), the value of entry e being the d planes val[d e .. d e + d - 1] (d = 2: the memory of a
+ * complex double); the matrices are the Hermitian completion of the lower triangle, so a diagonal entry is real (its
+ * planes 1 .. d - 1 are zero).  Neither the matrices nor their real representations are formed
+ * (cxk_add_hermitian_coo).  CONEX_UpdateLinearOperator and CONEX_UpdateAffineTerm fail on such a constraint;
+ * CONEX_GetDualVariable gives the real plane, as for every Hermitian constraint.  Returns the constraint id, -1 on
+ * invalid arguments (a position named twice in a list is found when the program is initialized). */
+int CONEX_HIP_AddHermitianConstraintFromEntries(void* x, int n, int d, const int* ptr, const int* row, const int* col,
+                                                const double* val, int num_vars, const long* vars) {
+  Program* p = static_cast<Program*>(x);
+  if (!p || p->magic != 0xC0DEC0DEu || n < 1 || num_vars < 0 || num_vars > 32767 || !ptr) return -1;
+  if (d != 1 && d != 2 && d != 4) return -1;
+  if ((long long)d * n > 32767) return -1;
+  if (vars ? false : num_vars != p->num_vars) return -1;
+  if (ptr[0] != 0) return -1;
+  for (int v = 0; v <= num_vars; v++)
+    if (ptr[v + 1] < ptr[v]) return -1;
+  const int nz = ptr[num_vars + 1];
+  if (nz > 0 && (!row || !col || !val)) return -1;
+  for (int e = 0; e < nz; e++) {
+    if (col[e] < 0 || row[e] < col[e] || row[e] >= n) return -1;
+    for (int pl = 0; pl < d; pl++)
+      if (!std::isfinite(val[(size_t)d * e + pl]) || (pl > 0 && row[e] == col[e] && val[(size_t)d * e + pl] != 0.0)) return -1;
+  }
+  Cone k;
+  k.kind = kLmi;
+  k.order = n;
+  k.hyper = d;
+  k.hermitian = true;
+  k.from_entries = true;
+  k.e_ptr.assign(ptr, ptr + num_vars + 2);
+  k.e_row.assign(row, row + nz);
+  k.e_col.assign(col, col + nz);
+  k.e_val.assign(val, val + (size_t)d * nz);
+  if (vars) {
+    for (int i = 0; i < num_vars; i++) {
+      if (vars[i] < 0 || vars[i] >= p->num_vars) return -1;
+      k.vars.push_back((int)vars[i]);
+    }
+  } else {
+    k.vars = AllVars(*p);
+  }
+  return AddCone(p, std::move(k));
+}
+
 /* not part of conex.h: a HermitianPsdConstraint over R / C / H (d = 1, 2, 4) whose matrices are low-rank and given by
  * their factors,  A_v = sum_k sigma[k] f_k f_k^*,  k = rank_ptr[v] .. rank_ptr[v + 1] - 1,  v < num_vars,
  * f_k the hyper-complex columns of F (d planes of n x R column-major, R = rank_ptr[num_vars]); sigma NULL = all +1; c
@@ -1537,6 +1588,22 @@ int CONEX_HIP_SetSparseAffine(void* x, int mode) {
 int CONEX_HIP_CountSparseAffine(void* x) {
   Program* p = static_cast<Program*>(x);
   return p && p->ctx ? cxk_count_sparse_affine(p->ctx) : -1;
+}
+
+/* not part of conex.h: whether sparse Hermitian matrix inequalities over C or H sum over the top block row of their
+ * real representations (conex_kkt_hip.h, cxk_set_sparse_fold): 1 every one, 0 none.  Without a call a constraint added
+ * by CONEX_HIP_AddHermitianConstraintFromEntries folds and every other one does not. */
+int CONEX_HIP_SetSparseFold(void* x, int mode) {
+  Program* p = static_cast<Program*>(x);
+  if (!p || (mode != 0 && mode != 1)) return CONEX_FAILURE;
+  p->sparse_fold = mode;
+  p->dirty = true;
+  return CONEX_SUCCESS;
+}
+/* matrix inequalities of the program's device context on the folded kernels (cxk_count_sparse_fold); -1 before a first solve */
+int CONEX_HIP_CountSparseFold(void* x) {
+  Program* p = static_cast<Program*>(x);
+  return p && p->ctx ? cxk_count_sparse_fold(p->ctx) : -1;
 }
 
 /* not part of conex.h: which quadratic cones are held in HBM and run on the streamed kernels (conex_kkt_hip.h,

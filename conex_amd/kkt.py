@@ -148,6 +148,9 @@ _SIGNATURES = {
     "cxk_add_lmi_coo": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, c_double_p, c_int_p]),
     "cxk_set_sparse_affine": (C.c_int, [C.c_void_p, C.c_int]),
     "cxk_count_sparse_affine": (C.c_int, [C.c_void_p]),
+    "cxk_add_hermitian_coo": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, c_double_p, c_int_p]),
+    "cxk_set_sparse_fold": (C.c_int, [C.c_void_p, C.c_int]),
+    "cxk_count_sparse_fold": (C.c_int, [C.c_void_p]),
     "cxk_count_tiled_linear": (C.c_int, [C.c_void_p]),
     "cxk_fused_tree_timed_out": (C.c_int, [C.c_void_p]),
     "cxk_debug_force_fused_timeout": (C.c_int, [C.c_void_p]),
@@ -341,6 +344,33 @@ class KktContext:
         r = self.L.cxk_add_hermitian(self.h, n, d, m, _dp(a), _dp(c), vp)
         if r >= 0:
             self.cons.append(("herm", n, m, d))
+        return r
+
+    def add_hermitian_coo(self, n, d, ptr, row, col, val, vars_=None):
+        """The constraint of add_hermitian, of order n over R / C / H (d = 1, 2, 4), by the entries of the lower
+        triangles: the lists as for add_lmi_coo; val is (nnz, d) real planes, or a complex array for d = 2.  The upper
+        triangle is the conjugate.  Neither the matrices nor their real representations are formed, and the constraint
+        takes the sparse route only."""
+        pt = np.ascontiguousarray(ptr, dtype=np.int32)
+        rw = np.ascontiguousarray(row, dtype=np.int32)
+        cl = np.ascontiguousarray(col, dtype=np.int32)
+        vl = np.asarray(val)
+        if np.iscomplexobj(vl):
+            if int(d) != 2 or vl.ndim != 1:
+                raise ValueError("add_hermitian_coo: a complex val is one number per entry, for d = 2")
+            vl = np.stack([vl.real, vl.imag], axis=1)
+        vl = np.ascontiguousarray(vl, dtype=np.float64)
+        if vl.ndim == 1 and int(d) == 1:
+            vl = vl.reshape(-1, 1)
+        keep, vp = self._vars(vars_)
+        m = self.num_vars if vars_ is None else len(keep)
+        if vl.ndim != 2 or vl.shape[1] != int(d):
+            raise ValueError("add_hermitian_coo: val is (nnz, d) planes")
+        if len(pt) != m + 2 or not (len(rw) == len(cl) == len(vl)) or pt[-1] > len(vl):
+            raise ValueError("add_hermitian_coo: ptr has m + 2 entries and points into row / col / val of equal length")
+        r = self.L.cxk_add_hermitian_coo(self.h, int(n), int(d), m, _ip(pt), _ip(rw), _ip(cl), _dp(vl), vp)
+        if r >= 0:
+            self.cons.append(("herm", int(n), m, int(d)))
         return r
 
     def add_hermitian_factored(self, F, rank_ptr, sigma, Cm, vars_=None):
@@ -933,6 +963,16 @@ class KktContext:
     def count_sparse_affine(self):
         """Constraints this context owns whose affine term is evaluated from its nonzeros."""
         return self.L.cxk_count_sparse_affine(self.h)
+
+    def set_sparse_fold(self, mode=1):
+        """The sums of sparse Hermitian matrix inequalities over C or H: 1 over the top block row of the real
+        representations (a d-th of the terms), 0 over all of it (before initialize; default: CXK_SPARSE_FOLD in the
+        environment, else 0 for add_hermitian and 1 for add_hermitian_coo)."""
+        self._check(self.L.cxk_set_sparse_fold(self.h, int(mode)), "cxk_set_sparse_fold")
+
+    def count_sparse_fold(self):
+        """Constraints this context owns that run on the folded sparse kernels."""
+        return self.L.cxk_count_sparse_fold(self.h)
 
     def set_wide_spectrum(self, mode=1):
         """The Lanczos run of large-order matrix inequalities spread over the chip: 1 every large-order group, 0 none

@@ -299,6 +299,47 @@ class Conex:
         if self._L.CONEX_HIP_SetSparseAffine(self.a, int(mode)) != 0:
             raise ConexError("Invalid mode.")
 
+    def AddHermitianMatrixInequalityFromEntries(self, n, d, ptr, row, col, val, variables=None):
+        """c - sum_i y_i A_i positive semidefinite of order n over R / C / H (d = 1, 2, 4) with sparse Hermitian A_i and c
+        given by the entries of their lower triangles and never expanded (CONEX_HIP_AddHermitianConstraintFromEntries,
+        an extra next to the reference's surface).  The lists are those of AddLinearMatrixInequalityFromEntries; val is
+        (nnz, d) real planes, or a complex array for d = 2; the upper triangle is the conjugate, so diagonal entries are
+        real.  As for NewLinearMatrixInequality, the dual variable is the real plane and ComputeErrors does not cover
+        the constraint.  UpdateLinearOperator and UpdateAffineTerm fail on it.  Returns the constraint id."""
+        pt = np.ascontiguousarray(np.asarray(ptr).ravel(), dtype=np.int32)
+        rw = np.ascontiguousarray(np.asarray(row).ravel(), dtype=np.int32)
+        cl = np.ascontiguousarray(np.asarray(col).ravel(), dtype=np.int32)
+        vl = np.asarray(val)
+        if np.iscomplexobj(vl):
+            if int(d) != 2:
+                raise ConexError("Invalid LMI")
+            vl = np.stack([vl.real.ravel(), vl.imag.ravel()], axis=1)
+        vl = _f64(np.asarray(vl, dtype=np.float64).reshape(len(rw), -1))
+        v = None if variables is None else np.ascontiguousarray(np.asarray(variables).ravel(), dtype=np.int64)
+        m = self.m if v is None else len(v)
+        if (n < 1 or d not in (1, 2, 4) or vl.shape != (len(rw), int(d)) or len(pt) != m + 2 or len(rw) != len(cl)
+                or pt[-1] > len(rw) or np.any(np.diff(pt) < 0)):
+            raise ConexError("Invalid LMI")
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+        cid = self._L.CONEX_HIP_AddHermitianConstraintFromEntries(
+            self.a, int(n), int(d), ip(pt), ip(rw), ip(cl), capi.dp(vl), m,
+            None if v is None else v.ctypes.data_as(C.POINTER(C.c_long)))
+        if cid < 0:
+            raise ConexError("Failed to add constraint.")
+        c = np.zeros((int(n), int(n)))  # (the real plane, as the other Hermitian builders keep)
+        cs = slice(pt[m], pt[m + 1])
+        c[rw[cs], cl[cs]] = vl[cs, 0]
+        c[cl[cs], rw[cs]] = vl[cs, 0]
+        self.c.append(c)
+        self.num_constraints += 1
+        return cid
+
+    def SetSparseFold(self, mode):
+        """Whether sparse Hermitian matrix inequalities over C or H sum over the top block row of their real
+        representations: 1 every one, 0 none (CONEX_HIP_SetSparseFold)."""
+        if self._L.CONEX_HIP_SetSparseFold(self.a, int(mode)) != 0:
+            raise ConexError("Invalid mode.")
+
     def AddFactoredHermitianMatrixInequality(self, F, rank_ptr, sigma, c, variables=None):
         """c - sum_i y_i A_i positive semidefinite over R / C / H with low-rank Hermitian A_i = sum_k sigma[k] f_k f_k^*,
         k in rank_ptr[i]:rank_ptr[i + 1], given by its factors and never expanded

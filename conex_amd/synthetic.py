@@ -251,6 +251,64 @@ def maxcut_entries(n, edges_per_node=3, seed=SEED + 9):
     return dict(n=n, m=n, ptr=ptr, row=row, col=col, val=val, cliques=[list(range(n))], num_vars=n, b=-np.ones(n))
 
 
+def hermitian_entries(n, d, m, per_matrix=0, seed=SEED + 11, planes_up_to=64):
+    """One sparse Hermitian matrix inequality of order n over R / C / H (d = 1, 2, 4) in m variables as the entry lists
+    of KktContext.add_hermitian_coo / Conex.AddHermitianMatrixInequalityFromEntries: list i < m holds the lower triangle
+    of A_i, list m that of C = I; val is (nnz, d) planes.
+    per_matrix = 0: the line family, as in relaxations of AC power flow: A_i has one diagonal entry (bus i mod n) and the
+    entries of one line (r, c), r > c: two real diagonal ones and a hyper-complex off-diagonal one.
+    per_matrix > 0: that many random positions of the lower triangle, the first on the diagonal.
+    For n <= planes_up_to the dense planes of the same data come along: A (m, d, n, n), C (d, n, n); else None.
+    b = 1/2 Re tr A_i (dual feasible at I / 2), one clique of all variables."""
+    rng = np.random.default_rng(seed + 1000 * n + 10 * m + d)
+    ptr, row, col, val = [0], [], [], []
+    for i in range(m):
+        ent = {}
+        if per_matrix == 0:
+            k = i % n
+            ent[(k, k)] = np.r_[rng.uniform(0.5, 1.5), np.zeros(d - 1)]
+            if n > 1:
+                r, c = (int(t) for t in rng.choice(n, size=2, replace=False))
+                r, c = max(r, c), min(r, c)
+                for q in (r, c):
+                    ent[(q, q)] = ent.get((q, q), np.zeros(d)) + np.r_[rng.uniform(0.2, 1.0), np.zeros(d - 1)]
+                ent[(r, c)] = rng.uniform(-1.0, 1.0, d)
+        else:
+            k = int(rng.integers(n))
+            ent[(k, k)] = np.r_[rng.uniform(0.5, 1.5), np.zeros(d - 1)]
+            while len(ent) < min(per_matrix, n * (n + 1) // 2):
+                r, c = (int(t) for t in rng.integers(n, size=2))
+                r, c = max(r, c), min(r, c)
+                ent[(r, c)] = np.r_[rng.uniform(-1.0, 1.0), np.zeros(d - 1)] if r == c else rng.uniform(-1.0, 1.0, d)
+        for (r, c), v in sorted(ent.items()):
+            row.append(r), col.append(c), val.append(v)
+        ptr.append(len(row))
+    row += list(range(n))
+    col += list(range(n))
+    val += [np.r_[1.0, np.zeros(d - 1)]] * n
+    ptr.append(len(row))
+    out = dict(n=n, d=d, m=m, ptr=np.array(ptr, np.int32), row=np.array(row, np.int32), col=np.array(col, np.int32),
+               val=np.array(val, np.float64).reshape(-1, d), cliques=[list(range(m))], num_vars=m, A=None, C=None)
+    out["b"] = np.array([0.5 * sum(out["val"][e, 0] for e in range(ptr[i], ptr[i + 1]) if row[e] == col[e]) for i in range(m)])
+    if n <= planes_up_to:
+        out["A"], out["C"] = hermitian_planes_of_entries(n, d, m, out["ptr"], out["row"], out["col"], out["val"])
+    return out
+
+
+def hermitian_planes_of_entries(n, d, m, ptr, row, col, val):
+    """The dense planes A (m, d, n, n) and C (d, n, n) of entry lists as hermitian_entries returns them: the lower
+    triangle as given, the upper its conjugate (plane 0 symmetric, the others skew)."""
+    M = np.zeros((m + 1, d, n, n))
+    for i in range(m + 1):
+        for e in range(ptr[i], ptr[i + 1]):
+            r, c = row[e], col[e]
+            M[i, :, r, c] = val[e]
+            if r != c:
+                M[i, 0, c, r] = val[e, 0]
+                M[i, 1:, c, r] = -val[e, 1:]
+    return M[:m], M[m]
+
+
 def scaling_points(K, n, seed=SEED + 1, scale=0.3):
     """W_c = expm(scale * sym(R)): symmetric positive definite, W != I."""
     rng = np.random.default_rng(seed)

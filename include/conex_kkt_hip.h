@@ -262,6 +262,36 @@ int cxk_add_lmi_coo(cxk_context* ctx, int n, int m, const int* ptr /* m + 2 */, 
 int cxk_set_sparse_affine(cxk_context* ctx, int mode);
 int cxk_count_sparse_affine(const cxk_context* ctx);
 
+/* Hermitian matrix inequalities over R / C / H given by their nonzeros.  cxk_add_hermitian_coo adds the constraint of
+ * cxk_add_hermitian(ctx, n, d, m, A, C, vars), d in {1, 2, 4}, by entries: the lists work as for cxk_add_lmi_coo (list
+ * i < m is A_i, list m is C, row >= col, any order within a list, an empty list is the zero matrix); the value of entry
+ * s is the d planes val[d s .. d s + d - 1] (for d = 2 the memory of a complex double).  The library mirrors with the
+ * conjugate: X_0[c,r] = X_0[r,c], X_p[c,r] = -X_p[r,c] for p >= 1.  An entry whose planes are all zero is dropped, and
+ * a zero plane of a kept entry makes no real entry.  The record is that of cxk_add_hermitian (herm_d = d, order
+ * N = d n) without the dense matrices: its lists hold the nonzeros of the real representations, built directly --
+ * block (k, j) of L(X) is sign[k ^ j][j] X_{k ^ j} (the reference's sign table), at row k n + r, column j n + c --
+ * each sorted by column then row, exactly the lists that the sparse route reads off the dense matrices of
+ * cxk_add_hermitian; and the N x N square of L(C).  Nothing of size m N^2 is allocated on the host or the device.
+ * Getters and setters speak d planes, as for every Hermitian constraint.  Returns -1 (cxk_last_error names the reason,
+ * prefixed "cxk_add_hermitian_coo: ") for n < 1, m < 0, a d that is not 1, 2 or 4 (8: the octonions have no real
+ * representation), null pointers, ptr[0] != 0, a decreasing ptr, an index outside [0, n), row < col, a position named
+ * twice in a list, a plane that is not finite, a diagonal entry with a nonzero plane p >= 1, and d n or m above 32767.
+ * Such a constraint can only take the sparse route: with CXK_SPARSE_LMI=0 in force cxk_finalize refuses it by name.
+ * The folded sums (kernels_lmi_sparse.hip.h): for a real representation M, tr M / d is the trace of its top-left
+ * n x n block, so tr(L(A_i) W L(A_j) W) / d, tr(L(A_i) W) / d and tr(L(A_i) W C W) / d need only the entries of L(A_i)
+ * in its top block row, 1 / d of them: a folded group runs every sum over a first list over those and multiplies by no
+ * 1 / d.  cxk_set_sparse_fold, before cxk_finalize: mode 1 every sparse Hermitian group with d > 1 folds, 0 none does
+ * (the bits of before).  Without a call: the environment's CXK_SPARSE_FOLD = 0 | 1, else 0 for a constraint added by
+ * cxk_add_hermitian (nothing that ran before changes its kernels or bits) and 1 for one added by
+ * cxk_add_hermitian_coo.  d = 1 never folds.  Constraints that differ in the outcome do not share a group.  Fixed
+ * summation orders, no atomics: two runs give the same bits; the values differ from the unfolded ones by rounding.
+ * cxk_count_sparse_fold: constraints this context owns on the folded kernels (-1 before cxk_finalize; 0 on a host-only
+ * context); cxk_lmi_kernels reports the name of the sparse instance with the suffix " folded" for them. */
+int cxk_add_hermitian_coo(cxk_context* ctx, int n, int d, int m, const int* ptr /* m + 2 */, const int* row,
+                          const int* col, const double* val /* d per entry */, const int* vars);
+int cxk_set_sparse_fold(cxk_context* ctx, int mode);
+int cxk_count_sparse_fold(const cxk_context* ctx);
+
 /* Low-rank matrix inequalities given by their factors (kernels_lmi_factored.hip.h).  cxk_add_lmi_factored adds the
  * constraint of cxk_add_lmi (DenseLMIConstraint semantics, real symmetric) with
  *   A_i = sum_k sigma_k f_k f_k',  k = rank_ptr[i] .. rank_ptr[i + 1] - 1,
@@ -646,7 +676,9 @@ int cxk_count_lmi_kernel(const cxk_context* ctx, int which);
  * the same functions.  Fails for a constraint of another type, one not owned by this rank, or before
  * initialize.  One instance is no row of that list because it runs only where it was asked for: the Schur stage of
  * a sparse LMI whose affine term is evaluated from its nonzeros (cxk_set_sparse_affine) reports the code
- * cxk_lmi_kernel_count() + 1, which cxk_lmi_kernel_name names "lmi_schur_sparse hbm sparse-C". */
+ * cxk_lmi_kernel_count() + 1, which cxk_lmi_kernel_name names "lmi_schur_sparse hbm sparse-C".  Likewise
+ * the folded forms of the five sparse instances (cxk_set_sparse_fold): codes cxk_lmi_kernel_count() + 2 .. + 6, named
+ * as the instance with the suffix " folded". */
 enum {
   CXK_LMI_STAGE_SCHUR = 0,   /* Schur complement assembly */
   CXK_LMI_STAGE_PREPARE = 1, /* PrepareStep */
