@@ -69,6 +69,8 @@ def api():
         # not in conex.h (the reference reaches these cones through its C++ API only)
         "CONEX_HIP_AddQuadraticConstraint": (ci, [vp, c_double_p, ci, c_double_p, ci, ci, c_double_p, ci,
                                                   C.POINTER(C.c_long), ci]),
+        "CONEX_HIP_AddStructuredQuadraticConstraint": (ci, [vp, ci, ip, ip, c_double_p, ci, c_double_p, c_double_p,
+                                                            c_double_p, ci, ci, c_double_p, ci, C.POINTER(C.c_long), ci]),
         "CONEX_HIP_AddFactoredLMIConstraint": (ci, [vp, ci, c_double_p, ci, c_double_p, ip, ci, c_double_p,
                                                     C.POINTER(C.c_long)]),
         "CONEX_HIP_AddFactoredHermitianConstraint": (ci, [vp, ci, ci, c_double_p, ci, c_double_p, ip, ci, c_double_p,

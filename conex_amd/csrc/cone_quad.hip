@@ -1,11 +1,11 @@
 // Quadratic cones on their two routes (kQuadLds, kQuadStreamed): the views, the stages of cxk_finalize and every
-// launch.  Owns the kernels of kernels_quad / _quad_stream; the slack of the streamed route is the second-order
+// launch.  Owns the kernels of kernels_quad / _quad_stream / _quad_structured; the streamed route's slack is the second-order
 // cones' kernel (cone_soc.hip: LaunchSocStreamSlack), the scaling point's identity the vector cones' (cone_linear.hip).
 // The family's state is Group::quad (cone_state.h).
 #include "cone_units.h"
 #include "kernels_gemm.hip.h"
 #include "kernels_quad.hip.h"
-#include "kernels_quad_stream.hip.h"
+#include "kernels_quad_structured.hip.h"  // (on top of kernels_quad_stream.hip.h, which it includes)
 
 namespace cxk_host {
 
@@ -65,6 +65,7 @@ QuadStreamGroup MakeQuadStream(Group& g) {
   d.m = g.m;
   d.count = static_cast<int>(cnt);
   d.splits = g.quad.splits;
+  d.q_form = g.quad.sq.on ? kQuadQStructured : g.quad.has_q ? kQuadQDense : kQuadQIdentity;  // (structured: Q.p is null)
   d.A = g.A.p;
   d.c = g.C.p;
   d.Q = g.quad.has_q ? g.quad.Q.p : nullptr;
@@ -87,8 +88,7 @@ QuadStreamGroup MakeQuadStream(Group& g) {
   return d;
 }
 size_t QuadStreamVecDoubles(size_t cnt, size_t n, size_t m) { return cnt * (4 * n + (n + 1) + 2 * m + 8 + 1); }
-// A group of streamed quadratic cones: Q as it is, the work space, and the constants (Q c1, c1' Q c1, A_gram) on the
-// device (QuadStreamConstants).
+// A group of streamed quadratic cones with a dense Q or none: Q as it is, the work space, the constants (QuadStreamConstants).
 int UploadQuadStream(cxk_context* ctx, Group& g, const FinalizeSwitches& sw) {
   const size_t cnt = g.ids.size();
   const size_t n = (size_t)g.n, m = (size_t)g.m, tiles = (n + kQuadStreamRowTile - 1) / kQuadStreamRowTile;
@@ -127,10 +127,10 @@ hipError_t RaiseQuadLdsLimits() {
 }
 
 // One pass over Q of a group of streamed quadratic cones: out_r = Q x_r for the R vectors of `x` (partials per
-// column split; QuadStreamQx adds them).  Nothing to do where Q is the identity.
+// column split; QuadStreamQx adds them).  Nothing to do where Q is the identity; its parts' own pass where Q is held by them.
 template <int R>
-hipError_t LaunchQuadStreamQmv(const QuadStreamGroup& d, const QuadStreamVecs& x, hipStream_t st) {
-  if (!d.Q) return hipSuccess;
+hipError_t LaunchQuadStreamQmv(Group& g, const QuadStreamGroup& d, const QuadStreamVecs& x, hipStream_t st) {
+  if (d.q_form != kQuadQDense) return d.q_form == kQuadQIdentity ? hipSuccess : LaunchQuadStructuredQmv<R>(g, d, x, st);
   const int tiles = (d.n + kQuadStreamRowTile - 1) / kQuadStreamRowTile;
   quad_stream_qmv<R><<<(unsigned)((size_t)d.count * tiles * d.splits), kQuadStreamBlock, 0, st>>>(d, x, tiles);
   return hipGetLastError();
@@ -151,7 +151,7 @@ void LaunchQuadLdsSchur(Group& g, const Arena& ar, hipStream_t st) {
 hipError_t LaunchQuadStreamSchur(Group& g, const Arena& ar, hipStream_t st) {
   const QuadStreamGroup d = MakeQuadStream(g);
   const int cnt = d.count, m = d.m;
-  hipError_t e = LaunchQuadStreamQmv<1>(d, QuadStreamOne(d.W + 1, (size_t)d.n + 1), st);
+  hipError_t e = LaunchQuadStreamQmv<1>(g, d, QuadStreamOne(d.W + 1, (size_t)d.n + 1), st);
   if (e != hipSuccess) return e;
   quad_stream_schur_vectors<<<cnt, kQuadStreamBlock, 0, st>>>(d);
   if (m > 0) quad_stream_schur_columns<<<(unsigned)((size_t)cnt * m), kQuadStreamBlock, 0, st>>>(d);
@@ -166,7 +166,7 @@ hipError_t LaunchQuadStreamSchur(Group& g, const Arena& ar, hipStream_t st) {
 int QuadStreamConstants(cxk_context* ctx, Group& g) {
   const QuadStreamGroup d = MakeQuadStream(g);
   const int cnt = d.count, n = d.n, m = d.m, len = n + 1;
-  CXK_TRY(LaunchQuadStreamQmv<1>(d, QuadStreamOne(d.c + 1, (size_t)len), ctx->stream));
+  CXK_TRY(LaunchQuadStreamQmv<1>(g, d, QuadStreamOne(d.c + 1, (size_t)len), ctx->stream));
   quad_stream_constants<<<cnt, kQuadStreamBlock, 0, ctx->stream>>>(d);
   CXK_TRY(hipGetLastError());
   DevBuf<double> T;
@@ -213,6 +213,190 @@ int QuadStreamConstants(cxk_context* ctx, Group& g) {
   return CXK_SUCCESS;
 }
 
+// ---- Streamed quadratic cones whose Q = S + F diag(sigma) F' is held by its parts (cxk_add_quadratic_structured; the
+// kernels of kernels_quad_structured.hip.h).  Such a group is a streamed group in everything but the two places that
+// read Q: the pass (LaunchQuadStreamQmv hands it to LaunchQuadStructuredQmv) and A_gram at finalize.
+
+// What those kernels read of the group (UploadQuadStructured allocates it): the products land in d.part as one split.
+QuadStructured MakeQuadStructured(const Group& g, const QuadStreamGroup& d) {
+  QuadStructured q;
+  q.n = g.n;
+  q.count = d.count;
+  q.rank = g.quad.sq.rank;
+  q.segs = g.quad.sq.segs;
+  q.has_s = g.quad.sq.has_s;
+  q.rowptr = g.quad.sq.rowptr.p;
+  q.col = g.quad.sq.col.p;
+  q.val = g.quad.sq.val.p;
+  q.F = g.quad.sq.F.p;
+  q.sigma = g.quad.sq.sigma.p;
+  q.tpart = g.quad.sq.tpart.p;
+  q.part = d.part;
+  return q;
+}
+// The pass out_r = Q x_r: the factor dots (rank > 0), then the rows at the group's lanes.
+template <int R>
+hipError_t LaunchQuadStructuredQmv(Group& g, const QuadStreamGroup& d, const QuadStreamVecs& x, hipStream_t st) {
+  const QuadStructured q = MakeQuadStructured(g, d);
+  const int tiles = (d.n + kQuadStreamRowTile - 1) / kQuadStreamRowTile;
+  const unsigned grid = (unsigned)((size_t)d.count * tiles);
+  if (q.rank > 0) quad_struct_dots<R><<<(unsigned)((size_t)d.count * q.rank * q.segs), kQuadStreamBlock, 0, st>>>(q, x);
+  switch (g.quad.sq.lanes) {
+    case 1: quad_struct_rows<R, 1><<<grid, kQuadStreamBlock, 0, st>>>(q, x, tiles); break;
+    case 8: quad_struct_rows<R, 8><<<grid, kQuadStreamBlock, 0, st>>>(q, x, tiles); break;
+    default: quad_struct_rows<R, 64><<<grid, kQuadStreamBlock, 0, st>>>(q, x, tiles); break;
+  }
+  return hipGetLastError();
+}
+
+// A_gram = A1' Q A1 without forming Q:
+//   T = S A1 (n x m, lives for this call) by quad_struct_sa, A_gram = A1' T;
+//   P = F' A1 (rank x m), Ps = diag(sigma) P, A_gram += P' Ps (beta = 1; 0 without S).
+// The products on the batched GEMM, as the dense form's.
+static int QuadStructuredGram(cxk_context* ctx, Group& g, const QuadStreamGroup& d) {
+  const QuadStructured q = MakeQuadStructured(g, d);
+  const int cnt = d.count, n = d.n, m = d.m, len = n + 1, rank = q.rank;
+  if (m == 0) return CXK_SUCCESS;
+  DevBuf<double> T, P, Ps;
+  const int tiles = (n + kQuadStreamRowTile - 1) / kQuadStreamRowTile, ctiles = (m + kQuadStructColTile - 1) / kQuadStructColTile;
+  if (q.has_s) {
+    CXK_DEMAND((size_t)cnt * tiles * ctiles <= (size_t)INT_MAX,
+               "a group of structured quadratic cones with more than 2^31 row tiles x column tiles is not supported");
+    CXK_TRY(T.alloc((size_t)cnt * n * m));
+    quad_struct_sa<<<(unsigned)((size_t)cnt * tiles * ctiles), kQuadStreamBlock, 0, ctx->stream>>>(q, g.A.p, m, T.p, tiles, ctiles);
+    CXK_TRY(hipGetLastError());
+  }
+  if (rank > 0) {
+    CXK_TRY(P.alloc((size_t)cnt * rank * m));
+    CXK_TRY(Ps.alloc((size_t)cnt * rank * m));
+  }
+  constexpr int kMaxBatch = 65535;  // gridDim.z
+  for (int b0 = 0; b0 < cnt; b0 += kMaxBatch) {
+    const int nb = std::min(kMaxBatch, cnt - b0);
+    const double* A1 = g.A.p + (size_t)b0 * len * m + 1;
+    GemmArgs a{};
+    a.inner = 1;
+    a.alpha = 1.0;
+    a.beta = 0.0;
+    a.splits = 1;
+    if (q.has_s) {  // A_gram = A1' T
+      a.M = a.N = m;
+      a.K = n;
+      a.A = A1;
+      a.lda = len;
+      a.sA1 = (int64_t)len * m;
+      a.B = T.p + (size_t)b0 * n * m;
+      a.ldb = n;
+      a.sB1 = (int64_t)n * m;
+      a.C = g.quad.Gram.p + (size_t)b0 * m * m;
+      a.ldc = m;
+      a.sC1 = (int64_t)m * m;
+      CXK_TRY(LaunchGemm(a, true, false, nb, ctx->stream));
+    }
+    if (rank > 0) {  // P = F' A1
+      a.M = rank;
+      a.N = m;
+      a.K = n;
+      a.A = q.F + (size_t)b0 * n * rank;
+      a.lda = n;
+      a.sA1 = (int64_t)n * rank;
+      a.B = A1;
+      a.ldb = len;
+      a.sB1 = (int64_t)len * m;
+      a.C = P.p + (size_t)b0 * rank * m;
+      a.ldc = rank;
+      a.sC1 = (int64_t)rank * m;
+      CXK_TRY(LaunchGemm(a, true, false, nb, ctx->stream));
+    }
+  }
+  if (rank > 0) {
+    const size_t blocks = ((size_t)cnt * rank * m + kQuadStreamBlock - 1) / kQuadStreamBlock;
+    CXK_DEMAND(blocks <= (size_t)INT_MAX, "a group of structured quadratic cones with more than 2^39 entries of F' A is not supported");
+    quad_struct_scale_rows<<<(unsigned)blocks, kQuadStreamBlock, 0, ctx->stream>>>(q, P.p, m, Ps.p);
+    CXK_TRY(hipGetLastError());
+    for (int b0 = 0; b0 < cnt; b0 += kMaxBatch) {  // A_gram += P' Ps
+      const int nb = std::min(kMaxBatch, cnt - b0);
+      GemmArgs a{};
+      a.inner = 1;
+      a.alpha = 1.0;
+      a.beta = q.has_s ? 1.0 : 0.0;
+      a.splits = 1;
+      a.M = a.N = m;
+      a.K = rank;
+      a.A = P.p + (size_t)b0 * rank * m;
+      a.lda = rank;
+      a.sA1 = (int64_t)rank * m;
+      a.B = Ps.p + (size_t)b0 * rank * m;
+      a.ldb = rank;
+      a.sB1 = (int64_t)rank * m;
+      a.C = g.quad.Gram.p + (size_t)b0 * m * m;
+      a.ldc = m;
+      a.sC1 = (int64_t)m * m;
+      CXK_TRY(LaunchGemm(a, true, false, nb, ctx->stream));
+    }
+  }
+  CXK_TRY(hipStreamSynchronize(ctx->stream));  // (T, P and Ps are released on return)
+  return CXK_SUCCESS;
+}
+
+// A group of structured quadratic cones at cxk_finalize: the members' CSR lists one after the other, each member's row
+// pointers shifted by where its list starts, F and sigma member by member; the streamed route's work space with one
+// split; then the constants on the device: Qc1 and c1' Q c1 by the pass and quad_stream_constants, as the dense form's,
+// and A_gram.  Nothing of n x n, on either side.
+int UploadQuadStructured(cxk_context* ctx, Group& g, const FinalizeSwitches& sw) {
+  const size_t cnt = g.ids.size(), n = (size_t)g.n, m = (size_t)g.m, rank = (size_t)g.quad.sq.rank;
+  const size_t tiles = (n + kQuadStreamRowTile - 1) / kQuadStreamRowTile;
+  QuadState::Structured& q = g.quad.sq;
+  size_t nnz = 0;
+  for (size_t k = 0; k < cnt; k++) nnz += ctx->cons[g.ids[k]].sq.col.size();
+  CXK_DEMAND(nnz <= (size_t)INT_MAX,
+             "a group of structured quadratic cones whose sparse parts have more than 2^31 nonzeros is not supported");
+  g.quad.splits = 1;
+  q.lanes = sw.quad_csr_lanes > 0 ? sw.quad_csr_lanes : QuadCsrLanes((double)nnz, (double)(cnt * n));
+  q.segs = QuadFactorSegments(g.n, (long long)(cnt * rank));
+  CXK_DEMAND(cnt * std::max<size_t>(std::max<size_t>(m, (m * m + kQuadStreamBlock - 1) / kQuadStreamBlock),
+                                    std::max<size_t>(std::max<size_t>(tiles, rank * (size_t)q.segs),
+                                                     (n + 1 + kSocStreamRowTile - 1) / kSocStreamRowTile)) <=
+                 (size_t)INT_MAX,
+             "a group of structured quadratic cones with more than 2^31 columns, row tiles, factor segments or blocks is not supported");
+  if (q.has_s) {
+    std::vector<long long> hp(cnt * (n + 1));
+    std::vector<int> hc(nnz);
+    std::vector<double> hv(nnz);
+    size_t base = 0;
+    for (size_t k = 0; k < cnt; k++) {
+      const ConstraintRec::StructuredQ& c = ctx->cons[g.ids[k]].sq;
+      for (size_t r = 0; r <= n; r++) hp[k * (n + 1) + r] = (long long)base + c.ptr[r];
+      std::copy(c.col.begin(), c.col.end(), hc.begin() + base);
+      std::copy(c.val.begin(), c.val.end(), hv.begin() + base);
+      base += c.col.size();
+    }
+    CXK_TRY(q.rowptr.upload(hp));
+    CXK_TRY(q.col.upload(hc));
+    CXK_TRY(q.val.upload(hv));
+  }
+  if (rank > 0) {
+    std::vector<double> hF(cnt * n * rank), hs(cnt * rank);
+    for (size_t k = 0; k < cnt; k++) {
+      const ConstraintRec::StructuredQ& c = ctx->cons[g.ids[k]].sq;
+      std::copy(c.F.begin(), c.F.end(), hF.begin() + k * n * rank);
+      std::copy(c.sigma.begin(), c.sigma.end(), hs.begin() + k * rank);
+    }
+    CXK_TRY(q.F.upload(hF));
+    CXK_TRY(q.sigma.upload(hs));
+    CXK_TRY(q.tpart.alloc(cnt * 2 * rank * (size_t)q.segs));
+  }
+  CXK_TRY(g.quad.Gram.alloc(m * m * cnt));
+  CXK_TRY(g.quad.S.alloc((n + 1) * cnt));
+  CXK_TRY(g.quad.vec.alloc(QuadStreamVecDoubles(cnt, n, m)));
+  CXK_TRY(g.quad.part.alloc(cnt * 2 * n));
+  const QuadStreamGroup d = MakeQuadStream(g);
+  CXK_TRY(LaunchQuadStreamQmv<1>(g, d, QuadStreamOne(d.c + 1, n + 1), ctx->stream));
+  quad_stream_constants<<<(int)cnt, kQuadStreamBlock, 0, ctx->stream>>>(d);
+  CXK_TRY(hipGetLastError());
+  return QuadStructuredGram(ctx, g, d);
+}
+
 // PrepareStep (MODE 0) or the eigenvalue query (MODE 1) of one group.
 namespace {
 template <int MODE>
@@ -227,9 +411,9 @@ int QuadPrepare(cxk_context* ctx, Group& g, const StepArgs& sa) {
       x.p[0] = d.W + 1;
       x.p[1] = d.ms + 1;
       x.stride[0] = x.stride[1] = (size_t)g.n + 1;
-      CXK_TRY(LaunchQuadStreamQmv<2>(d, x, ctx->stream));
+      CXK_TRY(LaunchQuadStreamQmv<2>(g, d, x, ctx->stream));
       quad_stream_prepare_mid<MODE><<<cnt, kQuadStreamBlock, 0, ctx->stream>>>(d, sa);
-      CXK_TRY(LaunchQuadStreamQmv<1>(d, QuadStreamOne(d.dv, (size_t)g.n), ctx->stream));
+      CXK_TRY(LaunchQuadStreamQmv<1>(g, d, QuadStreamOne(d.dv, (size_t)g.n), ctx->stream));
       quad_stream_prepare_finish<MODE><<<cnt, kQuadStreamBlock, 0, ctx->stream>>>(d, sa);
       break;
     }

@@ -95,6 +95,32 @@ inline bool SocSparsePays(double len, double m, double nnz, double ratio) {
 // more.  Nothing smaller was measured, so nothing smaller moves (the cones of a handful of doubles stay where they are).
 constexpr long long kQuadStreamMinWork = 32 * 32 + 33 * 8;  // 1288
 
+// A quadratic cone whose Q = S + F diag(sigma) F' is given by its parts (cxk_add_quadratic_structured,
+// kernels_quad_structured.hip.h).  How many lanes work on one row of S, from the mean nonzeros per row of the group: one
+// lane is a chain as long as the row, 64 lanes leave most of a wavefront idle on a short row.  Measured
+// (tools/quad_structured_speed.py --lanes, DESIGN.md 4.10.2: one cone, n = 16384, m = 8, rank 8, band matrices of 3, 9,
+// 27, 81 and 243 nonzeros per row, assembly + PrepareStep + TakeStep in us under 1 / 8 / 64 lanes): 255 / 268 / 363,
+// 256 / 271 / 368, 284 / 288 / 371, 363 / 330 / 414, 784 / 559 / 615.  One lane is the fastest up to 27 per row (a tie
+// with eight there), eight lanes from 81 on; 64 lanes won at no swept width.  So: one lane up to the largest width at
+// which it did not lose, eight up to the largest width measured; beyond 243 per row NOTHING was measured and the step to
+// 64 lanes there is a guess (the trend, 1.26 times the 8-lane time at 81 and 1.10 times at 243, is all that speaks for it).
+// One box, one day.  CXK_QUAD_CSR_LANES = 1 | 8 | 64 overrides the rule.
+constexpr double kQuadCsrOneLaneMaxMean = 27;
+constexpr double kQuadCsrEightLanesMaxMean = 243;
+inline int QuadCsrLanes(double nnz, double rows) {
+  const double mean = rows > 0 ? nnz / rows : 0;
+  return mean <= kQuadCsrOneLaneMaxMean ? 1 : mean <= kQuadCsrEightLanesMaxMean ? 8 : 64;
+}
+// Row segments of the factor dots F' x of `columns` = cones x rank columns of n rows: enough workgroups to fill the
+// chip (as QuadStreamSplits: 512), none shorter than kQuadFactorMinSegment rows (four per thread of a workgroup).
+constexpr int kQuadFactorMinSegment = 1024;
+inline int QuadFactorSegments(int n, long long columns) {
+  const long long cols = columns > 0 ? columns : 1;
+  const long long by_len = n / kQuadFactorMinSegment, by_fill = (512 + cols - 1) / cols;
+  const long long s = by_len < by_fill ? by_len : by_fill;
+  return s < 1 ? 1 : (int)s;
+}
+
 // Automatic mode (cxk_set_sparse_affine(ctx, -1)) evaluates the affine term C of a sparse matrix inequality beyond
 // the LDS-resident orders from C's nonzeros (kernels_lmi_sparse.hip.h: lmi_affine_wc, lmi_affine_x) when
 // R (nnz_c + npos) <= 4 n^2: the two kernels make n nnz_c + n npos multiply-adds (npos: the distinct positions of
@@ -143,6 +169,10 @@ struct ConeShape {
   // CXK_LMI: the predicates that live beside the kernels, already evaluated
   bool mfma_supports = false;  // LmiMfmaSupports(n, m, herm_d)
   bool sparse_pays = false;    // LmiSparsePays(n, m, nonzeros of A, LmiLdsResident(n, m), mfma_supports)
+  // CXK_QUAD whose Q = S + F diag(sigma) F' is held by its parts (has_q is set too): the nonzeros of S, the rank
+  bool q_structured = false;
+  double q_nnz = 0;
+  int q_rank = 0;
 };
 
 // The modes in force: what the context was told (cxk_set_*), else the environment's word, else the default here
@@ -255,6 +285,17 @@ inline RouteChoice ChooseSoc(const ConeShape& s, const RouteModes& md) {
 }
 
 inline RouteChoice ChooseQuad(const ConeShape& s, const RouteModes& md) {
+  // held by the parts of Q: no LDS form, whatever the switch says; n x n is never formed, so only the nonzeros of S
+  // (ints on the device, per group: UploadQuadStructured) and the two demands of every streamed cone remain
+  if (s.q_structured) {
+    if (!EntriesFitInt((int64_t)s.n + 1, s.m))
+      return Refuse("a streamed quadratic cone whose (dimension + 1) x variables entries exceed the int range is not supported");
+    if (!SquareFitsInt(s.m))
+      return Refuse("a streamed quadratic cone whose variables x variables Schur block exceeds the int range is not supported");
+    if (s.q_nnz > (double)INT_MAX)
+      return Refuse("a structured quadratic cone whose sparse part has more than 2^31 nonzeros is not supported");
+    return Take(ConeRoute::kQuadStreamed);
+  }
   // quad_prepare keeps y and four vectors of the cone in LDS; quad_schur and quad_take_step need less
   const bool fits = QuadPrepareLds(s.n, s.m) <= kLdsLimit && QuadSchurLds(s.n, s.m) <= kLdsLimit && QuadTakeLds(s.n) <= kLdsLimit;
   const double work = (s.has_q ? (double)s.n * s.n : 0.0) + ((double)s.n + 1) * s.m;  // doubles streamed per pass

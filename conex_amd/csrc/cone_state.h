@@ -2,8 +2,8 @@
 // route has (Group) around one by-value state struct per cone family.  A family's struct is read and written in its own
 // unit only -- lin in cone_linear.hip, soc in cone_soc.hip, quad in cone_quad.hip, lmi in cone_lmi.hip (cone_units.h) --
 // but for:
-//   kkt_cone_launch.hip  GroupConstraints writes the group key (lmi.literal, quad.has_q, lmi.f.R, lmi.sa.on);
-//                        UploadDenseData reads lmi.assembly; StepTailOk reads lmi.large and lmi.literal,
+//   kkt_cone_launch.hip  GroupConstraints writes the group key (lmi.literal, quad.has_q, quad.sq.on / has_s / rank, lmi.f.R, lmi.sa.on);
+//                        UploadDenseData reads lmi.assembly; UploadGroup reads quad.sq.on; StepTailOk reads lmi.large and lmi.literal,
 //                        TakeStepFromDeviceOk lmi.large
 //   MakeVec              (cone_linear.hip) hands lin.T2 to every vector cone's kernels, the other families' included
 // Host code only, no device code.
@@ -139,6 +139,19 @@ struct CXK_LOCAL QuadState {
   int splits = 1;       // column splits of the products with Q (QuadStreamSplits; 1 where Q is the identity)
   DevBuf<double> part;  // the split partials of those products
   DevBuf<double> vec;   // every vector and scalar of the work space (MakeQuadStream lays it out)
+  // kQuadStreamed with Q = S + F diag(sigma) F' held by its parts (cxk_add_quadratic_structured): the kernels of
+  // kernels_quad_structured.hip.h make the products with Q.  No Q: `has_q` is set, Q stays empty, splits is 1.
+  // Members agree on rank and on having S (the group key); their nonzeros are concatenated.
+  struct Structured {
+    bool on = false, has_s = false;
+    int rank = 0;
+    int lanes = 1;  // lanes per row of S (cone_route.h: QuadCsrLanes, or CXK_QUAD_CSR_LANES)
+    int segs = 1;   // row segments of the factor dots (QuadFactorSegments)
+    DevBuf<long long> rowptr;  // count x (n + 1), absolute positions in col / val
+    DevBuf<int> col;
+    DevBuf<double> val, F, sigma;
+    DevBuf<double> tpart;  // count x 2 x rank x segs
+  } sq;
 };
 
 // Matrix inequalities: cone_lmi.hip.

@@ -16,6 +16,11 @@
 #include "cone_types.h"
 #include "kkt_launch.h"
 
+namespace cxk {
+struct QuadStreamGroup;  // kernels_quad_stream.hip.h
+struct QuadStreamVecs;
+}  // namespace cxk
+
 namespace cxk_host {
 
 // ---- kkt_cone_launch.hip
@@ -77,6 +82,11 @@ CXK_LOCAL void LaunchSocStreamSlack(const SocStreamGroup& d, const StepArgs& sa,
 CXK_LOCAL hipError_t RaiseQuadLdsLimits();
 CXK_LOCAL int UploadQuadGram(cxk_context* ctx, Group& g);
 CXK_LOCAL int UploadQuadStream(cxk_context* ctx, Group& g, const FinalizeSwitches& sw);
+// a kQuadStreamed group whose Q is held by its parts (Group::quad.sq.on): instead of UploadQuadStream
+CXK_LOCAL int UploadQuadStructured(cxk_context* ctx, Group& g, const FinalizeSwitches& sw);
+// ... and its pass out_r = Q x_r, which LaunchQuadStreamQmv hands over (defined behind it, in the same unit)
+template <int R>
+CXK_LOCAL hipError_t LaunchQuadStructuredQmv(Group& g, const cxk::QuadStreamGroup& d, const cxk::QuadStreamVecs& x, hipStream_t st);
 CXK_LOCAL void LaunchQuadLdsSchur(Group& g, const Arena& ar, hipStream_t st);
 hipError_t LaunchQuadStreamSchur(Group& g, const Arena& ar, hipStream_t st);
 CXK_LOCAL int LaunchQuadPrepare(cxk_context* ctx, Group& g, int mode, const StepArgs& sa);

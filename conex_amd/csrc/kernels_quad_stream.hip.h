@@ -28,11 +28,15 @@ constexpr int kQuadStreamRowTile = 256;    // rows of Q one workgroup of quad_st
 constexpr int kQuadStreamXChunk = 64;      // entries of each x staged in LDS at a time
 constexpr int kQuadStreamMinSplit = 64;    // Q's columns are split only into pieces at least this long
 
+// How a group's inner-product matrix is held: what a pass out_r = Q x_r launches and whether QuadStreamQx has partials to read.
+enum QuadQForm { kQuadQIdentity = 0, kQuadQDense = 1, kQuadQStructured = 2 };
+
 struct QuadStreamGroup {
   int n, m, count, splits;
+  int q_form;           // QuadQForm; kQuadQStructured: Q = S + F diag(sigma) F' (kernels_quad_structured.hip.h), splits = 1
   const double* A;      // count x (n + 1) x m
   const double* c;      // count x (n + 1)
-  const double* Q;      // count x n x n, nullptr: identity
+  const double* Q;      // count x n x n; nullptr unless q_form is kQuadQDense
   const double* Agram;  // count x m x m
   double* W;            // count x (n + 1)
   double* D;            // count x (n + 1)
@@ -108,7 +112,7 @@ __global__ void __launch_bounds__(kQuadStreamBlock) quad_stream_qmv(QuadStreamGr
 
 // (Q x_r)_i of cone `mem` from the partials, the splits in order; x_i itself where Q is the identity.
 __device__ __forceinline__ double QuadStreamQx(const QuadStreamGroup& g, size_t mem, int r, int i, double x_i) {
-  if (!g.Q) return x_i;
+  if (g.q_form == kQuadQIdentity) return x_i;
   const double* p = g.part + ((mem * g.splits) * 2 + r) * (size_t)g.n + i;
   double t = 0;
   for (int s = 0; s < g.splits; s++) t += p[(size_t)s * 2 * g.n];

@@ -186,7 +186,7 @@ static void MeasureNonzeros(ConstraintRec* c, ConeShape* s) {
 // cxk_finalize fails with); constraints of one shape on one route form a group, numbered by first appearance.
 int GroupConstraints(cxk_context* ctx, const FinalizeSwitches& sw) {
   const int K = (int)ctx->cons.size();
-  std::map<std::tuple<int, int, int, int, ConeRoute, bool, bool, int, bool, bool>, int> gmap;
+  std::map<std::tuple<int, int, int, int, ConeRoute, bool, bool, int, bool, bool, int, int>, int> gmap;
   ctx->groups.clear();
   ctx->sparse_soc_setup_ms = 0;
   // what the context was told (-1 / -2: nothing) goes in front of the environment's word
@@ -204,7 +204,11 @@ int GroupConstraints(cxk_context* ctx, const FinalizeSwitches& sw) {
     c.entries.sparse_affine = false;
     c.entries.fold = false;
     if (!ctx->owned[i]) continue;
-    ConeShape s{c.type, c.n, c.m, c.herm_d, c.symmetric, c.csr_only, c.factors.given, c.type == CXK_QUAD && !c.Q.empty()};
+    ConeShape s{c.type, c.n, c.m, c.herm_d, c.symmetric, c.csr_only, c.factors.given,
+                c.type == CXK_QUAD && (!c.Q.empty() || c.sq.given)};
+    s.q_structured = c.sq.given;
+    s.q_nnz = (double)c.sq.col.size();
+    s.q_rank = c.sq.rank;
     const int sparse_mode = c.type == CXK_LINEAR ? modes.sparse_linear : c.type == CXK_SOC ? modes.sparse_soc : 0;
     if (sparse_mode != 0 && !c.csr_only) MeasureNonzeros(&c, &s);
     if (c.type == CXK_LMI && !c.factors.given) MeasureLmi(c, &s);
@@ -220,7 +224,11 @@ int GroupConstraints(cxk_context* ctx, const FinalizeSwitches& sw) {
     // (likewise the folded sums of a Hermitian constraint over C or H: the real one, d = 1, has nothing to fold)
     if (c.route == ConeRoute::kLmiSparse && c.herm_d > 1)
       c.entries.fold = (modes.sparse_fold != -2 ? modes.sparse_fold : c.entries.fold_default) != 0;
-    const auto key = std::make_tuple(c.type, c.n, c.m, c.herm_d, c.route, literal, s.has_q, f_R, c.entries.sparse_affine, c.entries.fold);
+    // the form of a quadratic cone's Q: 0 dense or none (has_q), else structured with (2) or without (1) a sparse part,
+    // and the rank; the nonzero counts of the members may differ
+    const int q_form = c.sq.given ? (c.sq.ptr.empty() ? 1 : 2) : 0;
+    const auto key = std::make_tuple(c.type, c.n, c.m, c.herm_d, c.route, literal, s.has_q, f_R, c.entries.sparse_affine, c.entries.fold,
+                                     q_form, c.sq.rank);
     auto it = gmap.find(key);
     if (it == gmap.end()) {
       it = gmap.emplace(key, (int)ctx->groups.size()).first;
@@ -233,6 +241,9 @@ int GroupConstraints(cxk_context* ctx, const FinalizeSwitches& sw) {
       // the rest of the key: the one place outside a family's unit that writes its state (cone_state.h)
       g.lmi.literal = literal;
       g.quad.has_q = s.has_q;
+      g.quad.sq.on = c.sq.given;
+      g.quad.sq.has_s = q_form == 2;
+      g.quad.sq.rank = c.sq.rank;
       g.lmi.f.R = f_R;
       g.lmi.sa.on = c.entries.sparse_affine;
       g.lmi.sp.fold = c.entries.fold;
@@ -266,7 +277,7 @@ int UploadGroup(cxk_context* ctx, Group& g, const FinalizeSwitches& sw) {
     case ConeRoute::kSocStreamed: return UploadSocStream(ctx, g, sw);
     case ConeRoute::kSocSparse: return UploadSocSparse(ctx, g);
     case ConeRoute::kQuadLds: return UploadQuadGram(ctx, g);
-    case ConeRoute::kQuadStreamed: return UploadQuadStream(ctx, g, sw);
+    case ConeRoute::kQuadStreamed: return g.quad.sq.on ? UploadQuadStructured(ctx, g, sw) : UploadQuadStream(ctx, g, sw);
     case ConeRoute::kLmiDense: return UploadLmiDense(ctx, g, sw);
     case ConeRoute::kLmiSparse: return UploadLmiSparse(ctx, g);
     case ConeRoute::kLmiFactored: return UploadLmiFactored(ctx, g);

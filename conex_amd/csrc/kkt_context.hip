@@ -104,6 +104,7 @@ static FinalizeSwitches ReadFinalizeSwitches() {
   if ((v = getenv("CXK_TILED_LINEAR")) && v[0] != '\0') sw.modes.tiled_linear = atoi(v) != 0;
   if ((v = getenv("CXK_STREAMED_QUADRATIC")) && v[0] != '\0') sw.modes.streamed_quadratic = atoi(v) != 0;
   if ((v = getenv("CXK_STREAMED_QUADRATIC_MIN_WORK")) && v[0] != '\0') sw.modes.streamed_quadratic_min_work = std::max(0ll, atoll(v));
+  if ((v = getenv("CXK_QUAD_CSR_LANES")) && (atoi(v) == 1 || atoi(v) == 8 || atoi(v) == 64)) sw.quad_csr_lanes = atoi(v);
   if ((v = getenv("CXK_SPARSE_LINEAR")) && v[0] != '\0') sw.modes.sparse_linear = atoi(v) != 0;
   if ((v = getenv("CXK_SPARSE_LINEAR_MIN_RATIO")) && v[0] != '\0') sw.modes.sparse_linear_min_ratio = std::max(0.0, atof(v));
   if ((v = getenv("CXK_TILED_LINEAR_MIN_WORK")) && v[0] != '\0') sw.modes.tiled_linear_min_work = std::max(0ll, atoll(v));
@@ -711,6 +712,56 @@ int cxk_add_quadratic(cxk_context* ctx, int n, int m, const double* Q, const dou
   return AddConstraint(ctx, std::move(r), vars);
 }
 
+int cxk_add_quadratic_structured(cxk_context* ctx, int n, int m, const int* q_rowptr, const int* q_col, const double* q_val,
+                                 int rank, const double* F, const double* sigma, const double* A, const double* c,
+                                 const int* vars) {
+  if (!ctx) return -1;
+  auto refuse = [ctx](const char* msg) {
+    ctx->err = std::string("cxk_add_quadratic_structured: ") + msg;
+    return -1;
+  };
+  if (n < 1 || m < 0) return refuse("n is at least 1 and m at least 0");
+  if (!A || !c) return refuse("A or c is null");
+  if (rank < 0) return refuse("rank is negative");
+  if (!q_rowptr && rank == 0)
+    return refuse("neither a sparse part nor factors: for the identity pass Q = NULL to cxk_add_quadratic");
+  if (rank > 0 && !F) return refuse("F is null");
+  if (q_rowptr) {
+    if (q_rowptr[0] != 0) return refuse("q_rowptr[0] is not 0");
+    for (int r = 0; r < n; r++)
+      if (q_rowptr[r + 1] < q_rowptr[r]) return refuse("q_rowptr decreases");
+    if (q_rowptr[n] > 0 && (!q_col || !q_val)) return refuse("q_col or q_val is null");
+    for (int e = 0; e < q_rowptr[n]; e++) {
+      if (q_col[e] < 0 || q_col[e] >= n) return refuse("a column of the sparse part is outside [0, n)");
+      if (!std::isfinite(q_val[e])) return refuse("q_val holds a value that is not finite");
+    }
+  }
+  const size_t nr = (size_t)n * rank;
+  for (size_t q = 0; q < nr; q++)
+    if (!std::isfinite(F[q])) return refuse("F holds a value that is not finite");
+  for (int k = 0; sigma && k < rank; k++)
+    if (!std::isfinite(sigma[k])) return refuse("sigma holds a value that is not finite");
+  ConstraintRec r;
+  r.type = CXK_QUAD;
+  r.n = n;
+  r.m = m;
+  r.A.assign(A, A + (size_t)(n + 1) * m);
+  r.C.assign(c, c + n + 1);
+  r.sq.given = true;
+  r.sq.rank = rank;
+  if (q_rowptr) {  // as given: duplicates stay, the kernels sum them
+    r.sq.ptr.assign(q_rowptr, q_rowptr + n + 1);
+    r.sq.col.assign(q_col, q_col + q_rowptr[n]);
+    r.sq.val.assign(q_val, q_val + q_rowptr[n]);
+  }
+  if (rank > 0) r.sq.F.assign(F, F + nr);
+  if (sigma)
+    r.sq.sigma.assign(sigma, sigma + rank);
+  else
+    r.sq.sigma.assign((size_t)rank, 1.0);
+  return AddConstraint(ctx, std::move(r), vars);
+}
+
 int cxk_add_static(cxk_context* ctx, int m, const double* G, const int* vars) {
   if (!ctx || m < 1 || !G) return -1;
   ConstraintRec r;
@@ -878,6 +929,12 @@ int cxk_set_streamed_quadratic(cxk_context* ctx, int mode) {
   return CXK_SUCCESS;
 }
 int cxk_count_streamed_quadratic(const cxk_context* ctx) { return CountOnRoute(ctx, ConeRoute::kQuadStreamed); }
+int cxk_count_structured_quadratic(const cxk_context* ctx) {
+  if (!ctx || !ctx->finalized) return -1;
+  int k = 0;
+  for (size_t i = 0; i < ctx->cons.size(); i++) k += ctx->owned[i] && ctx->cons[i].route == ConeRoute::kQuadStreamed && ctx->cons[i].sq.given;
+  return k;
+}
 
 int cxk_finalize(cxk_context* ctx) {
   if (!ctx) return CXK_FAILURE;

@@ -43,6 +43,14 @@ struct ConstraintRec {
   int eq_rows = 0; // CXK_STATIC built from EqualityConstraints: number of multipliers (last clique entries)
   std::vector<double> A, C;
   std::vector<double> Q;  // CXK_QUAD: n x n inner-product matrix, empty = identity
+  // CXK_QUAD whose Q = S + F diag(sigma) F' is given by its parts (cxk_add_quadratic_structured; Q above stays empty and
+  // nothing of n x n is formed): S by rows as given (duplicates kept, ptr empty: no sparse part), F n x rank column-major
+  struct StructuredQ {
+    bool given = false;
+    int rank = 0;
+    std::vector<int> ptr, col;
+    std::vector<double> val, F, sigma;
+  } sq;
   int group = -1, member = -1;
   ConeRoute route = ConeRoute::kStatic;  // the set of kernels it runs on, chosen by cxk_finalize (cone_route.h, Choose)
   // every A_i and C equals its transpose.  The fast kernels use tr(W A_i W A_j) = tr(P_i P_j),

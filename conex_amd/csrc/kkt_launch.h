@@ -74,7 +74,8 @@ struct FinalizeSwitches {
   bool no_packed_slack = false; // CXK_NO_PACKED_SLACK
   int gram_splits = 0;          // CXK_GRAM_SPLITS: K splits of the GEMM assembly (0: chosen by shape)
   int soc_stream_stages = 0;    // CXK_SOC_STREAM_STAGES=1 / 2: their assembly stops after that stage (timing runs: wrong results)
-  int wide_spectrum = -1;       // CXK_WIDE_SPECTRUM: -1 large-order LMI groups beyond the one-workgroup Lanczos run, 0 never, 1 all
+  int quad_csr_lanes = 0;       // CXK_QUAD_CSR_LANES=1 / 8 / 64: lanes per row of a structured quadratic cone's S (0: QuadCsrLanes)
+  int wide_spectrum = -1;     // CXK_WIDE_SPECTRUM: -1 large-order LMI groups beyond the one-workgroup Lanczos run, 0 never, 1 all
   int wide_reduce_min_order = -1;    // CXK_WIDE_REDUCE_MIN_ORDER instead of kWideReduceMinOrder (kernels_lmi_wide.hip.h; tests)
 };
 

@@ -63,6 +63,12 @@ struct Cone {
   std::vector<double> A;
   std::vector<double> c;
   std::vector<double> Q;  // kQuadCone: inner-product matrix (order x order), empty = identity
+  // kQuadCone added by CONEX_HIP_AddStructuredQuadraticConstraint: Q = S + F diag(sigma) F' by its parts (S in CSR as
+  // q_ptr / q_col / q_val, q_ptr empty: no sparse part; F order x q_rank in `F`, `sigma`); Q stays empty and is never formed
+  bool structured_q = false;
+  int q_rank = 0;
+  std::vector<int> q_ptr, q_col;
+  std::vector<double> q_val;
   // kLmi added by CONEX_HIP_AddFactoredLMIConstraint: A_v = sum_k sigma[k] f_k f_k', k in rank_ptr[v] .. rank_ptr[v + 1] - 1,
   // f_k the columns of F (order x rank_ptr.back()); `mats` stays empty, `affine` holds C.  Added by
   // CONEX_HIP_AddFactoredHermitianConstraint (`hermitian` set): F and `affine` hold `hyper` planes
@@ -230,6 +236,13 @@ int BuildContext(Program* p) {
         id = cxk_add_static(p->ctx, m, c.A.data(), c.vars.data());
         break;
       case kQuadCone:
+        if (c.structured_q) {  // the parts go to the device as they are
+          id = cxk_add_quadratic_structured(p->ctx, c.order, m, c.q_ptr.empty() ? nullptr : c.q_ptr.data(), c.q_col.data(),
+                                            c.q_val.data(), c.q_rank, c.q_rank > 0 ? c.F.data() : nullptr,
+                                            c.q_rank > 0 ? c.sigma.data() : nullptr, c.A.data(), c.c.data(), c.vars.data());
+          CONEX_DEMAND(id >= 0, cxk_last_error(p->ctx));
+          break;
+        }
         id = cxk_add_quadratic(p->ctx, c.order, m, c.Q.empty() ? nullptr : c.Q.data(), c.A.data(), c.c.data(),
                                c.vars.data());
         break;
@@ -1262,6 +1275,59 @@ int CONEX_HIP_AddQuadraticConstraint(void* x, const double* Q, int n, const doub
   k.A.assign(A, A + (size_t)(n + 1) * Ac);
   k.c.assign(c, c + n + 1);
   if (Q) k.Q.assign(Q, Q + (size_t)n * n);
+  if (vars) {
+    for (int i = 0; i < Ac; i++) {
+      if (vars[i] < 0 || vars[i] >= p->num_vars) return -1;
+      k.vars.push_back((int)vars[i]);
+    }
+  } else {
+    k.vars = AllVars(*p);
+  }
+  return AddCone(p, std::move(k));
+}
+
+/* not part of conex.h: the cone of CONEX_HIP_AddQuadraticConstraint with Q = S + F diag(sigma) F' given by its parts and
+ * never formed (cxk_add_quadratic_structured): S n x n in CSR (q_rowptr: n + 1 from 0, q_col, q_val; both triangles, as
+ * given; NULL: no sparse part), F n x rank column-major (NULL when rank = 0), sigma rank entries (NULL: all +1).  Not
+ * both parts absent.  A, c and vars as for CONEX_HIP_AddQuadraticConstraint.  Returns the constraint id, -1 on
+ * invalid arguments (among them a decreasing q_rowptr, a column outside [0, n), a value that is not finite). */
+int CONEX_HIP_AddStructuredQuadraticConstraint(void* x, int n, const int* q_rowptr, const int* q_col, const double* q_val,
+                                               int rank, const double* F, const double* sigma, const double* A, int Ar,
+                                               int Ac, const double* c, int cr, const long* vars, int num_vars) {
+  Program* p = static_cast<Program*>(x);
+  if (!p || p->magic != 0xC0DEC0DEu || n < 1 || !A || !c || Ar != n + 1 || cr != n + 1 || Ac < 1) return -1;
+  if (vars ? num_vars != Ac : Ac != p->num_vars) return -1;
+  if (rank < 0 || (rank > 0 && !F) || (!q_rowptr && rank == 0)) return -1;
+  Cone k;
+  k.kind = kQuadCone;
+  k.order = n;
+  k.cols = Ac;
+  k.structured_q = true;
+  k.q_rank = rank;
+  if (q_rowptr) {
+    if (q_rowptr[0] != 0) return -1;
+    for (int r = 0; r < n; r++)
+      if (q_rowptr[r + 1] < q_rowptr[r]) return -1;
+    const int nnz = q_rowptr[n];
+    if (nnz > 0 && (!q_col || !q_val)) return -1;
+    for (int e = 0; e < nnz; e++)
+      if (q_col[e] < 0 || q_col[e] >= n || !std::isfinite(q_val[e])) return -1;
+    k.q_ptr.assign(q_rowptr, q_rowptr + n + 1);
+    k.q_col.assign(q_col, q_col + nnz);
+    k.q_val.assign(q_val, q_val + nnz);
+  }
+  const size_t nr = (size_t)n * rank;
+  for (size_t q = 0; q < nr; q++)
+    if (!std::isfinite(F[q])) return -1;
+  for (int j = 0; sigma && j < rank; j++)
+    if (!std::isfinite(sigma[j])) return -1;
+  if (rank > 0) k.F.assign(F, F + nr);
+  if (sigma)
+    k.sigma.assign(sigma, sigma + rank);
+  else
+    k.sigma.assign((size_t)rank, 1.0);
+  k.A.assign(A, A + (size_t)(n + 1) * Ac);
+  k.c.assign(c, c + n + 1);
   if (vars) {
     for (int i = 0; i < Ac; i++) {
       if (vars[i] < 0 || vars[i] >= p->num_vars) return -1;

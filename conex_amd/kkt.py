@@ -135,6 +135,9 @@ _SIGNATURES = {
     "cxk_count_streamed_cones": (C.c_int, [C.c_void_p]),
     "cxk_set_streamed_quadratic": (C.c_int, [C.c_void_p, C.c_int]),
     "cxk_count_streamed_quadratic": (C.c_int, [C.c_void_p]),
+    "cxk_add_quadratic_structured": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_int_p, c_int_p, c_double_p, C.c_int, c_double_p,
+                                               c_double_p, c_double_p, c_double_p, c_int_p]),
+    "cxk_count_structured_quadratic": (C.c_int, [C.c_void_p]),
     "cxk_set_tiled_linear": (C.c_int, [C.c_void_p, C.c_int]),
     "cxk_set_sparse_linear": (C.c_int, [C.c_void_p, C.c_int]),
     "cxk_count_sparse_linear": (C.c_int, [C.c_void_p]),
@@ -201,6 +204,33 @@ def _colmajor(a):
 
 class KktError(RuntimeError):
     pass
+
+
+def structured_q_parts(S, n):
+    """(indptr, indices, data) as contiguous int32 / int32 / float64 arrays of the sparse part of a structured Q of order
+    n, or (None, None, None): S is None, a triple, or any object with the attributes indptr, indices and data (a scipy CSR
+    matrix; scipy itself is not needed)."""
+    if S is None:
+        return None, None, None
+    if all(hasattr(S, a) for a in ("indptr", "indices", "data")):
+        S = (S.indptr, S.indices, S.data)
+    try:
+        indptr, indices, data = S
+    except (TypeError, ValueError):
+        raise ValueError("S is None, (indptr, indices, data) or an object with those attributes") from None
+    ip64, ix64 = np.asarray(indptr).ravel(), np.asarray(indices).ravel()
+    if ip64.dtype.kind not in "iu" or (len(ix64) and ix64.dtype.kind not in "iu"):
+        raise ValueError("S: indptr and indices are integers")
+    if len(ip64) and (ip64.max() > 2 ** 31 - 1 or ip64.min() < -2 ** 31):
+        raise ValueError("S: indptr beyond the int range")
+    if len(ix64) and (ix64.max() > 2 ** 31 - 1 or ix64.min() < -2 ** 31):
+        raise ValueError("S: indices beyond the int range")
+    rp = np.ascontiguousarray(ip64, dtype=np.int32)
+    cl = np.ascontiguousarray(ix64, dtype=np.int32)
+    vl = np.ascontiguousarray(np.asarray(data, dtype=np.float64).ravel())
+    if len(rp) != n + 1 or len(cl) != len(vl) or (len(rp) and rp[-1] > len(vl)):
+        raise ValueError("S: indptr has n + 1 entries and points into indices / data of equal length")
+    return rp, cl, vl
 
 
 class KktContext:
@@ -435,6 +465,41 @@ class KktContext:
         if r >= 0:
             self.cons.append(("quad", n1 - 1, m))
         return r
+
+    def add_quadratic_structured(self, S, F, sigma, A, c, vars_=None):
+        """The cone of add_quadratic with Q = S + F diag(sigma) F' given by its parts and never formed.  S: None, a triple
+        (indptr, indices, data) or any object with those three attributes (a scipy CSR matrix), n x n with both
+        triangles stored; F: None or (n, r); sigma: None (all +1) or (r,).  Not both S and F None."""
+        A = np.asarray(A, dtype=np.float64)
+        n1, m = A.shape
+        a = _colmajor(A)
+        cc = np.ascontiguousarray(np.asarray(c, dtype=np.float64).ravel())
+        rp, cl, vl = structured_q_parts(S, n1 - 1)
+        f = sg = None
+        rank = 0
+        if F is not None:
+            F = np.asarray(F, dtype=np.float64)
+            if F.ndim != 2 or F.shape[0] != n1 - 1:
+                raise ValueError("add_quadratic_structured: F is (n, r)")
+            rank = F.shape[1]
+            f = _colmajor(F)
+        if sigma is not None:
+            sg = np.ascontiguousarray(np.asarray(sigma, dtype=np.float64).ravel())
+            if len(sg) != rank:
+                raise ValueError("add_quadratic_structured: sigma has one entry per column of F")
+        keep, vp = self._vars(vars_)
+        r = self.L.cxk_add_quadratic_structured(
+            self.h, n1 - 1, m, None if rp is None else _ip(rp), None if rp is None else _ip(cl),
+            None if rp is None else _dp(vl), rank, None if f is None or rank == 0 else _dp(f), None if sg is None else _dp(sg),
+            _dp(a), _dp(cc), vp)
+        if r < 0:  # refused by name (the context stays usable)
+            raise KktError(self.L.cxk_last_error(self.h).decode() or "cxk_add_quadratic_structured: invalid arguments")
+        self.cons.append(("quad", n1 - 1, m))
+        return r
+
+    def count_structured_quadratic(self):
+        """Constraints this context owns that were added by add_quadratic_structured."""
+        return self.L.cxk_count_structured_quadratic(self.h)
 
     def add_static(self, G, vars_):
         G = np.asarray(G, dtype=np.float64)

@@ -397,6 +397,47 @@ class Conex:
         self.num_constraints += 1
         return cid
 
+    def AddStructuredQuadraticConstraint(self, S, F, sigma, A, c, variables=None):
+        """The cone of AddQuadraticConstraint with Q = S + F diag(sigma) F' given by its parts and never formed
+        (CONEX_HIP_AddStructuredQuadraticConstraint).  S is None, a triple (indptr, indices, data) or any object with
+        those three attributes (a scipy CSR matrix), n x n with both triangles stored; F is None or (n, r); sigma None
+        (all +1) or (r,).  Not both S and F None.  Returns the constraint id."""
+        from .kkt import structured_q_parts
+        A = np.asarray(A, dtype=np.float64)
+        c = _f64(np.asarray(c, dtype=np.float64).ravel())
+        if A.ndim != 2 or A.shape[0] < 2 or len(c) != A.shape[0]:
+            raise ConexError("Invalid quadratic constraint.")
+        n = A.shape[0] - 1
+        try:
+            rp, cl, vl = structured_q_parts(S, n)
+        except ValueError as e:
+            raise ConexError("Invalid quadratic constraint: %s" % e) from None
+        rank, Ff, sg = 0, None, None
+        if F is not None:
+            F = np.asarray(F, dtype=np.float64)
+            if F.ndim != 2 or F.shape[0] != n:
+                raise ConexError("Invalid quadratic constraint.")
+            rank = F.shape[1]
+            Ff = capi.colmajor(F)
+        if sigma is not None:
+            sg = _f64(np.asarray(sigma, dtype=np.float64).ravel())
+            if len(sg) != rank:
+                raise ConexError("Invalid quadratic constraint.")
+        if rp is None and rank == 0:
+            raise ConexError("Invalid quadratic constraint: neither a sparse part nor factors.")
+        Af = capi.colmajor(A)
+        v = None if variables is None else np.ascontiguousarray(np.asarray(variables).ravel(), dtype=np.int64)
+        ip = C.POINTER(C.c_int)
+        cid = self._L.CONEX_HIP_AddStructuredQuadraticConstraint(
+            self.a, n, None if rp is None else rp.ctypes.data_as(ip), None if rp is None else cl.ctypes.data_as(ip),
+            None if rp is None else capi.dp(vl), rank, None if rank == 0 else capi.dp(Ff), None if sg is None else capi.dp(sg),
+            capi.dp(Af), n + 1, A.shape[1], capi.dp(c), n + 1,
+            None if v is None else v.ctypes.data_as(C.POINTER(C.c_long)), 0 if v is None else len(v))
+        if cid < 0:
+            raise ConexError("Failed to add constraint.")
+        self.num_constraints += 1
+        return cid
+
     # ---- entry-by-entry builders
     def _new(self, fn, *args, what="constraint"):
         cid = C.c_int()

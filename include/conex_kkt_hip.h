@@ -356,6 +356,8 @@ int cxk_add_hermitian_factored(cxk_context* ctx, int n, int d, int m, const int*
  * doubles streamed per pass, (Q ? n n : 0) + (n + 1) m, reach the measured threshold (kQuadStreamMinWork;
  * CXK_STREAMED_QUADRATIC_MIN_WORK moves it for comparison runs).  Cones on the LDS route keep their kernels and
  * their bits.  Every output, getter and setter of a streamed cone is that of any quadratic cone.
+ * A cone added by cxk_add_quadratic_structured (below) has no LDS form: it takes the streamed route under every mode,
+ * 0 included.
  * Refused on the streamed route at cxk_finalize, by name: (dimension + 1) x variables, variables^2 or the entries
  * of Q beyond the int range; a group of equal cones with more than 2^31 columns, row tiles or blocks.
  * cxk_count_streamed_quadratic: constraints this context owns that run on the streamed route (-1 before
@@ -363,6 +365,34 @@ int cxk_add_hermitian_factored(cxk_context* ctx, int n, int d, int m, const int*
  * second-order cones only. */
 int cxk_set_streamed_quadratic(cxk_context* ctx, int mode);
 int cxk_count_streamed_quadratic(const cxk_context* ctx);
+
+/* The quadratic cone of cxk_add_quadratic with Q = S + F diag(sigma) F' given by its parts and never formed: factor-model
+ * risk (D + F Sigma F'), generalised least squares with a banded or graph-structured precision matrix, energy bounds
+ * with a stiffness matrix, Q = L L' known by its factor.
+ *   S      n x n by its nonzeros in CSR (q_rowptr: n + 1 ints from 0, q_col, q_val), multiplied as given: BOTH triangles
+ *          are stored; symmetry and definiteness of Q are the caller's duty, as with the dense Q.  Duplicate entries of a
+ *          row are summed (in the order they are stored when one lane works on a row).  q_rowptr = NULL: no sparse part.
+ *   F      n x rank column-major, sigma rank entries of either sign (NULL: all +1).  rank = 0: no factors.
+ * Refused by name (cxk_last_error): q_rowptr[0] != 0 or decreasing, a column outside [0, n), a value of q_val, F or
+ * sigma that is not finite, rank < 0, and both parts absent (for the identity pass Q = NULL to cxk_add_quadratic).
+ * The constraint keeps the CSR arrays, F and sigma; nothing of n x n is allocated on the host or the device at any
+ * point, and the streamed route's refusal of an order beyond 46 340 (n^2 past the int range) does not apply; the demands
+ * on (n + 1) m and m^2 stay, and the nonzeros of a group of equal cones must fit an int.  A host-only context takes the
+ * call; the problem's structure (cliques, fill, order) is that of cxk_add_quadratic with the same A and vars.
+ * Such a cone always runs on the streamed kernels (kernels_quad_structured.hip.h makes the products with Q: the factor
+ * dots on cone x factor x row segment workgroups, then one kernel over row tiles with 1, 8 or 64 lanes per row of S by
+ * the mean nonzeros per row -- CXK_QUAD_CSR_LANES = 1 | 8 | 64 overrides); it has no LDS form, so
+ * cxk_set_streamed_quadratic(ctx, 0) does NOT refuse it and it counts in cxk_count_streamed_quadratic whatever the
+ * mode.  Cones of equal (n, m, rank, with or without S) share a group even when their nonzero counts differ.  Every
+ * output, getter and setter is that of any quadratic cone.  No atomics, fixed summation orders: same bits every run.
+ * cxk_count_structured_quadratic: constraints this context owns that were added this way (-1 before cxk_finalize; 0 on
+ * a host-only context, which chooses no kernels). */
+int cxk_add_quadratic_structured(cxk_context* ctx, int n, int m,
+                                 const int* q_rowptr /* n + 1, or NULL: no sparse part */, const int* q_col, const double* q_val,
+                                 int rank, const double* F /* n x rank column-major, or NULL when rank = 0 */,
+                                 const double* sigma /* rank, NULL = all +1 */,
+                                 const double* A /* (n+1) x m */, const double* c /* n+1 */, const int* vars);
+int cxk_count_structured_quadratic(const cxk_context* ctx);
 
 /* Initialize(): symbolic analysis (SupernodalKKTSolver ctor kkt_solver.cc:104-116),
  * Bind (kkt_solver.h:26-33), workspace carve + SetIdentity (cone_program.cc:78-112),
