@@ -71,6 +71,8 @@ def api():
                                                   C.POINTER(C.c_long), ci]),
         "CONEX_HIP_AddStructuredQuadraticConstraint": (ci, [vp, ci, ip, ip, c_double_p, ci, c_double_p, c_double_p,
                                                             c_double_p, ci, ci, c_double_p, ci, C.POINTER(C.c_long), ci]),
+        "CONEX_HIP_AddSparseQuadraticConstraint": (ci, [vp, ci, c_double_p, ip, ip, c_double_p, ci, c_double_p, c_double_p,
+                                                        ip, ip, c_double_p, ci, ci, c_double_p, ci, C.POINTER(C.c_long), ci]),
         "CONEX_HIP_AddFactoredLMIConstraint": (ci, [vp, ci, c_double_p, ci, c_double_p, ip, ci, c_double_p,
                                                     C.POINTER(C.c_long)]),
         "CONEX_HIP_AddFactoredHermitianConstraint": (ci, [vp, ci, ci, c_double_p, ci, c_double_p, ip, ci, c_double_p,

@@ -102,15 +102,15 @@ void LinearNonzeros(ConstraintRec* c) {
     }
 }
 
-// The device copy of a group of linear blocks (rows = n) or second-order cones (rows = n + 1) on the sparse route:
-// every member's nonzeros by rows and by columns, into its family's lists.
+// The device copy of a group of linear blocks (rows = n), second-order cones on the sparse route or quadratic cones added
+// by their nonzeros (rows = n + 1): every member's nonzeros by rows and by columns, into its family's lists.
 int UploadSparseNonzeros(cxk_context* ctx, const Group& g, NonzeroLists& nz) {
-  const size_t cnt = g.ids.size(), rows = (size_t)g.n + (g.type == CXK_SOC ? 1 : 0), m = (size_t)g.m;
+  const size_t cnt = g.ids.size(), rows = (size_t)g.n + (g.type == CXK_LINEAR ? 0 : 1), m = (size_t)g.m;
   size_t total = 0;
   for (size_t k = 0; k < cnt; k++) total += ctx->cons[g.ids[k]].rows.col.size();
-  CXK_DEMAND(total <= (size_t)INT_MAX, g.type == CXK_SOC
-                                           ? "a group of sparse second-order cones with more than 2^31 nonzeros is not supported"
-                                           : "a group of sparse linear blocks with more than 2^31 nonzeros is not supported");
+  CXK_DEMAND(total <= (size_t)INT_MAX, g.type == CXK_QUAD ? "a group of quadratic cones added by cxk_add_quadratic_csr with more than 2^31 nonzeros is not supported"
+                                       : g.type == CXK_SOC ? "a group of sparse second-order cones with more than 2^31 nonzeros is not supported"
+                                                           : "a group of sparse linear blocks with more than 2^31 nonzeros is not supported");
   std::vector<int> eptr(cnt + 1, 0), rowptr(cnt * (rows + 1)), colptr(cnt * (m + 1), 0), col(total), crow(total);
   std::vector<double> val(total), cval(total);
   for (size_t k = 0; k < cnt; k++) {

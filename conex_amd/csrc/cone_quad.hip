@@ -1,11 +1,11 @@
 // Quadratic cones on their two routes (kQuadLds, kQuadStreamed): the views, the stages of cxk_finalize and every
-// launch.  Owns the kernels of kernels_quad / _quad_stream / _quad_structured; the streamed route's slack is the second-order
-// cones' kernel (cone_soc.hip: LaunchSocStreamSlack), the scaling point's identity the vector cones' (cone_linear.hip).
+// launch.  Owns the kernels of kernels_quad / _quad_stream / _quad_structured / _quad_sparse; the streamed route's slack is the second-order
+// cones' kernel (cone_soc.hip: LaunchSocStreamSlack, LaunchSocSparseSlack), the scaling point's identity the vector cones' (cone_linear.hip).
 // The family's state is Group::quad (cone_state.h).
 #include "cone_units.h"
 #include "kernels_gemm.hip.h"
 #include "kernels_quad.hip.h"
-#include "kernels_quad_structured.hip.h"  // (on top of kernels_quad_stream.hip.h, which it includes)
+#include "kernels_quad_sparse.hip.h"  // (on top of kernels_quad_structured.hip.h and kernels_quad_stream.hip.h, which it includes)
 
 namespace cxk_host {
 
@@ -106,7 +106,7 @@ int UploadQuadStream(cxk_context* ctx, Group& g, const FinalizeSwitches& sw) {
   CXK_TRY(g.quad.S.alloc((n + 1) * cnt));
   CXK_TRY(g.quad.vec.alloc(QuadStreamVecDoubles(cnt, n, m)));
   CXK_TRY(g.quad.part.alloc(g.quad.has_q ? cnt * (size_t)g.quad.splits * 2 * n : 0));
-  return QuadStreamConstants(ctx, g);
+  return g.quad.sa.on ? QuadSparseConstants(ctx, g) : QuadStreamConstants(ctx, g);
 }
 // soc_stream_slack serves the streamed quadratic cone as it is (same layout, same formula): what it reads of the group.
 SocStreamGroup QuadStreamSlackView(Group& g, const QuadStreamGroup& d) {
@@ -150,13 +150,13 @@ void LaunchQuadLdsSchur(Group& g, const Arena& ar, hipStream_t st) {
 // The Schur complement of a group of streamed quadratic cones: Q w1, the scalars, the columns, the block.
 hipError_t LaunchQuadStreamSchur(Group& g, const Arena& ar, hipStream_t st) {
   const QuadStreamGroup d = MakeQuadStream(g);
-  const int cnt = d.count, m = d.m;
+  const int cnt = d.count, m = d.m, a0s = g.quad.sa.on ? 1 : d.n + 1;  // (row 0 of A: dense count x m with a sparse A)
   hipError_t e = LaunchQuadStreamQmv<1>(g, d, QuadStreamOne(d.W + 1, (size_t)d.n + 1), st);
   if (e != hipSuccess) return e;
   quad_stream_schur_vectors<<<cnt, kQuadStreamBlock, 0, st>>>(d);
-  if (m > 0) quad_stream_schur_columns<<<(unsigned)((size_t)cnt * m), kQuadStreamBlock, 0, st>>>(d);
+  if (m > 0) LaunchQuadSchurColumns(g, d, st);
   const int blocks = (int)std::max<size_t>(1, ((size_t)m * m + kQuadStreamBlock - 1) / kQuadStreamBlock);
-  quad_stream_schur_finish<<<(unsigned)((size_t)cnt * blocks), kQuadStreamBlock, 0, st>>>(d, ar, blocks);
+  quad_stream_schur_finish<<<(unsigned)((size_t)cnt * blocks), kQuadStreamBlock, 0, st>>>(d, ar, blocks, g.quad.sa.on ? g.quad.sa.a0.p : d.A, a0s);
   return hipGetLastError();
 }
 
@@ -249,6 +249,38 @@ hipError_t LaunchQuadStructuredQmv(Group& g, const QuadStreamGroup& d, const Qua
   return hipGetLastError();
 }
 
+// The factors' share of A_gram from P = F' A1 (rank x m per cone): Ps = diag(sigma) P, A_gram += P' Ps (beta = 1; 0
+// without S).  Both forms of A end here: the dense one below, the one held by its nonzeros in QuadSparseConstants.
+static int QuadFactorGram(cxk_context* ctx, Group& g, const QuadStructured& q, int m, const double* P, double* Ps) {
+  const int cnt = q.count, rank = q.rank;
+  constexpr int kMaxBatch = 65535;  // gridDim.z
+  const size_t blocks = ((size_t)cnt * rank * m + kQuadStreamBlock - 1) / kQuadStreamBlock;
+  CXK_DEMAND(blocks <= (size_t)INT_MAX, "a group of structured quadratic cones with more than 2^39 entries of F' A is not supported");
+  quad_struct_scale_rows<<<(unsigned)blocks, kQuadStreamBlock, 0, ctx->stream>>>(q, P, m, Ps);
+  CXK_TRY(hipGetLastError());
+  for (int b0 = 0; b0 < cnt; b0 += kMaxBatch) {  // A_gram += P' Ps
+    const int nb = std::min(kMaxBatch, cnt - b0);
+    GemmArgs a{};
+    a.inner = 1;
+    a.alpha = 1.0;
+    a.beta = q.has_s ? 1.0 : 0.0;
+    a.splits = 1;
+    a.M = a.N = m;
+    a.K = rank;
+    a.A = P + (size_t)b0 * rank * m;
+    a.lda = rank;
+    a.sA1 = (int64_t)rank * m;
+    a.B = Ps + (size_t)b0 * rank * m;
+    a.ldb = rank;
+    a.sB1 = (int64_t)rank * m;
+    a.C = g.quad.Gram.p + (size_t)b0 * m * m;
+    a.ldc = m;
+    a.sC1 = (int64_t)m * m;
+    CXK_TRY(LaunchGemm(a, true, false, nb, ctx->stream));
+  }
+  return CXK_SUCCESS;
+}
+
 // A_gram = A1' Q A1 without forming Q:
 //   T = S A1 (n x m, lives for this call) by quad_struct_sa, A_gram = A1' T;
 //   P = F' A1 (rank x m), Ps = diag(sigma) P, A_gram += P' Ps (beta = 1; 0 without S).
@@ -309,32 +341,7 @@ static int QuadStructuredGram(cxk_context* ctx, Group& g, const QuadStreamGroup&
       CXK_TRY(LaunchGemm(a, true, false, nb, ctx->stream));
     }
   }
-  if (rank > 0) {
-    const size_t blocks = ((size_t)cnt * rank * m + kQuadStreamBlock - 1) / kQuadStreamBlock;
-    CXK_DEMAND(blocks <= (size_t)INT_MAX, "a group of structured quadratic cones with more than 2^39 entries of F' A is not supported");
-    quad_struct_scale_rows<<<(unsigned)blocks, kQuadStreamBlock, 0, ctx->stream>>>(q, P.p, m, Ps.p);
-    CXK_TRY(hipGetLastError());
-    for (int b0 = 0; b0 < cnt; b0 += kMaxBatch) {  // A_gram += P' Ps
-      const int nb = std::min(kMaxBatch, cnt - b0);
-      GemmArgs a{};
-      a.inner = 1;
-      a.alpha = 1.0;
-      a.beta = q.has_s ? 1.0 : 0.0;
-      a.splits = 1;
-      a.M = a.N = m;
-      a.K = rank;
-      a.A = P.p + (size_t)b0 * rank * m;
-      a.lda = rank;
-      a.sA1 = (int64_t)rank * m;
-      a.B = Ps.p + (size_t)b0 * rank * m;
-      a.ldb = rank;
-      a.sB1 = (int64_t)rank * m;
-      a.C = g.quad.Gram.p + (size_t)b0 * m * m;
-      a.ldc = m;
-      a.sC1 = (int64_t)m * m;
-      CXK_TRY(LaunchGemm(a, true, false, nb, ctx->stream));
-    }
-  }
+  if (rank > 0 && QuadFactorGram(ctx, g, q, m, P.p, Ps.p)) return CXK_FAILURE;
   CXK_TRY(hipStreamSynchronize(ctx->stream));  // (T, P and Ps are released on return)
   return CXK_SUCCESS;
 }
@@ -390,11 +397,140 @@ int UploadQuadStructured(cxk_context* ctx, Group& g, const FinalizeSwitches& sw)
   CXK_TRY(g.quad.S.alloc((n + 1) * cnt));
   CXK_TRY(g.quad.vec.alloc(QuadStreamVecDoubles(cnt, n, m)));
   CXK_TRY(g.quad.part.alloc(cnt * 2 * n));
+  if (g.quad.sa.on) return QuadSparseConstants(ctx, g);
   const QuadStreamGroup d = MakeQuadStream(g);
   CXK_TRY(LaunchQuadStreamQmv<1>(g, d, QuadStreamOne(d.c + 1, n + 1), ctx->stream));
   quad_stream_constants<<<(int)cnt, kQuadStreamBlock, 0, ctx->stream>>>(d);
   CXK_TRY(hipGetLastError());
   return QuadStructuredGram(ctx, g, d);
+}
+
+// ---- Streamed quadratic cones whose A is held by its nonzeros (cxk_add_quadratic_csr; the kernels of
+// kernels_quad_sparse.hip.h), whatever the form of Q.  Such a group is a streamed group in everything but the four
+// places that read A: the columns and row 0 of the assembly, the slack, and A_gram at finalize.  Nothing of
+// (n + 1) x m or n x m is allocated.
+
+// What those kernels read of the group (UploadQuadSparseA uploads it).
+QuadSparseGroup MakeQuadSparse(const Group& g) {
+  QuadSparseGroup s;
+  s.n = g.n;
+  s.m = g.m;
+  s.count = static_cast<int>(g.ids.size());
+  s.eptr = g.quad.sa.nz.eptr.p;
+  s.colptr = g.quad.sa.nz.colptr.p;
+  s.crow = g.quad.sa.nz.crow.p;
+  s.cval = g.quad.sa.nz.cval.p;
+  return s;
+}
+// The nonzeros by rows and by columns (the lists of the sparse second-order cones), and row 0 as a dense vector per cone.
+int UploadQuadSparseA(cxk_context* ctx, Group& g) {
+  const size_t cnt = g.ids.size(), m = (size_t)g.m;
+  CXK_DEMAND(cnt * (size_t)kQuadGramPanelMaxCols <= (size_t)INT_MAX,
+             "a group of quadratic cones added by cxk_add_quadratic_csr with more than 2^25 members is not supported");
+  if (UploadSparseNonzeros(ctx, g, g.quad.sa.nz)) return CXK_FAILURE;
+  std::vector<double> h0(cnt * m, 0.0);
+  for (size_t k = 0; k < cnt; k++) {
+    const ConstraintRec::RowNonzeros& r = ctx->cons[g.ids[k]].rows;
+    for (int s = r.ptr[0]; s < r.ptr[1]; s++) h0[k * m + (size_t)r.col[(size_t)s]] = r.val[(size_t)s];
+  }
+  CXK_TRY(g.quad.sa.a0.upload(h0));
+  return CXK_SUCCESS;
+}
+
+// v = A1' Q w1 + A0 W0 of an assembly.  A dense A: one workgroup per column, which forms u = A1' Q c1 beside it.  By
+// nonzeros: one wavefront per column through the CSC; u is constant and was made at finalize.
+void LaunchQuadSchurColumns(Group& g, const QuadStreamGroup& d, hipStream_t st) {
+  const size_t cols = (size_t)d.count * d.m;
+  if (!g.quad.sa.on) {
+    quad_stream_schur_columns<<<(unsigned)cols, kQuadStreamBlock, 0, st>>>(d);
+    return;
+  }
+  constexpr int per = kQuadSparseBlock / 64;  // columns per workgroup
+  quad_sparse_columns<<<(unsigned)((cols + per - 1) / per), kQuadSparseBlock, 0, st>>>(MakeQuadSparse(g), d.W, (size_t)d.n + 1, d.qw, d.v);
+}
+
+// The constants of such a group, once at cxk_finalize, on the device: Qc1 and c1' Q c1 as every streamed group's,
+// u = A1' Q c1 by the columns kernel on (0, Qc1), and A_gram = A1' Q A1 in panels of P columns of A1
+// (cone_route.h: QuadGramPanelCols).  Per panel: its columns scattered into a zeroed buffer of the dense form's layout
+// ((n + 1) x P per cone, row 0 unread), T = Q panel by the code of the dense A -- the GEMM for a dense Q, quad_struct_sa
+// for S, nothing for the identity (T is the panel) -- and A_gram[:, panel] = A1' T gathered through the CSC.  The
+// factors' F' A1 (rank x m) is not made panel by panel: a GEMM of M = rank, N = P and K = n is one workgroup's loop over
+// n (55 ms a panel at n = 2^20, measured); it is the same gather on T = F, once, nnz rank multiply-adds.  Their share of
+// A_gram follows once, as with a dense A; where Q is the factors alone there are no panels at all.
+int QuadSparseConstants(cxk_context* ctx, Group& g) {
+  const QuadStreamGroup d = MakeQuadStream(g);
+  const QuadSparseGroup s = MakeQuadSparse(g);
+  const int cnt = d.count, n = d.n, m = d.m, len = n + 1;
+  constexpr int per = kQuadSparseBlock / 64;
+  CXK_TRY(LaunchQuadStreamQmv<1>(g, d, QuadStreamOne(d.c + 1, (size_t)len), ctx->stream));
+  quad_stream_constants<<<cnt, kQuadStreamBlock, 0, ctx->stream>>>(d);
+  CXK_TRY(hipGetLastError());
+  if (m == 0) return CXK_SUCCESS;
+  const unsigned col_grid = (unsigned)(((size_t)cnt * m + per - 1) / per);
+  quad_sparse_columns<<<col_grid, kQuadSparseBlock, 0, ctx->stream>>>(s, nullptr, 0, d.qc1, d.u);
+  CXK_TRY(hipGetLastError());
+  const bool structured = d.q_form == kQuadQStructured;
+  QuadStructured q{};
+  if (structured) q = MakeQuadStructured(g, d);
+  const int rank = structured ? q.rank : 0;
+  const bool with_t = d.q_form == kQuadQDense || (structured && q.has_s);  // (else T is the panel, or A_gram is the factors' alone)
+  const bool gathers = with_t || d.q_form == kQuadQIdentity;
+  const int P = std::min(m, QuadGramPanelCols(n, cnt));
+  DevBuf<double> panel, T, Pf, Ps;
+  if (gathers) CXK_TRY(panel.alloc((size_t)cnt * P * len));
+  if (with_t) CXK_TRY(T.alloc((size_t)cnt * n * P));
+  if (rank > 0) {  // Pf = F' A1: entry (k, i) from column i of A1 and column k of F
+    CXK_TRY(Pf.alloc((size_t)cnt * rank * m));
+    CXK_TRY(Ps.alloc((size_t)cnt * rank * m));
+    quad_sparse_gather<<<col_grid, kQuadSparseBlock, 0, ctx->stream>>>(s, q.F, (size_t)n, (size_t)n * rank, rank, Pf.p, (size_t)rank * m,
+                                                                      (size_t)rank, 1);
+    CXK_TRY(hipGetLastError());
+  }
+  const int tiles = (n + kQuadStreamRowTile - 1) / kQuadStreamRowTile;
+  constexpr int kMaxBatch = 65535;  // gridDim.z
+  for (int j0 = 0; gathers && j0 < m; j0 += P) {
+    const int pw = std::min(P, m - j0);
+    CXK_TRY(hipMemsetAsync(panel.p, 0, sizeof(double) * (size_t)cnt * P * len, ctx->stream));
+    quad_sparse_scatter<<<(unsigned)(((size_t)cnt * pw + per - 1) / per), kQuadSparseBlock, 0, ctx->stream>>>(s, panel.p, j0, pw, P);
+    CXK_TRY(hipGetLastError());
+    if (structured && q.has_s) {  // T = S panel (the panel as an A of P columns)
+      const int ctiles = (pw + kQuadStructColTile - 1) / kQuadStructColTile;
+      CXK_DEMAND((size_t)cnt * tiles * ctiles <= (size_t)INT_MAX,
+                 "a group of structured quadratic cones with more than 2^31 row tiles x column tiles is not supported");
+      quad_struct_sa<<<(unsigned)((size_t)cnt * tiles * ctiles), kQuadStreamBlock, 0, ctx->stream>>>(q, panel.p, P, T.p, tiles, ctiles);
+      CXK_TRY(hipGetLastError());
+    }
+    for (int b0 = 0; d.q_form == kQuadQDense && b0 < cnt; b0 += kMaxBatch) {  // T = Q panel
+      const int nb = std::min(kMaxBatch, cnt - b0);
+      GemmArgs a{};
+      a.inner = 1;
+      a.alpha = 1.0;
+      a.beta = 0.0;
+      a.splits = 1;
+      a.M = n;
+      a.N = pw;
+      a.K = n;
+      a.A = g.quad.Q.p + (size_t)b0 * n * n;
+      a.lda = n;
+      a.sA1 = (int64_t)n * n;
+      a.B = panel.p + (size_t)b0 * len * P + 1;
+      a.ldb = len;
+      a.sB1 = (int64_t)len * P;
+      a.C = T.p + (size_t)b0 * n * P;
+      a.ldc = n;
+      a.sC1 = (int64_t)n * P;
+      CXK_TRY(LaunchGemm(a, false, false, nb, ctx->stream));
+    }
+    double* out = g.quad.Gram.p + (size_t)j0 * m;  // A_gram[i, j0 + jj]
+    if (with_t)
+      quad_sparse_gather<<<col_grid, kQuadSparseBlock, 0, ctx->stream>>>(s, T.p, (size_t)n, (size_t)n * P, pw, out, (size_t)m * m, 1, (size_t)m);
+    else
+      quad_sparse_gather<<<col_grid, kQuadSparseBlock, 0, ctx->stream>>>(s, panel.p + 1, (size_t)len, (size_t)len * P, pw, out, (size_t)m * m, 1, (size_t)m);
+    CXK_TRY(hipGetLastError());
+  }
+  if (rank > 0 && QuadFactorGram(ctx, g, q, m, Pf.p, Ps.p)) return CXK_FAILURE;
+  CXK_TRY(hipStreamSynchronize(ctx->stream));  // (the panel, T, F' A1 and its scaled copy are released on return)
+  return CXK_SUCCESS;
 }
 
 // PrepareStep (MODE 0) or the eigenvalue query (MODE 1) of one group.
@@ -406,7 +542,10 @@ int QuadPrepare(cxk_context* ctx, Group& g, const StepArgs& sa) {
     case ConeRoute::kQuadLds: quad_prepare<MODE><<<cnt, 64, QuadPrepareLds(g.n, g.m), ctx->stream>>>(MakeQuad(g), sa); break;
     case ConeRoute::kQuadStreamed: {
       const QuadStreamGroup d = MakeQuadStream(g);
-      LaunchSocStreamSlack(QuadStreamSlackView(g, d), sa, ctx->stream);
+      if (g.quad.sa.on)  // (A by its nonzeros: the sparse second-order cones' slack, on this group's rows and ms)
+        LaunchSocSparseSlack(MakeVec(g), d.ms, g.quad.sa.nz, sa, ctx->stream);
+      else
+        LaunchSocStreamSlack(QuadStreamSlackView(g, d), sa, ctx->stream);
       QuadStreamVecs x;  // Q [w1, ms1] in one pass
       x.p[0] = d.W + 1;
       x.p[1] = d.ms + 1;

@@ -121,6 +121,20 @@ inline int QuadFactorSegments(int n, long long columns) {
   return s < 1 ? 1 : (int)s;
 }
 
+// A quadratic cone whose A is held by its nonzeros (cxk_add_quadratic_csr, kernels_quad_sparse.hip.h) forms
+// A_gram = A1' Q A1 at cxk_finalize in panels of P columns of A1: the panel and T = Q panel, n x P each per cone, are
+// all the work space, whatever m is.  P from a fixed budget of bytes for the two buffers of the whole group, at least
+// kQuadGramPanelMinCols (the column tile of quad_struct_sa) and at most kQuadGramPanelMaxCols (a handful of launches
+// per 64 columns is amortised; a wider panel of a small cone would only cost memory).  Neither bound was tuned.
+constexpr long long kQuadGramPanelBytes = 256ll << 20;
+constexpr int kQuadGramPanelMinCols = 4;
+constexpr int kQuadGramPanelMaxCols = 64;
+inline int QuadGramPanelCols(int n, long long count) {
+  const long long per_col = 2 * 8 * (count > 0 ? count : 1) * (n > 0 ? n : 1);
+  const long long p = kQuadGramPanelBytes / per_col;
+  return p < kQuadGramPanelMinCols ? kQuadGramPanelMinCols : p > kQuadGramPanelMaxCols ? kQuadGramPanelMaxCols : (int)p;
+}
+
 // Automatic mode (cxk_set_sparse_affine(ctx, -1)) evaluates the affine term C of a sparse matrix inequality beyond
 // the LDS-resident orders from C's nonzeros (kernels_lmi_sparse.hip.h: lmi_affine_wc, lmi_affine_x) when
 // R (nnz_c + npos) <= 4 n^2: the two kernels make n nnz_c + n npos multiply-adds (npos: the distinct positions of
@@ -159,7 +173,8 @@ inline bool LmiLdsResident(int n, int m) { return LmiTakeLds(n) <= kLdsLimit && 
 struct ConeShape {
   int type = 0, n = 0, m = 0, herm_d = 0;  // CXK_LMI ..., the sizes as cxk_add_* took them
   bool symmetric = true;  // CXK_LMI: every A_i and C equals its transpose
-  // added by its nonzeros (no dense matrix); CXK_LMI given by factors; CXK_QUAD with an inner-product matrix
+  // added by its nonzeros (no dense matrix; CXK_QUAD: cxk_add_quadratic_csr, `nnz` below is set); CXK_LMI given by
+  // factors; CXK_QUAD with an inner-product matrix
   bool csr_only = false, factored = false, has_q = false;
   // the nonzeros of a linear block or a second-order cone, measured only while its sparse mode is not 0
   bool nnz_fits_int = true;  // their count is within the int range
@@ -288,12 +303,25 @@ inline RouteChoice ChooseQuad(const ConeShape& s, const RouteModes& md) {
   // held by the parts of Q: no LDS form, whatever the switch says; n x n is never formed, so only the nonzeros of S
   // (ints on the device, per group: UploadQuadStructured) and the two demands of every streamed cone remain
   if (s.q_structured) {
-    if (!EntriesFitInt((int64_t)s.n + 1, s.m))
+    if (!s.csr_only && !EntriesFitInt((int64_t)s.n + 1, s.m))
       return Refuse("a streamed quadratic cone whose (dimension + 1) x variables entries exceed the int range is not supported");
+    if (s.csr_only && s.nnz > (double)INT_MAX)
+      return Refuse("a quadratic cone added by cxk_add_quadratic_csr with more than 2^31 nonzeros is not supported");
     if (!SquareFitsInt(s.m))
       return Refuse("a streamed quadratic cone whose variables x variables Schur block exceeds the int range is not supported");
     if (s.q_nnz > (double)INT_MAX)
       return Refuse("a structured quadratic cone whose sparse part has more than 2^31 nonzeros is not supported");
+    return Take(ConeRoute::kQuadStreamed);
+  }
+  // held by the nonzeros of A (cxk_add_quadratic_csr; ConeShape::nnz counts them): no LDS form either, and nothing
+  // of (n + 1) x m exists to be indexed; the Schur block, a dense Q and the int pointers of the nonzeros remain
+  if (s.csr_only) {
+    if (!SquareFitsInt(s.m))
+      return Refuse("a streamed quadratic cone whose variables x variables Schur block exceeds the int range is not supported");
+    if (s.has_q && !SquareFitsInt(s.n))
+      return Refuse("a streamed quadratic cone whose inner-product matrix has more than 2^31 entries is not supported");
+    if (s.nnz > (double)INT_MAX)
+      return Refuse("a quadratic cone added by cxk_add_quadratic_csr with more than 2^31 nonzeros is not supported");
     return Take(ConeRoute::kQuadStreamed);
   }
   // quad_prepare keeps y and four vectors of the cone in LDS; quad_schur and quad_take_step need less

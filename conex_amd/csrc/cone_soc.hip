@@ -1,6 +1,6 @@
 // Second-order cones on their three routes (kSocLds, kSocStreamed, kSocSparse): the views, the stages of cxk_finalize
 // and every launch.  Owns the kernels of kernels_soc / _soc_stream / _soc_sparse; the streamed quadratic cones reach
-// soc_stream_slack through LaunchSocStreamSlack.  The family's state is Group::soc (cone_state.h).
+// soc_stream_slack through LaunchSocStreamSlack, soc_sparse_slack through LaunchSocSparseSlack.  The family's state is Group::soc (cone_state.h).
 #include "cone_units.h"
 #include "kernels_soc.hip.h"
 #include "kernels_soc_stream.hip.h"
@@ -169,6 +169,20 @@ int SocSparseConstants(cxk_context* ctx, Group& g) {
 void LaunchSocStreamSlack(const SocStreamGroup& d, const StepArgs& sa, hipStream_t st) {
   const int tiles = (d.v.len + kSocStreamRowTile - 1) / kSocStreamRowTile;
   soc_stream_slack<<<(unsigned)((size_t)d.v.count * tiles), kSocStreamBlock, 0, st>>>(d, sa, tiles);
+}
+
+// soc_sparse_slack serves a quadratic cone held by the nonzeros of A as it is (same rows, same formula): the view of
+// such a group it reads, v and the lists by rows, and where the slack goes.
+void LaunchSocSparseSlack(const VecGroup& v, double* ms, const NonzeroLists& nz, const StepArgs& sa, hipStream_t st) {
+  SocSparseGroup d{};
+  d.st.v = v;
+  d.st.ms = ms;
+  d.eptr = nz.eptr.p;
+  d.rowptr = nz.rowptr.p;
+  d.col = nz.col.p;
+  d.val = nz.val.p;
+  const int tiles = (v.len + kSocStreamRowTile - 1) / kSocStreamRowTile;
+  soc_sparse_slack<<<(unsigned)((size_t)v.count * tiles), kSocStreamBlock, 0, st>>>(d, sa, tiles);
 }
 
 // PrepareStep (MODE 0) or the eigenvalue query (MODE 1) of one group.

@@ -2,8 +2,9 @@
 // route has (Group) around one by-value state struct per cone family.  A family's struct is read and written in its own
 // unit only -- lin in cone_linear.hip, soc in cone_soc.hip, quad in cone_quad.hip, lmi in cone_lmi.hip (cone_units.h) --
 // but for:
-//   kkt_cone_launch.hip  GroupConstraints writes the group key (lmi.literal, quad.has_q, quad.sq.on / has_s / rank, lmi.f.R, lmi.sa.on);
-//                        UploadDenseData reads lmi.assembly; UploadGroup reads quad.sq.on; StepTailOk reads lmi.large and lmi.literal,
+//   kkt_cone_launch.hip  GroupConstraints writes the group key (lmi.literal, quad.has_q, quad.sq.on / has_s / rank, quad.sa.on,
+//                        lmi.f.R, lmi.sa.on);
+//                        UploadDenseData reads lmi.assembly; UploadGroup reads quad.sq.on and quad.sa.on; StepTailOk reads lmi.large and lmi.literal,
 //                        TakeStepFromDeviceOk lmi.large
 //   MakeVec              (cone_linear.hip) hands lin.T2 to every vector cone's kernels, the other families' included
 // Host code only, no device code.
@@ -152,6 +153,14 @@ struct CXK_LOCAL QuadState {
     DevBuf<double> val, F, sigma;
     DevBuf<double> tpart;  // count x 2 x rank x segs
   } sq;
+  // kQuadStreamed with A held by its nonzeros (cxk_add_quadratic_csr), whatever the form of Q: the kernels of
+  // kernels_quad_sparse.hip.h stand where the route reads A.  Group::A stays empty; row 0 of A is kept dense.  Members
+  // have their own patterns (nz.eptr); u = A1' Q c1 in `vec` is made once at cxk_finalize.
+  struct SparseA {
+    bool on = false;
+    NonzeroLists nz;
+    DevBuf<double> a0;  // count x m
+  } sa;
 };
 
 // Matrix inequalities: cone_lmi.hip.

@@ -77,6 +77,8 @@ CXK_LOCAL int LaunchSocPrepare(cxk_context* ctx, Group& g, int mode, const StepA
 CXK_LOCAL int LaunchSocTakeStep(cxk_context* ctx, Group& g, const StepArgs& sa);
 // soc_stream_slack on the rows of d.v into d.ms (the streamed quadratic cones: QuadStreamSlackView)
 CXK_LOCAL void LaunchSocStreamSlack(const SocStreamGroup& d, const StepArgs& sa, hipStream_t st);
+// soc_sparse_slack on the rows of `nz` (those of v) into ms (the quadratic cones held by the nonzeros of A)
+CXK_LOCAL void LaunchSocSparseSlack(const VecGroup& v, double* ms, const NonzeroLists& nz, const StepArgs& sa, hipStream_t st);
 
 // ---- cone_quad.hip
 CXK_LOCAL hipError_t RaiseQuadLdsLimits();
@@ -87,6 +89,12 @@ CXK_LOCAL int UploadQuadStructured(cxk_context* ctx, Group& g, const FinalizeSwi
 // ... and its pass out_r = Q x_r, which LaunchQuadStreamQmv hands over (defined behind it, in the same unit)
 template <int R>
 CXK_LOCAL hipError_t LaunchQuadStructuredQmv(Group& g, const cxk::QuadStreamGroup& d, const cxk::QuadStreamVecs& x, hipStream_t st);
+// a kQuadStreamed group whose A is held by its nonzeros (Group::quad.sa.on): the nonzeros and row 0, ahead of either
+// Upload above, which then form the constants from them (QuadSparseConstants)
+CXK_LOCAL int UploadQuadSparseA(cxk_context* ctx, Group& g);
+CXK_LOCAL int QuadSparseConstants(cxk_context* ctx, Group& g);
+// v (and, with a dense A, u) of an assembly: quad_stream_schur_columns, or quad_sparse_columns through the CSC
+CXK_LOCAL void LaunchQuadSchurColumns(Group& g, const cxk::QuadStreamGroup& d, hipStream_t st);
 CXK_LOCAL void LaunchQuadLdsSchur(Group& g, const Arena& ar, hipStream_t st);
 hipError_t LaunchQuadStreamSchur(Group& g, const Arena& ar, hipStream_t st);
 CXK_LOCAL int LaunchQuadPrepare(cxk_context* ctx, Group& g, int mode, const StepArgs& sa);

@@ -34,7 +34,7 @@ enum QuadQForm { kQuadQIdentity = 0, kQuadQDense = 1, kQuadQStructured = 2 };
 struct QuadStreamGroup {
   int n, m, count, splits;
   int q_form;           // QuadQForm; kQuadQStructured: Q = S + F diag(sigma) F' (kernels_quad_structured.hip.h), splits = 1
-  const double* A;      // count x (n + 1) x m
+  const double* A;      // count x (n + 1) x m; nullptr where A is held by its nonzeros (kernels_quad_sparse.hip.h)
   const double* c;      // count x (n + 1)
   const double* Q;      // count x n x n; nullptr unless q_form is kQuadQDense
   const double* Agram;  // count x m x m
@@ -47,7 +47,7 @@ struct QuadStreamGroup {
   double* cqc;          // count                    c1' Q c1 (constant)
   double* qw;           // count x n                Q w1 of the last assembly
   double* v;            // count x m                A1' Q w1 + A0 W0
-  double* u;            // count x m                A1' Q c1
+  double* u;            // count x m                A1' Q c1 (of every assembly; constant, made once, with a sparse A)
   double* ms;           // count x (n + 1)          minus the slack
   double* dv;           // count x n                d1 of PrepareStep / the query
   double* qd;           // count x n                Q d1 as PrepareStep left it (TakeStep reads it)
@@ -188,13 +188,16 @@ __global__ void __launch_bounds__(kQuadStreamBlock) quad_stream_schur_columns(Qu
 
 // ---- stage 3: G (the full square), AW, AQc and the two scalars from v, u, A_gram and the scalars, by
 // quad_schur's expressions.  Grid: cone x `blocks` workgroups of 256 entries of G; the first of a cone also
-// writes AW, AQc and the scalars.
-__global__ void __launch_bounds__(kQuadStreamBlock) quad_stream_schur_finish(QuadStreamGroup g, Arena ar, int blocks) {
+// writes AW, AQc and the scalars.  Row 0 of A comes as a pointer and the stride between its entries: (g.A, n + 1) where
+// A is dense, a count x m vector with stride 1 where A is held by its nonzeros (kernels_quad_sparse.hip.h).
+__global__ void __launch_bounds__(kQuadStreamBlock) quad_stream_schur_finish(QuadStreamGroup g, Arena ar, int blocks, const double* a0,
+                                                                             int a0_stride) {
   const int n = g.n, m = g.m, len = n + 1, tid = threadIdx.x;
   const size_t mem = blockIdx.x / blocks;
   const int blk = (int)(blockIdx.x % blocks);
   const int id = g.ids[mem];
-  const double* A = g.A + mem * len * m;
+  const size_t a0s = (size_t)a0_stride;
+  const double* A0 = a0 + mem * m * a0s;
   const double* c = g.c + mem * len;
   const double* Agram = g.Agram + mem * m * m;
   const double* v = g.v + mem * m;
@@ -205,14 +208,14 @@ __global__ void __launch_bounds__(kQuadStreamBlock) quad_stream_schur_finish(Qua
   const long long idx = (long long)blk * kQuadStreamBlock + tid;
   if (idx < (long long)m * m) {
     const int i = (int)(idx % m), j = (int)(idx / m);
-    double t = (A[(size_t)i * len] * A[(size_t)j * len] - Agram[idx]) * -det_w;
+    double t = (A0[i * a0s] * A0[j * a0s] - Agram[idx]) * -det_w;
     t += v[i] * v[j];
     t += v[i] * v[j];
     G[idx] = t * 2;
   }
   if (blk != 0) return;
   for (int i = tid; i < m; i += kQuadStreamBlock) {
-    double q = det_w * (u[i] - A[(size_t)i * len] * C0);
+    double q = det_w * (u[i] - A0[i * a0s] * C0);
     q += 2 * v[i] * scale;
     ar.AWc[ar.r_off[id] + i] = v[i] * 2;
     ar.AQcc[ar.r_off[id] + i] = q * 2;

@@ -186,7 +186,7 @@ static void MeasureNonzeros(ConstraintRec* c, ConeShape* s) {
 // cxk_finalize fails with); constraints of one shape on one route form a group, numbered by first appearance.
 int GroupConstraints(cxk_context* ctx, const FinalizeSwitches& sw) {
   const int K = (int)ctx->cons.size();
-  std::map<std::tuple<int, int, int, int, ConeRoute, bool, bool, int, bool, bool, int, int>, int> gmap;
+  std::map<std::tuple<int, int, int, int, ConeRoute, bool, bool, int, bool, bool, int, int, bool>, int> gmap;
   ctx->groups.clear();
   ctx->sparse_soc_setup_ms = 0;
   // what the context was told (-1 / -2: nothing) goes in front of the environment's word
@@ -209,6 +209,7 @@ int GroupConstraints(cxk_context* ctx, const FinalizeSwitches& sw) {
     s.q_structured = c.sq.given;
     s.q_nnz = (double)c.sq.col.size();
     s.q_rank = c.sq.rank;
+    if (c.type == CXK_QUAD && c.csr_only) s.nnz = (double)c.rows.col.size();
     const int sparse_mode = c.type == CXK_LINEAR ? modes.sparse_linear : c.type == CXK_SOC ? modes.sparse_soc : 0;
     if (sparse_mode != 0 && !c.csr_only) MeasureNonzeros(&c, &s);
     if (c.type == CXK_LMI && !c.factors.given) MeasureLmi(c, &s);
@@ -227,8 +228,10 @@ int GroupConstraints(cxk_context* ctx, const FinalizeSwitches& sw) {
     // the form of a quadratic cone's Q: 0 dense or none (has_q), else structured with (2) or without (1) a sparse part,
     // and the rank; the nonzero counts of the members may differ
     const int q_form = c.sq.given ? (c.sq.ptr.empty() ? 1 : 2) : 0;
+    // the form of a quadratic cone's A: dense, or its nonzeros (cxk_add_quadratic_csr); the patterns of the members may differ
+    const bool a_csr = c.type == CXK_QUAD && c.csr_only;
     const auto key = std::make_tuple(c.type, c.n, c.m, c.herm_d, c.route, literal, s.has_q, f_R, c.entries.sparse_affine, c.entries.fold,
-                                     q_form, c.sq.rank);
+                                     q_form, c.sq.rank, a_csr);
     auto it = gmap.find(key);
     if (it == gmap.end()) {
       it = gmap.emplace(key, (int)ctx->groups.size()).first;
@@ -244,6 +247,7 @@ int GroupConstraints(cxk_context* ctx, const FinalizeSwitches& sw) {
       g.quad.sq.on = c.sq.given;
       g.quad.sq.has_s = q_form == 2;
       g.quad.sq.rank = c.sq.rank;
+      g.quad.sa.on = a_csr;
       g.lmi.f.R = f_R;
       g.lmi.sa.on = c.entries.sparse_affine;
       g.lmi.sp.fold = c.entries.fold;
@@ -263,7 +267,7 @@ int UploadGroup(cxk_context* ctx, Group& g, const FinalizeSwitches& sw) {
   if (g.type == CXK_LMI && PlanLmiGroup(ctx, g, sw)) return CXK_FAILURE;
   // the routes that hold their data as nonzeros or factors keep no dense copy of A on the device
   const bool dense_a = g.route != ConeRoute::kLmiSparse && g.route != ConeRoute::kLmiFactored &&
-                       g.route != ConeRoute::kLinearSparse && g.route != ConeRoute::kSocSparse;
+                       g.route != ConeRoute::kLinearSparse && g.route != ConeRoute::kSocSparse && !g.quad.sa.on;
   if (UploadDenseData(ctx, g, dense_a ? sz.a : 0, sz.c)) return CXK_FAILURE;
   CXK_TRY(g.W.alloc(sz.w * cnt));
   CXK_TRY(g.T1.alloc(sz.w * cnt));
@@ -277,7 +281,9 @@ int UploadGroup(cxk_context* ctx, Group& g, const FinalizeSwitches& sw) {
     case ConeRoute::kSocStreamed: return UploadSocStream(ctx, g, sw);
     case ConeRoute::kSocSparse: return UploadSocSparse(ctx, g);
     case ConeRoute::kQuadLds: return UploadQuadGram(ctx, g);
-    case ConeRoute::kQuadStreamed: return g.quad.sq.on ? UploadQuadStructured(ctx, g, sw) : UploadQuadStream(ctx, g, sw);
+    case ConeRoute::kQuadStreamed:
+      if (g.quad.sa.on && UploadQuadSparseA(ctx, g)) return CXK_FAILURE;  // (the nonzeros of A first: the constants read them)
+      return g.quad.sq.on ? UploadQuadStructured(ctx, g, sw) : UploadQuadStream(ctx, g, sw);
     case ConeRoute::kLmiDense: return UploadLmiDense(ctx, g, sw);
     case ConeRoute::kLmiSparse: return UploadLmiSparse(ctx, g);
     case ConeRoute::kLmiFactored: return UploadLmiFactored(ctx, g);

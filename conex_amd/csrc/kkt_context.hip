@@ -712,6 +712,47 @@ int cxk_add_quadratic(cxk_context* ctx, int n, int m, const double* Q, const dou
   return AddConstraint(ctx, std::move(r), vars);
 }
 
+// The parts of Q = S + F diag(sigma) F' as cxk_add_quadratic_structured and cxk_add_quadratic_csr take them (n >= 1):
+// why they are refused, or null.
+static const char* StructuredQRefusal(int n, const int* q_rowptr, const int* q_col, const double* q_val, int rank, const double* F,
+                                      const double* sigma) {
+  if (rank < 0) return "rank is negative";
+  if (!q_rowptr && rank == 0) return "neither a sparse part nor factors: for the identity pass Q = NULL to cxk_add_quadratic";
+  if (rank > 0 && !F) return "F is null";
+  if (q_rowptr) {
+    if (q_rowptr[0] != 0) return "q_rowptr[0] is not 0";
+    for (int r = 0; r < n; r++)
+      if (q_rowptr[r + 1] < q_rowptr[r]) return "q_rowptr decreases";
+    if (q_rowptr[n] > 0 && (!q_col || !q_val)) return "q_col or q_val is null";
+    for (int e = 0; e < q_rowptr[n]; e++) {
+      if (q_col[e] < 0 || q_col[e] >= n) return "a column of the sparse part is outside [0, n)";
+      if (!std::isfinite(q_val[e])) return "q_val holds a value that is not finite";
+    }
+  }
+  const size_t nr = (size_t)n * rank;
+  for (size_t q = 0; q < nr; q++)
+    if (!std::isfinite(F[q])) return "F holds a value that is not finite";
+  for (int k = 0; sigma && k < rank; k++)
+    if (!std::isfinite(sigma[k])) return "sigma holds a value that is not finite";
+  return nullptr;
+}
+// ... and the record's copy of them, once they have passed.
+static void KeepStructuredQ(ConstraintRec* r, int n, const int* q_rowptr, const int* q_col, const double* q_val, int rank,
+                            const double* F, const double* sigma) {
+  r->sq.given = true;
+  r->sq.rank = rank;
+  if (q_rowptr) {  // as given: duplicates stay, the kernels sum them
+    r->sq.ptr.assign(q_rowptr, q_rowptr + n + 1);
+    r->sq.col.assign(q_col, q_col + q_rowptr[n]);
+    r->sq.val.assign(q_val, q_val + q_rowptr[n]);
+  }
+  if (rank > 0) r->sq.F.assign(F, F + (size_t)n * rank);
+  if (sigma)
+    r->sq.sigma.assign(sigma, sigma + rank);
+  else
+    r->sq.sigma.assign((size_t)rank, 1.0);
+}
+
 int cxk_add_quadratic_structured(cxk_context* ctx, int n, int m, const int* q_rowptr, const int* q_col, const double* q_val,
                                  int rank, const double* F, const double* sigma, const double* A, const double* c,
                                  const int* vars) {
@@ -722,44 +763,69 @@ int cxk_add_quadratic_structured(cxk_context* ctx, int n, int m, const int* q_ro
   };
   if (n < 1 || m < 0) return refuse("n is at least 1 and m at least 0");
   if (!A || !c) return refuse("A or c is null");
-  if (rank < 0) return refuse("rank is negative");
-  if (!q_rowptr && rank == 0)
-    return refuse("neither a sparse part nor factors: for the identity pass Q = NULL to cxk_add_quadratic");
-  if (rank > 0 && !F) return refuse("F is null");
-  if (q_rowptr) {
-    if (q_rowptr[0] != 0) return refuse("q_rowptr[0] is not 0");
-    for (int r = 0; r < n; r++)
-      if (q_rowptr[r + 1] < q_rowptr[r]) return refuse("q_rowptr decreases");
-    if (q_rowptr[n] > 0 && (!q_col || !q_val)) return refuse("q_col or q_val is null");
-    for (int e = 0; e < q_rowptr[n]; e++) {
-      if (q_col[e] < 0 || q_col[e] >= n) return refuse("a column of the sparse part is outside [0, n)");
-      if (!std::isfinite(q_val[e])) return refuse("q_val holds a value that is not finite");
-    }
-  }
-  const size_t nr = (size_t)n * rank;
-  for (size_t q = 0; q < nr; q++)
-    if (!std::isfinite(F[q])) return refuse("F holds a value that is not finite");
-  for (int k = 0; sigma && k < rank; k++)
-    if (!std::isfinite(sigma[k])) return refuse("sigma holds a value that is not finite");
+  if (const char* why = StructuredQRefusal(n, q_rowptr, q_col, q_val, rank, F, sigma)) return refuse(why);
   ConstraintRec r;
   r.type = CXK_QUAD;
   r.n = n;
   r.m = m;
   r.A.assign(A, A + (size_t)(n + 1) * m);
   r.C.assign(c, c + n + 1);
-  r.sq.given = true;
-  r.sq.rank = rank;
-  if (q_rowptr) {  // as given: duplicates stay, the kernels sum them
-    r.sq.ptr.assign(q_rowptr, q_rowptr + n + 1);
-    r.sq.col.assign(q_col, q_col + q_rowptr[n]);
-    r.sq.val.assign(q_val, q_val + q_rowptr[n]);
-  }
-  if (rank > 0) r.sq.F.assign(F, F + nr);
-  if (sigma)
-    r.sq.sigma.assign(sigma, sigma + rank);
-  else
-    r.sq.sigma.assign((size_t)rank, 1.0);
+  KeepStructuredQ(&r, n, q_rowptr, q_col, q_val, rank, F, sigma);
   return AddConstraint(ctx, std::move(r), vars);
+}
+
+int cxk_add_quadratic_csr(cxk_context* ctx, int n, int m, const double* Q, const int* q_rowptr, const int* q_col, const double* q_val,
+                          int rank, const double* F, const double* sigma, const int* a_rowptr, const int* a_col, const double* a_val,
+                          const double* c, const int* vars) {
+  if (!ctx) return -1;
+  auto refuse = [ctx](const char* msg) {
+    ctx->err = std::string("cxk_add_quadratic_csr: ") + msg;
+    return -1;
+  };
+  if (n < 1 || n == INT_MAX || m < 0) return refuse("n is at least 1 and m at least 0");
+  if (!a_rowptr || !c) return refuse("a_rowptr or c is null");
+  const bool parts = q_rowptr || rank != 0 || F || sigma;
+  if (Q && parts) return refuse("Q is given dense and by its parts: one form, or none for the identity");
+  if (parts)
+    if (const char* why = StructuredQRefusal(n, q_rowptr, q_col, q_val, rank, F, sigma)) return refuse(why);
+  if (Q && (int64_t)n * n > INT_MAX) return refuse("a dense Q of more than 2^31 entries: give it by its parts");
+  for (size_t q = 0; Q && q < (size_t)n * n; q++)
+    if (!std::isfinite(Q[q])) return refuse("Q holds a value that is not finite");
+  const int rows = n + 1;
+  if (a_rowptr[0] != 0) return refuse("a_rowptr[0] is not 0");
+  for (int r = 0; r < rows; r++)
+    if (a_rowptr[r + 1] < a_rowptr[r]) return refuse("a_rowptr decreases");
+  if (a_rowptr[rows] > 0 && (!a_col || !a_val)) return refuse("a_col or a_val is null");
+  for (int r = 0; r < rows; r++)
+    if (!std::isfinite(c[r])) return refuse("c holds a value that is not finite");
+  ConstraintRec rec;
+  rec.type = CXK_QUAD;
+  rec.n = n;
+  rec.m = m;
+  rec.csr_only = true;
+  rec.C.assign(c, c + rows);
+  rec.rows.ptr.assign((size_t)rows + 1, 0);
+  std::vector<std::pair<int, double>> row;
+  for (int r = 0; r < rows; r++) {
+    row.clear();
+    for (int s = a_rowptr[r]; s < a_rowptr[r + 1]; s++) {
+      if (a_col[s] < 0 || a_col[s] >= m) return refuse("a column is outside [0, m)");
+      if (!std::isfinite(a_val[s])) return refuse("a_val holds a value that is not finite");
+      row.emplace_back(a_col[s], a_val[s]);
+    }
+    std::sort(row.begin(), row.end(), [](const std::pair<int, double>& a, const std::pair<int, double>& b) { return a.first < b.first; });
+    for (size_t s = 1; s < row.size(); s++)
+      if (row[s].first == row[s - 1].first) return refuse("a row names a column twice");
+    for (const auto& e : row)
+      if (e.second != 0.0) {  // explicit zeros are dropped
+        rec.rows.col.push_back(e.first);
+        rec.rows.val.push_back(e.second);
+      }
+    rec.rows.ptr[(size_t)r + 1] = (int)rec.rows.col.size();
+  }
+  if (Q) rec.Q.assign(Q, Q + (size_t)n * n);
+  if (parts) KeepStructuredQ(&rec, n, q_rowptr, q_col, q_val, rank, F, sigma);
+  return AddConstraint(ctx, std::move(rec), vars);
 }
 
 int cxk_add_static(cxk_context* ctx, int m, const double* G, const int* vars) {
@@ -933,6 +999,14 @@ int cxk_count_structured_quadratic(const cxk_context* ctx) {
   if (!ctx || !ctx->finalized) return -1;
   int k = 0;
   for (size_t i = 0; i < ctx->cons.size(); i++) k += ctx->owned[i] && ctx->cons[i].route == ConeRoute::kQuadStreamed && ctx->cons[i].sq.given;
+  return k;
+}
+
+int cxk_count_sparse_quadratic(const cxk_context* ctx) {
+  if (!ctx || !ctx->finalized) return -1;
+  int k = 0;
+  for (size_t i = 0; i < ctx->cons.size(); i++)
+    k += ctx->owned[i] && ctx->cons[i].route == ConeRoute::kQuadStreamed && ctx->cons[i].type == CXK_QUAD && ctx->cons[i].csr_only;
   return k;
 }
 

@@ -69,6 +69,11 @@ struct Cone {
   int q_rank = 0;
   std::vector<int> q_ptr, q_col;
   std::vector<double> q_val;
+  // kQuadCone added by CONEX_HIP_AddSparseQuadraticConstraint: the (order + 1) x cols matrix by its nonzeros in CSR
+  // (row 0 is A0), columns ascending within a row, no explicit zeros; `A` stays empty and is never formed
+  bool sparse_a = false;
+  std::vector<int> a_ptr, a_col;
+  std::vector<double> a_val;
   // kLmi added by CONEX_HIP_AddFactoredLMIConstraint: A_v = sum_k sigma[k] f_k f_k', k in rank_ptr[v] .. rank_ptr[v + 1] - 1,
   // f_k the columns of F (order x rank_ptr.back()); `mats` stays empty, `affine` holds C.  Added by
   // CONEX_HIP_AddFactoredHermitianConstraint (`hermitian` set): F and `affine` hold `hyper` planes
@@ -236,6 +241,14 @@ int BuildContext(Program* p) {
         id = cxk_add_static(p->ctx, m, c.A.data(), c.vars.data());
         break;
       case kQuadCone:
+        if (c.sparse_a) {  // the nonzeros go to the device as they are, with whatever form Q has
+          id = cxk_add_quadratic_csr(p->ctx, c.order, m, c.Q.empty() ? nullptr : c.Q.data(),
+                                     c.structured_q && !c.q_ptr.empty() ? c.q_ptr.data() : nullptr, c.q_col.data(), c.q_val.data(),
+                                     c.q_rank, c.q_rank > 0 ? c.F.data() : nullptr, c.q_rank > 0 ? c.sigma.data() : nullptr,
+                                     c.a_ptr.data(), c.a_col.data(), c.a_val.data(), c.c.data(), c.vars.data());
+          CONEX_DEMAND(id >= 0, cxk_last_error(p->ctx));
+          break;
+        }
         if (c.structured_q) {  // the parts go to the device as they are
           id = cxk_add_quadratic_structured(p->ctx, c.order, m, c.q_ptr.empty() ? nullptr : c.q_ptr.data(), c.q_col.data(),
                                             c.q_val.data(), c.q_rank, c.q_rank > 0 ? c.F.data() : nullptr,
@@ -1291,42 +1304,112 @@ int CONEX_HIP_AddQuadraticConstraint(void* x, const double* Q, int n, const doub
  * given; NULL: no sparse part), F n x rank column-major (NULL when rank = 0), sigma rank entries (NULL: all +1).  Not
  * both parts absent.  A, c and vars as for CONEX_HIP_AddQuadraticConstraint.  Returns the constraint id, -1 on
  * invalid arguments (among them a decreasing q_rowptr, a column outside [0, n), a value that is not finite). */
+static bool TakeStructuredQ(Cone* k, int n, const int* q_rowptr, const int* q_col, const double* q_val, int rank, const double* F,
+                            const double* sigma) {
+  if (rank < 0 || (rank > 0 && !F) || (!q_rowptr && rank == 0)) return false;
+  k->structured_q = true;
+  k->q_rank = rank;
+  if (q_rowptr) {
+    if (q_rowptr[0] != 0) return false;
+    for (int r = 0; r < n; r++)
+      if (q_rowptr[r + 1] < q_rowptr[r]) return false;
+    const int nnz = q_rowptr[n];
+    if (nnz > 0 && (!q_col || !q_val)) return false;
+    for (int e = 0; e < nnz; e++)
+      if (q_col[e] < 0 || q_col[e] >= n || !std::isfinite(q_val[e])) return false;
+    k->q_ptr.assign(q_rowptr, q_rowptr + n + 1);
+    k->q_col.assign(q_col, q_col + nnz);
+    k->q_val.assign(q_val, q_val + nnz);
+  }
+  const size_t nr = (size_t)n * rank;
+  for (size_t q = 0; q < nr; q++)
+    if (!std::isfinite(F[q])) return false;
+  for (int j = 0; sigma && j < rank; j++)
+    if (!std::isfinite(sigma[j])) return false;
+  if (rank > 0) k->F.assign(F, F + nr);
+  if (sigma)
+    k->sigma.assign(sigma, sigma + rank);
+  else
+    k->sigma.assign((size_t)rank, 1.0);
+  return true;
+}
+
 int CONEX_HIP_AddStructuredQuadraticConstraint(void* x, int n, const int* q_rowptr, const int* q_col, const double* q_val,
                                                int rank, const double* F, const double* sigma, const double* A, int Ar,
                                                int Ac, const double* c, int cr, const long* vars, int num_vars) {
   Program* p = static_cast<Program*>(x);
   if (!p || p->magic != 0xC0DEC0DEu || n < 1 || !A || !c || Ar != n + 1 || cr != n + 1 || Ac < 1) return -1;
   if (vars ? num_vars != Ac : Ac != p->num_vars) return -1;
-  if (rank < 0 || (rank > 0 && !F) || (!q_rowptr && rank == 0)) return -1;
   Cone k;
   k.kind = kQuadCone;
   k.order = n;
   k.cols = Ac;
-  k.structured_q = true;
-  k.q_rank = rank;
-  if (q_rowptr) {
-    if (q_rowptr[0] != 0) return -1;
-    for (int r = 0; r < n; r++)
-      if (q_rowptr[r + 1] < q_rowptr[r]) return -1;
-    const int nnz = q_rowptr[n];
-    if (nnz > 0 && (!q_col || !q_val)) return -1;
-    for (int e = 0; e < nnz; e++)
-      if (q_col[e] < 0 || q_col[e] >= n || !std::isfinite(q_val[e])) return -1;
-    k.q_ptr.assign(q_rowptr, q_rowptr + n + 1);
-    k.q_col.assign(q_col, q_col + nnz);
-    k.q_val.assign(q_val, q_val + nnz);
-  }
-  const size_t nr = (size_t)n * rank;
-  for (size_t q = 0; q < nr; q++)
-    if (!std::isfinite(F[q])) return -1;
-  for (int j = 0; sigma && j < rank; j++)
-    if (!std::isfinite(sigma[j])) return -1;
-  if (rank > 0) k.F.assign(F, F + nr);
-  if (sigma)
-    k.sigma.assign(sigma, sigma + rank);
-  else
-    k.sigma.assign((size_t)rank, 1.0);
+  if (!TakeStructuredQ(&k, n, q_rowptr, q_col, q_val, rank, F, sigma)) return -1;
   k.A.assign(A, A + (size_t)(n + 1) * Ac);
+  k.c.assign(c, c + n + 1);
+  if (vars) {
+    for (int i = 0; i < Ac; i++) {
+      if (vars[i] < 0 || vars[i] >= p->num_vars) return -1;
+      k.vars.push_back((int)vars[i]);
+    }
+  } else {
+    k.vars = AllVars(*p);
+  }
+  return AddCone(p, std::move(k));
+}
+
+/* not part of conex.h: the cone of CONEX_HIP_AddQuadraticConstraint or CONEX_HIP_AddStructuredQuadraticConstraint with its
+ * (n + 1) x Ac matrix given by its nonzeros and never formed (cxk_add_quadratic_csr): a_rowptr has Ar + 1 = n + 2 entries
+ * from 0 (row 0 is A0), a_col the columns in [0, Ac) in any order within a row, a_val the values; explicit zeros are
+ * dropped.  Q: n x n dense (Q), or its parts as CONEX_HIP_AddStructuredQuadraticConstraint takes them, or neither (the
+ * identity); not both.  c and vars as there.  Returns the constraint id, -1 on invalid arguments (among them a
+ * decreasing a_rowptr, a column outside [0, Ac) or named twice in a row, a value that is not finite).  The program keeps
+ * the nonzeros only. */
+int CONEX_HIP_AddSparseQuadraticConstraint(void* x, int n, const double* Q, const int* q_rowptr, const int* q_col,
+                                           const double* q_val, int rank, const double* F, const double* sigma,
+                                           const int* a_rowptr, const int* a_col, const double* a_val, int Ar, int Ac,
+                                           const double* c, int cr, const long* vars, int num_vars) {
+  Program* p = static_cast<Program*>(x);
+  if (!p || p->magic != 0xC0DEC0DEu || n < 1 || n == INT_MAX || !a_rowptr || !c || Ar != n + 1 || cr != n + 1 || Ac < 1) return -1;
+  if (vars ? num_vars != Ac : Ac != p->num_vars) return -1;
+  const bool parts = q_rowptr || rank != 0 || F || sigma;
+  if (Q && parts) return -1;
+  Cone k;
+  k.kind = kQuadCone;
+  k.order = n;
+  k.cols = Ac;
+  k.sparse_a = true;
+  if (parts && !TakeStructuredQ(&k, n, q_rowptr, q_col, q_val, rank, F, sigma)) return -1;
+  if (Q) {
+    if ((long long)n * n > INT_MAX) return -1;
+    for (size_t q = 0; q < (size_t)n * n; q++)
+      if (!std::isfinite(Q[q])) return -1;
+    k.Q.assign(Q, Q + (size_t)n * n);
+  }
+  if (a_rowptr[0] != 0) return -1;
+  for (int r = 0; r < Ar; r++)
+    if (a_rowptr[r + 1] < a_rowptr[r]) return -1;
+  if (a_rowptr[Ar] > 0 && (!a_col || !a_val)) return -1;
+  k.a_ptr.assign((size_t)Ar + 1, 0);
+  std::vector<std::pair<int, double>> row;
+  for (int r = 0; r < Ar; r++) {
+    row.clear();
+    for (int s = a_rowptr[r]; s < a_rowptr[r + 1]; s++) {
+      if (a_col[s] < 0 || a_col[s] >= Ac || !std::isfinite(a_val[s])) return -1;
+      row.emplace_back(a_col[s], a_val[s]);
+    }
+    std::sort(row.begin(), row.end(), [](const std::pair<int, double>& a, const std::pair<int, double>& b) { return a.first < b.first; });
+    for (size_t s = 1; s < row.size(); s++)
+      if (row[s].first == row[s - 1].first) return -1;
+    for (const auto& e : row)
+      if (e.second != 0.0) {
+        k.a_col.push_back(e.first);
+        k.a_val.push_back(e.second);
+      }
+    k.a_ptr[(size_t)r + 1] = (int)k.a_col.size();
+  }
+  for (int r = 0; r <= n; r++)
+    if (!std::isfinite(c[r])) return -1;
   k.c.assign(c, c + n + 1);
   if (vars) {
     for (int i = 0; i < Ac; i++) {

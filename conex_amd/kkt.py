@@ -138,6 +138,9 @@ _SIGNATURES = {
     "cxk_add_quadratic_structured": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_int_p, c_int_p, c_double_p, C.c_int, c_double_p,
                                                c_double_p, c_double_p, c_double_p, c_int_p]),
     "cxk_count_structured_quadratic": (C.c_int, [C.c_void_p]),
+    "cxk_add_quadratic_csr": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_double_p, c_int_p, c_int_p, c_double_p, C.c_int, c_double_p,
+                                        c_double_p, c_int_p, c_int_p, c_double_p, c_double_p, c_int_p]),
+    "cxk_count_sparse_quadratic": (C.c_int, [C.c_void_p]),
     "cxk_set_tiled_linear": (C.c_int, [C.c_void_p, C.c_int]),
     "cxk_set_sparse_linear": (C.c_int, [C.c_void_p, C.c_int]),
     "cxk_count_sparse_linear": (C.c_int, [C.c_void_p]),
@@ -206,31 +209,70 @@ class KktError(RuntimeError):
     pass
 
 
-def structured_q_parts(S, n):
-    """(indptr, indices, data) as contiguous int32 / int32 / float64 arrays of the sparse part of a structured Q of order
-    n, or (None, None, None): S is None, a triple, or any object with the attributes indptr, indices and data (a scipy CSR
-    matrix; scipy itself is not needed)."""
-    if S is None:
-        return None, None, None
+def csr_triple(S, rows, name="S"):
+    """(indptr, indices, data) as contiguous int32 / int32 / float64 arrays of a matrix of `rows` rows held in CSR: S is a
+    triple or any object with the attributes indptr, indices and data (a scipy CSR matrix; scipy itself is not needed)."""
     if all(hasattr(S, a) for a in ("indptr", "indices", "data")):
         S = (S.indptr, S.indices, S.data)
     try:
         indptr, indices, data = S
     except (TypeError, ValueError):
-        raise ValueError("S is None, (indptr, indices, data) or an object with those attributes") from None
+        raise ValueError("%s is %s(indptr, indices, data) or an object with those attributes"
+                         % (name, "None, " if name == "S" else "")) from None
     ip64, ix64 = np.asarray(indptr).ravel(), np.asarray(indices).ravel()
     if ip64.dtype.kind not in "iu" or (len(ix64) and ix64.dtype.kind not in "iu"):
-        raise ValueError("S: indptr and indices are integers")
+        raise ValueError("%s: indptr and indices are integers" % name)
     if len(ip64) and (ip64.max() > 2 ** 31 - 1 or ip64.min() < -2 ** 31):
-        raise ValueError("S: indptr beyond the int range")
+        raise ValueError("%s: indptr beyond the int range" % name)
     if len(ix64) and (ix64.max() > 2 ** 31 - 1 or ix64.min() < -2 ** 31):
-        raise ValueError("S: indices beyond the int range")
+        raise ValueError("%s: indices beyond the int range" % name)
     rp = np.ascontiguousarray(ip64, dtype=np.int32)
     cl = np.ascontiguousarray(ix64, dtype=np.int32)
     vl = np.ascontiguousarray(np.asarray(data, dtype=np.float64).ravel())
-    if len(rp) != n + 1 or len(cl) != len(vl) or (len(rp) and rp[-1] > len(vl)):
-        raise ValueError("S: indptr has n + 1 entries and points into indices / data of equal length")
+    if len(rp) != rows + 1 or len(cl) != len(vl) or (len(rp) and rp[-1] > len(vl)):
+        raise ValueError("%s: indptr has %s + 1 entries and points into indices / data of equal length"
+                         % (name, "n" if name == "S" else "rows"))
     return rp, cl, vl
+
+
+def structured_q_parts(S, n):
+    """csr_triple of the sparse part of a structured Q of order n, or (None, None, None) where S is None."""
+    if S is None:
+        return None, None, None
+    return csr_triple(S, n)
+
+
+def quadratic_q_forms(Q, n, who):
+    """(dense, (rp, cl, vl), rank, F, sigma) of a quadratic cone's Q as add_quadratic_csr and
+    Conex.AddSparseQuadraticConstraint take it: None (the identity), an (n, n) array, or the parts -- a dict with any of
+    the keys S, F, sigma, or a tuple (S, F, sigma) -- in the forms add_quadratic_structured takes.  Column-major
+    float64 copies; what is absent is None."""
+    none3 = (None, None, None)
+    if Q is None:
+        return None, none3, 0, None, None
+    if isinstance(Q, dict):
+        S, F, sigma = Q.get("S"), Q.get("F"), Q.get("sigma")
+    elif isinstance(Q, tuple) and len(Q) == 3:
+        S, F, sigma = Q
+    else:
+        Qa = np.asarray(Q, dtype=np.float64)
+        if Qa.shape != (n, n):
+            raise ValueError("%s: Q is None, (n, n), or the parts (S, F, sigma)" % who)
+        return _colmajor(Qa), none3, 0, None, None
+    rank, f, sg = 0, None, None
+    if F is not None:
+        F = np.asarray(F, dtype=np.float64)
+        if F.ndim != 2 or F.shape[0] != n:
+            raise ValueError("%s: F is (n, r)" % who)
+        rank = F.shape[1]
+        f = _colmajor(F)
+    if sigma is not None:
+        sg = np.ascontiguousarray(np.asarray(sigma, dtype=np.float64).ravel())
+        if len(sg) != rank:
+            raise ValueError("%s: sigma has one entry per column of F" % who)
+    if S is None and rank == 0:
+        raise ValueError("%s: neither a sparse part nor factors (for the identity pass Q = None)" % who)
+    return None, structured_q_parts(S, n), rank, f, sg
 
 
 class KktContext:
@@ -500,6 +542,31 @@ class KktContext:
     def count_structured_quadratic(self):
         """Constraints this context owns that were added by add_quadratic_structured."""
         return self.L.cxk_count_structured_quadratic(self.h)
+
+    def add_quadratic_csr(self, Q, A, c, vars_=None):
+        """The cone of add_quadratic / add_quadratic_structured with its (n + 1) x m matrix A given by its nonzeros and
+        never formed.  A: a triple (indptr, indices, data) or any object with those three attributes (a scipy CSR
+        matrix), row 0 is A0; columns in any order within a row, explicit zeros dropped; as many columns as vars_ has
+        entries (every variable without vars_).  Q: None (the identity), an (n, n) array, or the parts as a dict(S=, F=, sigma=) or a tuple (S, F, sigma), each as add_quadratic_structured
+        takes it."""
+        cc = np.ascontiguousarray(np.asarray(c, dtype=np.float64).ravel())
+        n = len(cc) - 1
+        rp, cl, vl = csr_triple(A, n + 1, "A")
+        keep, vp = self._vars(vars_)
+        m = self.num_vars if vars_ is None else len(keep)
+        dense, (qp, qc, qv), rank, f, sg = quadratic_q_forms(Q, n, "add_quadratic_csr")
+        r = self.L.cxk_add_quadratic_csr(
+            self.h, n, m, None if dense is None else _dp(dense), None if qp is None else _ip(qp), None if qp is None else _ip(qc),
+            None if qp is None else _dp(qv), rank, None if f is None or rank == 0 else _dp(f), None if sg is None else _dp(sg),
+            _ip(rp), _ip(cl), _dp(vl), _dp(cc), vp)
+        if r < 0:  # refused by name (the context stays usable)
+            raise KktError(self.L.cxk_last_error(self.h).decode() or "cxk_add_quadratic_csr: invalid arguments")
+        self.cons.append(("quad", n, m))
+        return r
+
+    def count_sparse_quadratic(self):
+        """Constraints this context owns that were added by add_quadratic_csr."""
+        return self.L.cxk_count_sparse_quadratic(self.h)
 
     def add_static(self, G, vars_):
         G = np.asarray(G, dtype=np.float64)

@@ -438,6 +438,37 @@ class Conex:
         self.num_constraints += 1
         return cid
 
+    def AddSparseQuadraticConstraint(self, Q, A, c, variables=None):
+        """The cone of AddQuadraticConstraint / AddStructuredQuadraticConstraint with its (n + 1) x m matrix A given by
+        its nonzeros and never formed (CONEX_HIP_AddSparseQuadraticConstraint).  A is a triple (indptr, indices, data)
+        or any object with those three attributes (a scipy CSR matrix); row 0 is A0, the columns of a row may come in
+        any order, explicit zeros are dropped; it has as many columns as `variables` has entries (every variable
+        without).  Q is None (the identity), an (n, n) array, or the parts in the forms AddStructuredQuadraticConstraint
+        takes, as a dict(S=, F=, sigma=) or a tuple (S, F, sigma).  Returns the constraint id."""
+        from .kkt import csr_triple, quadratic_q_forms
+        c = _f64(np.asarray(c, dtype=np.float64).ravel())
+        n = len(c) - 1
+        if n < 1:
+            raise ConexError("Invalid quadratic constraint.")
+        try:
+            rp, cl, vl = csr_triple(A, n + 1, "A")
+            dense, (qp, qc, qv), rank, Ff, sg = quadratic_q_forms(Q, n, "AddSparseQuadraticConstraint")
+        except ValueError as e:
+            raise ConexError("Invalid quadratic constraint: %s" % e) from None
+        v = None if variables is None else np.ascontiguousarray(np.asarray(variables).ravel(), dtype=np.int64)
+        m = self.m if v is None else len(v)
+        ip = C.POINTER(C.c_int)
+        cid = self._L.CONEX_HIP_AddSparseQuadraticConstraint(
+            self.a, n, None if dense is None else capi.dp(dense), None if qp is None else qp.ctypes.data_as(ip),
+            None if qp is None else qc.ctypes.data_as(ip), None if qp is None else capi.dp(qv), rank,
+            None if rank == 0 else capi.dp(Ff), None if sg is None else capi.dp(sg),
+            rp.ctypes.data_as(ip), cl.ctypes.data_as(ip), capi.dp(vl), n + 1, m, capi.dp(c), n + 1,
+            None if v is None else v.ctypes.data_as(C.POINTER(C.c_long)), 0 if v is None else len(v))
+        if cid < 0:
+            raise ConexError("Failed to add constraint.")
+        self.num_constraints += 1
+        return cid
+
     # ---- entry-by-entry builders
     def _new(self, fn, *args, what="constraint"):
         cid = C.c_int()

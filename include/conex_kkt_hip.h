@@ -356,8 +356,8 @@ int cxk_add_hermitian_factored(cxk_context* ctx, int n, int d, int m, const int*
  * doubles streamed per pass, (Q ? n n : 0) + (n + 1) m, reach the measured threshold (kQuadStreamMinWork;
  * CXK_STREAMED_QUADRATIC_MIN_WORK moves it for comparison runs).  Cones on the LDS route keep their kernels and
  * their bits.  Every output, getter and setter of a streamed cone is that of any quadratic cone.
- * A cone added by cxk_add_quadratic_structured (below) has no LDS form: it takes the streamed route under every mode,
- * 0 included.
+ * A cone added by cxk_add_quadratic_structured or cxk_add_quadratic_csr (below) has no LDS form: it takes the streamed
+ * route under every mode, 0 included.
  * Refused on the streamed route at cxk_finalize, by name: (dimension + 1) x variables, variables^2 or the entries
  * of Q beyond the int range; a group of equal cones with more than 2^31 columns, row tiles or blocks.
  * cxk_count_streamed_quadratic: constraints this context owns that run on the streamed route (-1 before
@@ -393,6 +393,39 @@ int cxk_add_quadratic_structured(cxk_context* ctx, int n, int m,
                                  const double* sigma /* rank, NULL = all +1 */,
                                  const double* A /* (n+1) x m */, const double* c /* n+1 */, const int* vars);
 int cxk_count_structured_quadratic(const cxk_context* ctx);
+
+/* The quadratic cone of cxk_add_quadratic or cxk_add_quadratic_structured with its (n + 1) x m matrix A given by its
+ * nonzeros and never formed: a risk bound over assets (A1 = [I 0], A0 = e_t), a generalised-least-squares residual
+ * that touches a few variables per row.
+ *   A      (n + 1) x m in CSR (a_rowptr: n + 2 ints from 0, a_col, a_val); row 0 is A0.  The columns of a row may
+ *          come in any order (the library sorts them); explicit zeros are dropped.
+ *   Q      n x n dense column-major, OR its parts as cxk_add_quadratic_structured takes them, OR neither (Q = NULL,
+ *          q_rowptr = NULL, rank = 0, F = NULL, sigma = NULL): the identity.
+ * Refused by name (cxk_last_error): a_rowptr[0] != 0 or decreasing, a column outside [0, m), a column named twice in
+ * a row, a value of a_val, c or Q that is not finite, a_rowptr or c null, Q given dense and by its parts, and every
+ * refusal cxk_add_quadratic_structured makes for the parts.
+ * The constraint keeps the nonzeros only: nothing of (n + 1) x m or n x m is allocated on the host or on the device
+ * at any point, cxk_finalize included, and the streamed route's refusal of (n + 1) x m beyond the int range does not
+ * apply; m^2, a dense Q's n^2 and the nonzeros of a group of equal cones must fit an int.  A host-only context takes
+ * the call; the problem's structure (cliques, fill, order) and every getter are those of cxk_add_quadratic with the
+ * same vars.
+ * Such a cone always runs on the streamed kernels, as a structured one does, under every mode of
+ * cxk_set_streamed_quadratic, 0 included, with the four places that read A replaced (kernels_quad_sparse.hip.h):
+ * v = A'(W0, Q w1) by one wavefront per column through the CSC (u = A1' Q c1 is constant and made once at
+ * cxk_finalize), row 0 from a dense copy of it, the slack by the sparse second-order cones' kernel, and
+ * A_gram = A1' Q A1 at cxk_finalize in panels of a few columns (work space 2 n P doubles per cone).  Cones of equal
+ * (n, m, form of Q, rank) share a group whatever their patterns.  No atomics, fixed summation orders: same bits every
+ * run, and the bits of ascending input whatever the order of the columns given.
+ * cxk_count_sparse_quadratic: constraints this context owns that were added this way (-1 before cxk_finalize; 0 on a
+ * host-only context, which chooses no kernels); they count in cxk_count_streamed_quadratic too, and in
+ * cxk_count_structured_quadratic when Q came by its parts. */
+int cxk_add_quadratic_csr(cxk_context* ctx, int n, int m,
+                          const double* Q /* n x n dense, or NULL */,
+                          const int* q_rowptr, const int* q_col, const double* q_val,
+                          int rank, const double* F, const double* sigma /* as cxk_add_quadratic_structured; all absent = none */,
+                          const int* a_rowptr /* n + 2 */, const int* a_col, const double* a_val,
+                          const double* c /* n + 1 */, const int* vars);
+int cxk_count_sparse_quadratic(const cxk_context* ctx);
 
 /* Initialize(): symbolic analysis (SupernodalKKTSolver ctor kkt_solver.cc:104-116),
  * Bind (kkt_solver.h:26-33), workspace carve + SetIdentity (cone_program.cc:78-112),
